@@ -9,7 +9,7 @@ framebuffer are resident in HBM before the timed region.  At N > 1 the frame is 
 its tiles into a rank-compact staging buffer and the packed pixels are gathered to rank 0 with ONE
 ncclSend / ncclRecv group (C ABI: rt_comm_* / rt_render_gather_device) inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Frames are enqueued on two streams alternately (two frames in flight, each into its own frame buffer): a launch cannot
@@ -20,6 +20,9 @@ frame; the K steps are bracketed by barrier + synchronise.
 Rank 0 prints ONE JSON line.  `value` = (primary + reflection + refraction rays of one frame as the
 reference casts them, all ranks) / (max-over-ranks seconds per frame), in Mray/s; `value_traced` = the rays the GPU
 traced (repeated AA samples once) over the same time.
+
+--dump-outputs DIR writes the frame of the last timed step, as the caller's buffer holds it, to DIR (dump_outputs below):
+the scene and its sample tables are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -32,10 +35,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# HIP maps its streams onto a few hardware queues (4 by default); two streams that share one run their work one after
-# the other.  This process uses two render streams, the library's gather stream and whatever torch.distributed creates:
-# give them queues of their own, so that two frames in flight really overlap.  (Must be set before HIP initialises.)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np  # noqa: E402
 
@@ -97,6 +96,30 @@ def build_workload(key):
     else:
         flat = scenes.test_scene(cfg).flatten().without_triangles()
     return cfg, flat, w["name"]
+
+
+DUMP_BUDGET = 64_000_000  # bytes of .npy files --dump-outputs may write in all
+
+
+def dump_outputs(out_dir, argb, width, height):
+    """--dump-outputs: the frame a caller of the timed path receives (W*H packed 0xAARRGGBB words, row-major) as float32
+    channels [A, R, G, B] (0..255) in out_dir/frame.npy, shape (height, width, 4).  A frame over DUMP_BUDGET is replaced
+    by a fixed sample of its pixels (seed 0, ascending): frame.npy (n, 4) and their row-major indices in
+    frame_pixels.npy (float64, exact).  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    px = np.ascontiguousarray(argb).view(np.uint32).reshape(-1)
+    assert px.size == width * height
+    channels = np.stack([(px >> s) & 0xFF for s in (24, 16, 8, 0)], axis=-1).astype(np.float32)
+    header = 128  # bytes of an .npy header
+    if channels.nbytes + header <= DUMP_BUDGET:
+        arrays = {"frame": channels.reshape(height, width, 4)}
+    else:
+        n = (DUMP_BUDGET - 2 * header) // (channels.itemsize * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(px.size, n, replace=False))
+        arrays = {"frame": channels[idx], "frame_pixels": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def pmc_summary(workload, build_id):
@@ -276,7 +299,11 @@ def main():
                          "launch, 3 = levels traced back to back, each shaded on one of two streams as soon as it is sorted")
     ap.add_argument("--backend", default=os.environ.get("RT_BENCH_BACKEND", "nccl"), choices=["nccl", "gloo"],
                     help="nccl (= RCCL, the real path); gloo only to rehearse N > 1 on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/*.npy (rank 0: the gathered frame)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -354,6 +381,8 @@ def main():
         frame(i)
     barrier()
     elapsed = time.perf_counter() - t0
+    # the last timed step's frame, before the frames below reuse its buffer
+    last_frame = fbs[(args.steps - 1) % n_fly].cpu().numpy() if (args.dump_outputs and rank == 0) else None
     # The dominant kernel's launch duration, for the roofline: frames one after the other on ONE stream, each bracketed by
     # events on that stream (with two frames in flight a launch shares the GPU with its neighbour and its duration says
     # nothing about the kernel).  Outside the timed region.
@@ -523,6 +552,8 @@ def main():
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, flat)
             out["cpu_baseline"]["gpu_over_cpu"] = mrays / out["cpu_baseline"]["value"]
+        if last_frame is not None:
+            out["outputs"] = dump_outputs(args.dump_outputs, last_frame, cfg.width, cfg.height)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()
