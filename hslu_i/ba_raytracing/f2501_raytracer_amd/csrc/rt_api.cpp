@@ -464,8 +464,8 @@ int rt_validate_params(const rt_params* p) {
   if (p->n_ranks > 1 && p->rank >= p->n_ranks) return fail(RT_ERR_INVALID_ARG, "rank out of range");
   if (p->n_ranks > 1 && p->tile_size != 0 && p->tile_size < 16) return fail(RT_ERR_UNSUPPORTED, "tile_size < 16");
   if (p->traversal > RT_TRAVERSAL_LINEAR) return fail(RT_ERR_INVALID_ARG, "unknown traversal mode");
-  if (p->max_depth_reflection > 64 || p->max_depth_refraction > 64)
-    return fail(RT_ERR_UNSUPPORTED, "recursion depth > 64");
+  if (p->max_depth_reflection > RT_MAX_DEPTH || p->max_depth_refraction > RT_MAX_DEPTH)
+    return fail(RT_ERR_UNSUPPORTED, "recursion depth > %u", RT_MAX_DEPTH);
   if (p->tuning.shadow_candidate_cap > 64u && p->tuning.shadow_candidate_cap != RT_CAND_CAP_NONE)
     return fail(RT_ERR_INVALID_ARG, "tuning.shadow_candidate_cap > 64");
   if (p->tuning.chunk_log2 && (p->tuning.chunk_log2 < 10u || p->tuning.chunk_log2 > 26u))
@@ -761,27 +761,18 @@ static int prepare(rt_scene* s, const rt_params* p, uint32_t* argb_dev, const rt
 // what the counters say was needed and the frame is rendered again.  A verified shape renders asynchronously from then
 // on (the scene is static, so its ray counts repeat exactly).  Pixel sums use a fixed-point accumulator (order
 // independent, hence bit-reproducible), resolved to packed pixels by a last kernel.
+// render_frame_impl runs these as stages: plan_schedule, take_workspace, match_stream_key, then per attempt size_queues,
+// set_up_chains, enqueue_chains (enqueue_primary + enqueue_merged_levels / enqueue_chained_levels per batch) and finish_frame.
 static const size_t RT_QUEUE_BUDGET = (size_t)160 << 30;  // hard ceiling; the real limit is half of the free HBM
-#define RT_CNT_OVERFLOW 0u                       // dropped children
-#define RT_CNT_LEVEL(k) (k)                      // 1 .. levels + 1: rays appended to level k (dropped ones included)
-#define RT_CNT_HARD(levels) ((levels) + 2u)      // hard pairs waiting
-#define RT_CNT_HARD_STAT(levels) ((levels) + 3u) // [0] dropped pairs, [1] largest batch of pairs
-#define RT_CNT_HITS(levels, k) ((levels) + 5u + (k))  // rays of level k that hit something
-#define RT_CNT_SETS(levels, k, c) (2u * (levels) + 8u + 3u * (k) + (c))  // phase-split pipeline: sets of class c at level k = 0 .. levels
-#define RT_CNT_SEG(levels, k) (2u * (levels) + 8u + 3u * ((levels) + 1u) + (k))  // merged levels: first queue index of level k = 1 .. levels + 1
-#define RT_CNT_TOTAL(levels) (2u * (levels) + 8u + 3u * ((levels) + 1u) + (levels) + 2u)
+// phase-split pipeline: bytes of a (wavefront, light) set record (header, 64-dword candidate list, slots in 3 class queues, class)
+static const uint32_t RT_SET_RECORD_BYTES = 32u + 256u + 12u + 1u;
 
 // Diagnostics: RT_TRACE_LAUNCHES=1 in the environment makes every launch of a frame wait for its kernel and report it on
 // stderr (which launch of which level does not come back, with which sizes); never set in timed runs.
-static bool trace_launches() {
-  static const bool on = [] {
-    const char* v = getenv("RT_TRACE_LAUNCHES");
-    return v && *v && *v != '0';
-  }();
-  return on;
-}
 static void trace_point(hipStream_t stream, const char* what, uint32_t a, uint32_t b, uint32_t c) {
-  if (!trace_launches()) return;
+  static const char* const v = getenv("RT_TRACE_LAUNCHES");
+  static const bool on = v && *v && *v != '0';
+  if (!on) return;
   fprintf(stderr, "[rt_hip] %s (%u, %u, %u) launched ...", what, a, b, c);
   fflush(stderr);
   const hipError_t e = hipStreamSynchronize(stream);
@@ -789,85 +780,95 @@ static void trace_point(hipStream_t stream, const char* what, uint32_t a, uint32
   fflush(stderr);
 }
 
+// the result of a kernel launch on `stream`: "<what> failed: <HIP error>", or its RT_TRACE_LAUNCHES point (when it has a label)
+static int launched(int err, hipStream_t stream, const char* what, const char* label = nullptr, uint32_t a = 0, uint32_t b = 0, uint32_t c = 0) {
+  if ((hipError_t)err != hipSuccess) return fail(RT_ERR_HIP, "%s failed: %s", what, hipGetErrorString((hipError_t)err));
+  if (label) trace_point(stream, label, a, b, c);
+  return RT_OK;
+}
+#define RC_TRY(expr) do { const int rc_ = (expr); if (rc_ != RT_OK) return rc_; } while (0)
+
 static uint32_t grid_for(uint64_t items, uint32_t per_wg, uint32_t cap_wgs) {
   uint64_t w = (items + items / 16u + per_wg - 1u) / per_wg + 8u;  // a little above the guess; the loop covers the rest
   if (w > cap_wgs) w = cap_wgs;
   return w ? (uint32_t)w : 1u;
 }
-
-static int render_frame_impl(rt_scene* s, RtDevParams& P, hipStream_t stream, uint32_t forced_chunk_log2, bool blocking);
+static uint32_t cap32(uint64_t n) { return (uint32_t)std::min<uint64_t>(n, 0xFFFFFF00ull); }  // (16-byte aligned arrays behind a queue)
 
 // how the levels of a ray tree are run (rt_tuning.levels)
 // (measured, round 4: MERGED config 4 40.6 ms alone / 39.3 with two frames in flight against 49.8 / 42.6 CHAINED, config 5 120.4 / 118.4
 // against 126.4 / 122.3; PIPELINED 47.7 / 42.9 and 129.4 / 123.3: one hit-point order over all levels is worth more than the overlap)
-static uint32_t rt_levels_mode(uint32_t wanted) {
-  if (wanted == RT_LEVELS_DEFAULT) return RT_LEVELS_MERGED;
-  return wanted;
-}
+static uint32_t rt_levels_mode(uint32_t wanted) { return wanted == RT_LEVELS_DEFAULT ? RT_LEVELS_MERGED : wanted; }
 
-// which form of the render loop a frame takes (rt_tuning.phases; RT_PHASES_DEFAULT: by frame shape)
-static bool rt_use_phases(uint32_t wanted, const RtDevParams& P, bool secondary) {
-  if (P.cost_map) return false;  // (the calibration frame of RT_TILE_ORDER_COST times the fused primary kernel)
-  if (wanted == RT_PHASES_SPLIT) return true;
-  if (wanted == RT_PHASES_FUSED) return false;
-  (void)secondary;
-  return false;
-}
+// which form of the render loop a frame takes (rt_tuning.phases; RT_PHASES_DEFAULT: by frame shape; the calibration frame of
+// RT_TILE_ORDER_COST times the fused primary kernel)
+static bool rt_use_phases(uint32_t wanted, const RtDevParams& P) { return !P.cost_map && wanted == RT_PHASES_SPLIT; }
 
-// A frame that fails half-way (HIP / launch error, out of memory) leaves partial sums in the pixel accumulator: mark
-// the accumulator dirty so that the next frame clears it.
-static int render_frame(rt_scene* s, RtDevParams& P, hipStream_t stream, uint32_t forced_chunk_log2, bool blocking = false) {
-  const int rc = render_frame_impl(s, P, stream, forced_chunk_log2, blocking);
-  if (rc != RT_OK) s->ws[s->cur_ws].acc_pixels = 0;
-  // marks the end of this frame's use of its counter block (prepare() of a later frame waits for it)
-  if (hipEventRecord(s->frame_ev[s->cur_block], stream) == hipSuccess) s->frame_pending[s->cur_block] = true;
-  s->last_block = s->cur_block;
-  return rc;
-}
-
-static int render_frame_impl(rt_scene* s, RtDevParams& P, hipStream_t stream, uint32_t forced_chunk_log2, bool blocking) {
-  const bool secondary = (P.flags & (RT_FLAG_REFLECTIONS | RT_FLAG_REFRACTIONS)) != 0;
-  const uint32_t total_wgs = rt_primary_total_wgs(P);
-  s->queue_bytes = 0;
-  // The phase-split pipeline (rt_phases.h; rt_tuning.phases): hit -> classify -> one kernel per class of (wavefront, light)
-  // set -> resolve, instead of the fused kernels.  Frames without secondary rays then also sum through the accumulator.
-  const bool split = rt_use_phases(s->phases_wanted, P, secondary);
-  P.resolve_counts_written = split ? 1u : 0u;
-  // RT_PHASES_FUSED_DEFER: the fused kernels, but a frame without secondary rays also sums through the accumulator, so that its
-  // incoherent (wavefront, light) sets can be deferred to rt_hard_kernel like those of a frame with secondary rays
-  const bool defer = !secondary && !split && !P.cost_map && s->phases_wanted == RT_PHASES_FUSED_DEFER && P.light_mult > 1;
-  if (!secondary && !split && !defer) {
-    P.acc = nullptr;
-    P.q_out = nullptr;
-    P.batch_first_wg = 0, P.batch_stride = 1, P.batch_group_log2 = 0;
-    hipError_t e = (hipError_t)rt_launch_primary(s->dev, P, total_wgs, stream);
-    if (e != hipSuccess) return fail(RT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    trace_point(stream, "rt_primary_kernel: workgroups", total_wgs);
-    return RT_OK;
+// What the stages of one accumulated frame share.  Side chains and shade streams with work in flight drain when it goes out of scope,
+// on every error path: their work refers to the workspace set, and only the caller's stream is guarded by the frame event.
+struct Frame {
+  rt_scene* s;
+  RtDevParams& P;
+  hipStream_t stream;
+  uint32_t forced;  // rt_tuning.chunk_log2: batch size under test (0: sized by need)
+  bool blocking;
+  // ---- plan (hard: soft-shadow sets of incoherent wavefronts deferred to rt_hard_kernel; merged: one append-only queue per chain)
+  bool secondary, split, defer, hard = false, merged = false, pipelined = false;
+  uint32_t total_wgs, levels = 0, levels_mode = RT_LEVELS_CHAINED, lanes = 1, n_cnt = 0;
+  uint64_t items = 0;  // primary work items (threads) of the frame
+  rt_scene::StreamWs* w = nullptr;
+  // ---- sizes of the current attempt; guess: grids from the previous frame's counts (else: whole capacity)
+  uint32_t n_buckets = 0, q_sort_cap = 0, set_cap = 0, n_batches = 0, cap_wgs = 0, pairs_per_wg = 0, hard_cap_wgs = 0;
+  size_t hitrec_items = 0;
+  bool guess = false;
+  // ---- the chains: the caller's parameters with the chain's own queues and counters; what is in flight on their streams
+  RtDevParams Pl[RT_LANES];
+  float4* q[RT_LANES][2];
+  uint32_t* counts[RT_LANES];
+  bool forked = false, joined = false, shading = false;
+  Frame(rt_scene* s_, RtDevParams& P_, hipStream_t stream_, uint32_t forced_, bool blocking_)
+      : s(s_), P(P_), stream(stream_), forced(forced_), blocking(blocking_), secondary((P.flags & (RT_FLAG_REFLECTIONS | RT_FLAG_REFRACTIONS)) != 0) {
+    total_wgs = rt_primary_total_wgs(P);
+    // The phase-split pipeline (rt_phases.h; rt_tuning.phases): hit -> classify -> one kernel per class of (wavefront, light)
+    // set -> resolve, instead of the fused kernels.  Frames without secondary rays then also sum through the accumulator.
+    split = rt_use_phases(s->phases_wanted, P);
+    // RT_PHASES_FUSED_DEFER: the fused kernels, but a frame without secondary rays also sums through the accumulator, so that its
+    // incoherent (wavefront, light) sets can be deferred to rt_hard_kernel like those of a frame with secondary rays
+    defer = !secondary && !split && !P.cost_map && s->phases_wanted == RT_PHASES_FUSED_DEFER && P.light_mult > 1;
   }
-  int rc;
-  if (total_wgs == 0) return RT_OK;  // this rank owns no tile inside the window (more ranks than tiles): nothing to trace, nothing to resolve
-  const uint32_t levels = !secondary ? 0u : (P.max_depth_reflection > P.max_depth_refraction ? P.max_depth_reflection : P.max_depth_refraction);
-  if (secondary && levels == 0) return fail(RT_ERR_INVALID_ARG, "secondary rays enabled with depth 0");
-  const size_t npix = (size_t)P.width * P.height;
-  const uint64_t items = (uint64_t)total_wgs * 256u;  // primary work items (threads) of the frame
-  // Soft-shadow sets of incoherent wavefronts are deferred to rt_hard_kernel as (hit point, light) pairs
-  const bool hard = (secondary || split || defer) && P.light_mult > 1 && P.light_mult <= 64 && P.traversal == RT_TRAVERSAL_BVH && s->dev.n_triangles && P.cand_cap != 0;
-  if (!hard && P.light_mult > 1) s->notes |= RT_NOTE_HARD_PAIRS_OFF;
+  ~Frame() {
+    for (uint32_t j = 1; j < lanes && forked && !joined; j++) (void)hipStreamSynchronize(w->lane[j].stream);
+    for (uint32_t j = 0; j < lanes && shading; j++)
+      for (hipStream_t ss : w->lane[j].shade_stream)
+        if (ss) (void)hipStreamSynchronize(ss);
+  }
+  // a grid over the rays (or hits) of counter `idx` of chain j in the last frame of this shape
+  uint32_t ray_grid(uint32_t j, uint32_t idx) const { return guess ? grid_for(s->est[j][idx], 256u, cap_wgs) : cap_wgs; }
+};
+
+// ---- plan: depth, pair deferral, level schedule, chains
+static int plan_schedule(Frame& f) {
+  rt_scene* s = f.s;
+  const RtDevParams& P = f.P;
+  f.levels = !f.secondary ? 0u : std::max(P.max_depth_reflection, P.max_depth_refraction);
+  if (f.secondary && f.levels == 0) return fail(RT_ERR_INVALID_ARG, "secondary rays enabled with depth 0");
+  f.items = (uint64_t)f.total_wgs * 256u;
+  f.hard = (f.secondary || f.split || f.defer) && P.light_mult > 1 && P.light_mult <= 64 && P.traversal == RT_TRAVERSAL_BVH &&
+           s->dev.n_triangles && P.cand_cap != 0;
+  if (!f.hard && P.light_mult > 1) s->notes |= RT_NOTE_HARD_PAIRS_OFF;
   // merged levels (rt_tuning.levels): every level traced first (the trace kernel appends the children), then ONE sort and ONE shade launch
-  uint32_t levels_mode = (secondary && !split) ? rt_levels_mode(s->levels_wanted) : RT_LEVELS_CHAINED;
-  if (levels_mode == RT_LEVELS_MERGED && s->levels_wanted == RT_LEVELS_DEFAULT) {
+  f.levels_mode = (f.secondary && !f.split) ? rt_levels_mode(s->levels_wanted) : RT_LEVELS_CHAINED;
+  if (f.levels_mode == RT_LEVELS_MERGED && s->levels_wanted == RT_LEVELS_DEFAULT) {
     // The merged queue holds every level of the tree at once (config 4: 5.0 GB against the 2.9 GB of two alternating queues).  Where a
     // third of the free memory (plus what this scene's workspaces already hold) does not take about four times the primary work items,
     // the library's choice is the chained schedule rather than a frame cut into batches.
     size_t free_b = 0, total_b = 0, held = 0;
     for (const auto& o : s->ws) held += o.bytes();
-    const uint64_t want = (uint64_t)total_wgs * 256u * 4u * (64u + 12u);
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || want > (free_b + held) / 3u) levels_mode = RT_LEVELS_CHAINED;
+    const uint64_t want = (uint64_t)f.total_wgs * 256u * 4u * (64u + 12u);
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || want > (free_b + held) / 3u) f.levels_mode = RT_LEVELS_CHAINED;
   }
-  const bool pipelined = levels_mode == RT_LEVELS_PIPELINED;
-  const bool merged = levels_mode == RT_LEVELS_MERGED || pipelined;  // (one append-only queue per chain, children spawned by the trace kernel)
-  const uint32_t n_cnt = RT_CNT_TOTAL(levels);
+  f.pipelined = f.levels_mode == RT_LEVELS_PIPELINED, f.merged = f.levels_mode == RT_LEVELS_MERGED || f.pipelined;
+  f.n_cnt = RT_CNT_TOTAL(f.levels);
   // ---- chains.  The ray tree of a frame is a chain of launches, one per level, each with a drain of its own (a launch
   // cannot end before its longest wavefront does).  A frame that has the GPU to itself is therefore split into two
   // interleaved halves of its primary work-group list that run as independent chains -- own queues, own counters, own
@@ -876,65 +877,71 @@ static int render_frame_impl(rt_scene* s, RtDevParams& P, hipStream_t stream, ui
   // frames in flight itself the other FRAME is the better filler (42.3 ms against 43.3 with chains on top): sub_frames = 0
   // uses two chains only while no other frame of the scene is running (and stays with one for 8 frames after the last
   // overlap, so that a pipeline that drains now and then does not flip -- every flip re-verifies the queue sizes).
-  uint32_t lanes = s->lanes_wanted ? std::min<uint32_t>(s->lanes_wanted, RT_LANES) : RT_LANES;
+  f.lanes = s->lanes_wanted ? std::min<uint32_t>(s->lanes_wanted, RT_LANES) : RT_LANES;
   if (!s->lanes_wanted) {
     bool busy = false;
     for (int b = 0; b < RT_SLOTS; b++)
       if (b != s->cur_block && s->frame_pending[b] && hipEventQuery(s->frame_ev[b]) == hipErrorNotReady) busy = true;
     s->calm_frames = busy ? 0u : std::min<uint32_t>(s->calm_frames + 1u, 1u << 30);
-    if (s->calm_frames < 8u) lanes = 1;
+    if (s->calm_frames < 8u) f.lanes = 1;
   }
-  if (forced_chunk_log2 || items < (1ull << 16) || (!secondary && !s->lanes_wanted)) lanes = 1;
-  if (merged && !s->lanes_wanted) lanes = 1;  // (measured: two chains add nothing once the levels share one shade launch)  // (forced batch sizes: the batching itself is under test; tiny frames: nothing to overlap)
-  // This frame's workspace set: the one of its slot -- unless that would mean ALLOCATING a second set on a device that
-  // cannot spare the memory (a partitioned or shared GPU): then the frame waits for the frame that uses set 0 and takes it.
+  // (forced batch sizes: the batching itself is under test; tiny frames: nothing to overlap)
+  if (f.forced || f.items < (1ull << 16) || (!f.secondary && !s->lanes_wanted)) f.lanes = 1;
+  if (f.merged && !s->lanes_wanted) f.lanes = 1;  // (measured: two chains add nothing once the levels share one shade launch)
+  return RT_OK;
+}
+
+// ---- workspace: this frame's set -- the one of its slot, unless that would mean ALLOCATING a second set on a device that cannot
+// spare the memory (a partitioned or shared GPU): then the frame waits for the frame that uses set 0 and takes it.
+static int take_workspace(Frame& f) {
+  rt_scene* s = f.s;
   int wsi = s->cur_block;
   if (wsi > 0 && !s->ws[wsi].lane[0].queues.p && s->ws[0].lane[0].queues.p) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 3 * s->ws[0].bytes()) wsi = 0;
   }
   if (s->ws_last_block[wsi] != s->cur_block && s->frame_pending[s->ws_last_block[wsi]])
-    HIP_TRY(hipStreamWaitEvent(stream, s->frame_ev[s->ws_last_block[wsi]], 0));
+    HIP_TRY(hipStreamWaitEvent(f.stream, s->frame_ev[s->ws_last_block[wsi]], 0));
   s->ws_last_block[wsi] = s->cur_block;
   s->cur_ws = wsi;
-  rt_scene::StreamWs& w = s->ws[wsi];
-  for (uint32_t j = 0; j < lanes; j++) {
-    if ((rc = w.lane[j].qcount.ensure((size_t)n_cnt * 4)) != RT_OK) return rc;
+  rt_scene::StreamWs& w = *(f.w = &s->ws[wsi]);
+  for (uint32_t j = 0; j < f.lanes; j++) {
+    RC_TRY(w.lane[j].qcount.ensure((size_t)f.n_cnt * 4));
     if (j && !w.lane[j].stream) HIP_TRY(hipStreamCreateWithFlags(&w.lane[j].stream, hipStreamNonBlocking));
     if (j && !w.lane[j].done_ev) HIP_TRY(hipEventCreateWithFlags(&w.lane[j].done_ev, hipEventDisableTiming));
   }
-  for (uint32_t j = lanes; j < RT_LANES; j++)  // memory by need: a set that runs one chain does not keep the other chain's queues
-    if (w.lane[j].queues.p || w.lane[j].trace_ws.p || w.lane[j].hard.p || w.lane[j].hitrec.p || w.lane[j].sets.p) {
-      if (w.lane[j].stream) HIP_TRY(hipStreamSynchronize(w.lane[j].stream));
-      HIP_TRY(hipStreamSynchronize(stream));  // (behind the wait for the set's last frame enqueued above)
-      w.lane[j].queues.release(), w.lane[j].trace_ws.release(), w.lane[j].hard.release(), w.lane[j].hitrec.release(), w.lane[j].sets.release();
-      w.lane[j].sort_hist_clean = nullptr;
+  for (rt_scene::Lane* L = w.lane + f.lanes; L < w.lane + RT_LANES; L++)  // memory by need: a set that runs one chain does not keep the other chain's queues
+    if (L->queues.p || L->trace_ws.p || L->hard.p || L->hitrec.p || L->sets.p) {
+      if (L->stream) HIP_TRY(hipStreamSynchronize(L->stream));
+      HIP_TRY(hipStreamSynchronize(f.stream));  // (behind the wait for the set's last frame enqueued above)
+      L->queues.release(), L->trace_ws.release(), L->hard.release(), L->hitrec.release(), L->sets.release();
+      L->sort_hist_clean = nullptr;
     }
   if (!w.cnt_host) HIP_TRY(hipHostMalloc((void**)&w.cnt_host, RT_LANES * RT_CNT_STRIDE * 4, hipHostMallocDefault));
   if (!w.cnt_ev) HIP_TRY(hipEventCreateWithFlags(&w.cnt_ev, hipEventDisableTiming));
   if (!w.fork_ev) HIP_TRY(hipEventCreateWithFlags(&w.fork_ev, hipEventDisableTiming));
+  return RT_OK;
+}
 
-  // ---- the shape of this frame: what its ray counts depend on.  Same key as the last verified frame = same counts.
+// ---- the shape of this frame: what its ray counts depend on.  Same key as the last verified frame = same counts.  Then the counts
+// of earlier frames of this shape whose read-back has landed.
+static void match_stream_key(Frame& f) {
+  rt_scene* s = f.s;
+  const RtDevParams& P = f.P;
   StreamKey key;
   memset(&key, 0, sizeof(key));
   key.width = P.width, key.height = P.height, key.flags = P.flags, key.aa_rays = P.aa_rays, key.aa_unique = P.aa_unique;
   key.light_mult = P.light_mult, key.depth_refl = P.max_depth_reflection, key.depth_refr = P.max_depth_refraction;
   key.win[0] = P.win_x0, key.win[1] = P.win_y0, key.win[2] = P.win_w, key.win[3] = P.win_h;
   key.tile_size = P.tile_size, key.n_ranks = P.n_ranks, key.rank = P.rank, key.traversal = P.traversal, key.cand_cap = P.cand_cap;
-  key.cloud_seed = P.cloud_seed, key.n_cloud_sets = P.n_cloud_sets, key.forced = forced_chunk_log2;
-  key.tables = s->tables_version;
+  key.cloud_seed = P.cloud_seed, key.n_cloud_sets = P.n_cloud_sets, key.forced = f.forced, key.tables = s->tables_version;
   memcpy(key.f, P.focus, 12), key.f[3] = P.fw, key.f[4] = P.fh, key.f[5] = P.fd, key.f[6] = P.eps_distance, key.f[7] = P.air_ior;
-  key.staged = P.stage_slot != nullptr, key.flags_on = P.recv_flags != nullptr, key.n_sup = P.n_sup, key.lanes = lanes;
-  key.merged = levels_mode;
-  key.split = (split ? 1u : 0u) | (defer ? 2u : 0u), key.sort_bits = s->sort_bits_wanted, key.lists_on = P.cell_lists != nullptr;
+  key.staged = P.stage_slot != nullptr, key.flags_on = P.recv_flags != nullptr, key.n_sup = P.n_sup, key.lanes = f.lanes, key.merged = f.levels_mode;
+  key.split = (f.split ? 1u : 0u) | (f.defer ? 2u : 0u), key.sort_bits = s->sort_bits_wanted, key.lists_on = P.cell_lists != nullptr;
   if (memcmp(&key, &s->stream_key, sizeof(key)) != 0) {
-    s->stream_key = key;
-    s->key_gen++;
-    s->stream_verified = false;
-    s->est_valid = false;
+    s->stream_key = key, s->key_gen++, s->stream_verified = false, s->est_valid = false;
     s->q_cap = s->hard_cap = s->batch_items = 0;
   }
-  // the counts of an earlier frame of this shape, if their read-back has landed
   for (auto& o : s->ws)
     if (o.cnt_pending && hipEventQuery(o.cnt_ev) == hipSuccess) {
       o.cnt_pending = false;
@@ -947,418 +954,405 @@ static int render_frame_impl(rt_scene* s, RtDevParams& P, hipStream_t stream, ui
         const uint32_t* c = o.cnt_host + (size_t)j * RT_CNT_STRIDE;
         if (c[RT_CNT_OVERFLOW] || c[RT_CNT_HARD_STAT(o.cnt_host_levels)]) {
           dropped_any = true;
-          s->hard_cap = std::max<uint32_t>(s->hard_cap, (uint32_t)std::min<uint64_t>((uint64_t)c[RT_CNT_HARD_STAT(o.cnt_host_levels) + 1u] * 5u / 4u + 256u, 0xFFFFFF00ull));
+          s->hard_cap = std::max<uint32_t>(s->hard_cap, cap32((uint64_t)c[RT_CNT_HARD_STAT(o.cnt_host_levels) + 1u] * 5u / 4u + 256u));
         }
       }
       if (dropped_any) {
-        s->stream_verified = false, s->est_valid = false;
-        s->sticky_notes |= RT_NOTE_FRAME_DROPPED_WORK;
+        s->stream_verified = false, s->est_valid = false, s->sticky_notes |= RT_NOTE_FRAME_DROPPED_WORK;
         continue;
       }
-      if (o.cnt_host_levels == levels && o.cnt_host_lanes == lanes && o.cnt_host_valid) memcpy(s->est, o.cnt_host, sizeof(s->est)), s->est_valid = true;
+      if (o.cnt_host_levels == f.levels && o.cnt_host_lanes == f.lanes && o.cnt_host_valid) memcpy(s->est, o.cnt_host, sizeof(s->est)), s->est_valid = true;
     }
+}
 
-  // chains other than the caller's must have drained before this function returns on an error path (their work refers to
-  // the workspace set; only the caller's stream is guarded by the frame event)
-  struct Joiner {
-    rt_scene::StreamWs& w;
-    uint32_t lanes;
-    bool forked = false, joined = false;
-    bool shading = false;  // pipelined levels: work is in flight on the chains' shade streams
-    ~Joiner() {
-      if (forked && !joined)
-        for (uint32_t j = 1; j < lanes; j++) (void)hipStreamSynchronize(w.lane[j].stream);
-      if (shading)
-        for (uint32_t j = 0; j < lanes; j++)
-          for (int k = 0; k < 2; k++)
-            if (w.lane[j].shade_stream[k]) (void)hipStreamSynchronize(w.lane[j].shade_stream[k]);
-    }
-  } joiner{w, lanes};
+// smaller primary batches, queues and pair buffer in proportion (rays per queue no fewer than q_floor)
+static void shrink_sizes(rt_scene* s, bool hard, uint32_t q_floor) {
+  s->q_cap = std::max<uint32_t>(s->q_cap / 2u, q_floor);
+  s->hard_cap = hard ? std::max<uint32_t>(s->hard_cap / 2u, 1u << 16) : 0u;
+  s->batch_items = std::max<uint32_t>(s->batch_items / 2u, 1u << 10);
+}
 
-  for (int attempt = 0;; attempt++) {
-    // ---- sizes, per chain.  Unknown shape: every level fits the chain's primary work items (children usually thin out; a
-    // scene where they multiply is caught by the verification below), pairs = 1/8 of that.  Budget: half of the free HBM.
-    if (!s->q_cap) {
-      if (forced_chunk_log2) {
-        s->batch_items = 1u << forced_chunk_log2;
-        s->q_cap = 2u * s->batch_items;
-      } else {
-        const uint64_t lane_items = ((uint64_t)total_wgs + lanes - 1u) / lanes * 256u;
-        s->batch_items = (uint32_t)std::min<uint64_t>(lane_items, 1ull << 28);
-        // (merged levels: ONE queue of 2 q_cap rays holds every level of the tree -- three times the primary work items as a first guess)
-        s->q_cap = merged ? (uint32_t)std::min<uint64_t>((uint64_t)s->batch_items * 3u / 2u, 0x7FFFFF00ull) : s->batch_items;
-      }
-      if (s->q_cap < (1u << 16)) s->q_cap = 1u << 16;
-      s->hard_cap = hard ? std::max<uint32_t>(s->q_cap / 8u, 1u << 16) : 0u;
+// ---- sizes, per chain, and the workspaces that hold them.  Unknown shape: every level fits the chain's primary work items
+// (children usually thin out; a scene where they multiply is caught by the verification), pairs = 1/8 of that.  Budget: half
+// of the free HBM.  `oom`: an allocation failed, the sizes were halved -- try again.
+static int size_queues(Frame& f, int attempt, bool& oom) {
+  rt_scene* s = f.s;
+  rt_scene::StreamWs& w = *f.w;
+  if (!s->q_cap) {
+    if (f.forced) {
+      s->batch_items = 1u << f.forced;
+      s->q_cap = 2u * s->batch_items;
+    } else {
+      const uint64_t lane_items = ((uint64_t)f.total_wgs + f.lanes - 1u) / f.lanes * 256u;
+      s->batch_items = (uint32_t)std::min<uint64_t>(lane_items, 1ull << 28);
+      // (merged levels: ONE queue of 2 q_cap rays holds every level of the tree -- three times the primary work items as a first guess)
+      s->q_cap = f.merged ? (uint32_t)std::min<uint64_t>((uint64_t)s->batch_items * 3u / 2u, 0x7FFFFF00ull) : s->batch_items;
     }
-    size_t budget = RT_QUEUE_BUDGET, free_b = 0, total_b = 0;
-    const size_t held = w.bytes() - w.acc.cap;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, (size_t)((double)(free_b + held) * 0.5));
-    // (phase-split pipeline: 8 bytes of hit record per primary work item of a batch + the (wavefront, light) set records, dense by
-    // set id: 32-byte header, 64-dword candidate list, a slot in each of the three class queues)
-    auto set_cap_for = [&](uint64_t q, uint64_t batch) { return (uint32_t)(((std::max<uint64_t>(levels ? q : 0u, batch + 64u * 256u) / 64u + 4u) * std::max<uint32_t>(s->dev.n_lights, 1u) + 15u) & ~7ull); };
-    auto bytes_for = [&](uint64_t q, uint64_t h) {
-      size_t b = levels ? (size_t)(q * (2u * 64u + (merged ? 24u : 12u)) + (h ? (h + 64u) * 64u : 0u)) : 0u;
-      if (split) b += (size_t)(s->batch_items + 64u * 256u) * 8u + (size_t)set_cap_for(q, s->batch_items) * (32u + 256u + 12u + 1u);
-      return (size_t)lanes * b;
-    };
-    while (bytes_for(s->q_cap, s->hard_cap) > budget && s->q_cap > (1u << 16)) {
-      // does not fit: smaller primary batches, queues and pair buffer in proportion
-      s->q_cap = std::max<uint32_t>(s->q_cap / 2u, 1u << 16);
-      s->hard_cap = hard ? std::max<uint32_t>(s->hard_cap / 2u, 1u << 16) : 0u;
-      s->batch_items = std::max<uint32_t>(s->batch_items / 2u, 1u << 10);
-      s->stream_verified = false;
+    if (s->q_cap < (1u << 16)) s->q_cap = 1u << 16;
+    s->hard_cap = f.hard ? std::max<uint32_t>(s->q_cap / 8u, 1u << 16) : 0u;
+  }
+  size_t budget = RT_QUEUE_BUDGET, free_b = 0, total_b = 0;
+  const size_t held = w.bytes() - w.acc.cap;
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, (size_t)((double)(free_b + held) * 0.5));
+  // (phase-split pipeline: 8 bytes of hit record per primary work item of a batch + the (wavefront, light) set records, dense by set id)
+  const uint32_t levels = f.levels;
+  auto set_cap_for = [&](uint64_t q, uint64_t batch) { return (uint32_t)(((std::max<uint64_t>(levels ? q : 0u, batch + 64u * 256u) / 64u + 4u) * std::max<uint32_t>(s->dev.n_lights, 1u) + 15u) & ~7ull); };
+  auto bytes_for = [&](uint64_t q, uint64_t h) {
+    size_t b = levels ? (size_t)(q * (2u * 64u + (f.merged ? 24u : 12u)) + (h ? (h + 64u) * 64u : 0u)) : 0u;
+    if (f.split) b += (size_t)(s->batch_items + 64u * 256u) * 8u + (size_t)set_cap_for(q, s->batch_items) * RT_SET_RECORD_BYTES;
+    return (size_t)f.lanes * b;
+  };
+  while (bytes_for(s->q_cap, s->hard_cap) > budget && s->q_cap > (1u << 16))  // does not fit
+    shrink_sizes(s, f.hard, 1u << 16), s->stream_verified = false;
+  s->batch_items = std::max<uint32_t>((s->batch_items + 255u) / 256u * 256u, 256u);
+  s->q_cap = cap32(((uint64_t)s->q_cap + 255u) / 256u * 256u);
+  // (more rays per level = more rays per bucket: two more key bits for 4K-sized frames: config 5 136.2 -> 133.4 ms)
+  // (merged levels sort the rays of every level at once, three times a level's: config 4 20 / 22 / 23 / 24 bits = 41.3 / 39.9 / 39.3 / 38.9 ms)
+  f.P.sort_bits = s->sort_bits_wanted ? s->sort_bits_wanted : ((f.merged || f.items >= (32ull << 20)) ? RT_SORT_BITS_DEFAULT + 2u : RT_SORT_BITS_DEFAULT);
+  f.n_buckets = 1u << f.P.sort_bits;
+  // (merged levels: the two queues of q_cap rays are ONE queue of 2 q_cap -- same memory -- and the sort workspace covers all of it)
+  f.q_sort_cap = f.merged ? 2u * s->q_cap : s->q_cap;
+  f.set_cap = f.split ? set_cap_for(s->q_cap, s->batch_items) : 0u;
+  f.hitrec_items = (size_t)s->batch_items + 64u * 256u;  // (an interleaved chain's launch is rounded up to whole groups)
+  int rc = RT_OK;
+  for (uint32_t j = 0; j < f.lanes && rc == RT_OK; j++) {
+    rt_scene::Lane& L = w.lane[j];
+    if (levels) {
+      rc = L.queues.ensure((size_t)2 * s->q_cap * RT_QUEUE_QUADS * sizeof(float4));
+      if (rc == RT_OK) rc = L.trace_ws.ensure((size_t)f.q_sort_cap * 12 + (size_t)f.n_buckets * 8 + (f.n_buckets / RT_SORT_TILE) * 4 + 256);
     }
-    s->batch_items = std::max<uint32_t>((s->batch_items + 255u) / 256u * 256u, 256u);
-    s->q_cap = (uint32_t)std::min<uint64_t>(((uint64_t)s->q_cap + 255u) / 256u * 256u, 0xFFFFFF00ull);  // (16-byte aligned arrays behind it)
-    // (more rays per level = more rays per bucket: two more key bits for 4K-sized frames: config 5 136.2 -> 133.4 ms)
-    // (merged levels sort the rays of every level at once, three times a level's: config 4 20 / 22 / 23 / 24 bits = 41.3 / 39.9 / 39.3 / 38.9 ms)
-    P.sort_bits = s->sort_bits_wanted ? s->sort_bits_wanted : ((merged || items >= (32ull << 20)) ? RT_SORT_BITS_DEFAULT + 2u : RT_SORT_BITS_DEFAULT);
-    const uint32_t n_buckets = 1u << P.sort_bits;
-    rc = RT_OK;
-    // (merged levels: the two queues of q_cap rays are ONE queue of 2 q_cap -- same memory -- and the sort workspace covers all of it)
-    const uint32_t q_sort_cap = merged ? 2u * s->q_cap : s->q_cap;
-    const uint32_t set_cap = split ? set_cap_for(s->q_cap, s->batch_items) : 0u;
-    const size_t hitrec_items = (size_t)s->batch_items + 64u * 256u;  // (an interleaved chain's launch is rounded up to whole groups)
-    for (uint32_t j = 0; j < lanes && rc == RT_OK; j++) {
-      if (levels) {
-        rc = w.lane[j].queues.ensure((size_t)2 * s->q_cap * RT_QUEUE_QUADS * sizeof(float4));
-        if (rc == RT_OK) rc = w.lane[j].trace_ws.ensure((size_t)q_sort_cap * 12 + (size_t)n_buckets * 8 + (n_buckets / RT_SORT_TILE) * 4 + 256);
-      }
-      if (rc == RT_OK && hard) rc = w.lane[j].hard.ensure(((size_t)s->hard_cap + 64u) * 4u * sizeof(float4));
-      if (rc == RT_OK && (split || merged)) rc = w.lane[j].hitrec.ensure(hitrec_items * 8u);
-      if (rc == RT_OK && split) rc = w.lane[j].sets.ensure((size_t)set_cap * (32u + 256u + 12u + 1u) + 256u);
-    }
-    if (rc == RT_ERR_OOM && s->q_cap > (1u << 16) && attempt < 12) {
-      s->q_cap /= 2u, s->hard_cap = hard ? std::max<uint32_t>(s->hard_cap / 2u, 1u << 16) : 0u;
-      s->batch_items = std::max<uint32_t>(s->batch_items / 2u, 1u << 10);
-      continue;
-    }
-    if (rc != RT_OK) return rc;
-    if (w.acc_pixels != npix) {
-      if ((rc = w.acc.ensure(npix * 4 * sizeof(long long))) != RT_OK) return rc;
-      HIP_TRY(hipMemsetAsync(w.acc.p, 0, npix * 4 * sizeof(long long), stream));
-      w.acc_pixels = npix;
-    }
-    const uint32_t n_batches = (uint32_t)((items + s->batch_items - 1) / s->batch_items);
-    if (n_batches > lanes) s->notes |= RT_NOTE_FRAME_BATCHED;
-    const uint32_t cap_wgs = (q_sort_cap + 255u) / 256u;
-    const bool guess = s->est_valid && n_batches == lanes;  // grids from the previous frame's counts (else: whole capacity)
-    const uint32_t ppw = 64u / (P.light_mult < 2u ? 2u : P.light_mult), pairs_per_wg = 4u * (ppw ? ppw : 1u);
-    const uint32_t hard_cap_wgs = hard ? (s->hard_cap + pairs_per_wg - 1u) / pairs_per_wg : 1u;
+    if (rc == RT_OK && f.hard) rc = L.hard.ensure(((size_t)s->hard_cap + 64u) * 4u * sizeof(float4));
+    if (rc == RT_OK && (f.split || f.merged)) rc = L.hitrec.ensure(f.hitrec_items * 8u);
+    if (rc == RT_OK && f.split) rc = L.sets.ensure((size_t)f.set_cap * RT_SET_RECORD_BYTES + 256u);
+  }
+  if (rc == RT_ERR_OOM && s->q_cap > (1u << 16) && attempt < 12) {
+    shrink_sizes(s, f.hard, 0u), oom = true;
+    return RT_OK;
+  }
+  if (rc != RT_OK) return rc;
+  const size_t npix = (size_t)f.P.width * f.P.height;
+  if (w.acc_pixels != npix) {
+    RC_TRY(w.acc.ensure(npix * 4 * sizeof(long long)));
+    HIP_TRY(hipMemsetAsync(w.acc.p, 0, npix * 4 * sizeof(long long), f.stream));
+    w.acc_pixels = npix;
+  }
+  f.n_batches = (uint32_t)((f.items + s->batch_items - 1) / s->batch_items);
+  if (f.n_batches > f.lanes) s->notes |= RT_NOTE_FRAME_BATCHED;
+  f.cap_wgs = (f.q_sort_cap + 255u) / 256u;
+  f.guess = s->est_valid && f.n_batches == f.lanes;
+  const uint32_t ppw = 64u / (f.P.light_mult < 2u ? 2u : f.P.light_mult);
+  f.pairs_per_wg = 4u * (ppw ? ppw : 1u), f.hard_cap_wgs = f.hard ? (s->hard_cap + f.pairs_per_wg - 1u) / f.pairs_per_wg : 1u;
+  return RT_OK;
+}
 
-    // ---- every chain's view of the frame: the caller's parameters with the chain's own queues and counters
-    RtDevParams Pl[RT_LANES];
-    float4* q[RT_LANES][2];
-    uint32_t* counts[RT_LANES];
-    for (uint32_t j = 0; j < lanes; j++) {
-      rt_scene::Lane& L = w.lane[j];
-      RtDevParams& Q = Pl[j];
-      Q = P;
-      uint32_t* ws = (uint32_t*)L.trace_ws.p;
-      Q.sort_slot = (uint2*)ws;  // (8-byte aligned: first)
-      Q.sh_idx = ws + (size_t)2 * q_sort_cap;
-      Q.sort_hist = Q.sh_idx + q_sort_cap;
-      Q.sort_offs = Q.sort_hist + n_buckets;
-      Q.sort_tile = Q.sort_offs + n_buckets;
-      if (split) {
-        Q.hitrec = (uint2*)L.hitrec.p;
-        Q.set_hdr = (uint4*)L.sets.p;                                        // [set_cap][2] uint4
-        Q.set_list = (uint32_t*)L.sets.p + (size_t)set_cap * 8u;             // [set_cap][64]
-        Q.set_q = (uint32_t*)L.sets.p + (size_t)set_cap * (8u + 64u);        // [3][set_cap]
-        Q.set_cls = (uint8_t*)((uint32_t*)L.sets.p + (size_t)set_cap * (8u + 64u + 3u));  // [set_cap] bytes
-        Q.set_cap = set_cap;
-        Q.set_lights = s->dev.n_lights;
-      }
-      if (levels && (L.sort_hist_clean != (void*)Q.sort_hist || L.sort_hist_buckets != n_buckets)) {
-        // a fresh (moved, resized) histogram: zero it once; every use leaves it zero
-        HIP_TRY(hipMemsetAsync(Q.sort_hist, 0, (size_t)n_buckets * 4, stream));
-        L.sort_hist_clean = (void*)Q.sort_hist;
-        L.sort_hist_buckets = n_buckets;
-      }
-      counts[j] = (uint32_t*)L.qcount.p;
-      HIP_TRY(hipMemsetAsync(counts[j], 0, (size_t)n_cnt * 4, stream));
-      Q.acc = (long long*)w.acc.p;
-      Q.q_capacity = s->q_cap;
-      Q.q_overflow = counts[j] + RT_CNT_OVERFLOW;
-      Q.hard_q = hard ? (float4*)L.hard.p : nullptr;
-      Q.hard_capacity = s->hard_cap;
-      Q.hard_count = counts[j] + RT_CNT_HARD(levels);
-      Q.hard_stat = counts[j] + RT_CNT_HARD_STAT(levels);
-      q[j][0] = (float4*)L.queues.p, q[j][1] = (float4*)L.queues.p + (size_t)s->q_cap * RT_QUEUE_QUADS;
+// ---- every chain's view of the frame, its histogram zeroed once and its counters zeroed for this attempt
+static int set_up_chains(Frame& f) {
+  rt_scene* s = f.s;
+  rt_scene::StreamWs& w = *f.w;
+  for (uint32_t j = 0; j < f.lanes; j++) {
+    rt_scene::Lane& L = w.lane[j];
+    RtDevParams& Q = f.Pl[j] = f.P;
+    uint32_t* ws = (uint32_t*)L.trace_ws.p;
+    Q.sort_slot = (uint2*)ws;  // (8-byte aligned: first)
+    Q.sh_idx = ws + (size_t)2 * f.q_sort_cap;
+    Q.sort_hist = Q.sh_idx + f.q_sort_cap;
+    Q.sort_offs = Q.sort_hist + f.n_buckets, Q.sort_tile = Q.sort_offs + f.n_buckets;
+    if (f.split) {
+      const uint32_t set_cap = f.set_cap;
+      Q.hitrec = (uint2*)L.hitrec.p;
+      Q.set_hdr = (uint4*)L.sets.p;                                        // [set_cap][2] uint4
+      Q.set_list = (uint32_t*)L.sets.p + (size_t)set_cap * 8u;             // [set_cap][64]
+      Q.set_q = (uint32_t*)L.sets.p + (size_t)set_cap * (8u + 64u);        // [3][set_cap]
+      Q.set_cls = (uint8_t*)((uint32_t*)L.sets.p + (size_t)set_cap * (8u + 64u + 3u));  // [set_cap] bytes
+      Q.set_cap = set_cap, Q.set_lights = s->dev.n_lights;
     }
-    s->queue_bytes = 0;
-    for (auto& o : s->ws) s->queue_bytes += o.bytes();
-    if (lanes > 1) {  // fork: the other chains start behind everything enqueued on the caller's stream so far
-      HIP_TRY(hipEventRecord(w.fork_ev, stream));
-      for (uint32_t j = 1; j < lanes; j++) HIP_TRY(hipStreamWaitEvent(w.lane[j].stream, w.fork_ev, 0));
-      joiner.forked = true, joiner.joined = false;
+    if (f.levels && (L.sort_hist_clean != (void*)Q.sort_hist || L.sort_hist_buckets != f.n_buckets)) {
+      // a fresh (moved, resized) histogram: zero it once; every use leaves it zero
+      HIP_TRY(hipMemsetAsync(Q.sort_hist, 0, (size_t)f.n_buckets * 4, f.stream));
+      L.sort_hist_clean = (void*)Q.sort_hist, L.sort_hist_buckets = f.n_buckets;
     }
-    auto run_hard = [&](uint32_t j, hipStream_t st) -> int {
-      if (!hard) return RT_OK;
-      RtDevParams& Q = Pl[j];
-      const uint32_t g = guess ? grid_for(s->est[j][RT_CNT_HARD_STAT(levels) + 1u], pairs_per_wg, hard_cap_wgs) : std::min(hard_cap_wgs, 16384u);
-      hipError_t e = (hipError_t)rt_launch_hard(s->dev, Q, g, st);
-      if (e != hipSuccess) return fail(RT_ERR_HIP, "hard-pair launch failed: %s", hipGetErrorString(e));
-      trace_point(st, "rt_hard_kernel: workgroups, pair capacity, chain", g, s->hard_cap, j);
-      HIP_TRY(hipMemsetAsync(Q.hard_count, 0, 4, st));  // (stream ordered: behind the kernel that read it)
-      return RT_OK;
-    };
-    const uint32_t batch_wgs = s->batch_items / 256u;
-    // One batch per chain (the rule): the chains INTERLEAVE, groups of 64 workgroups of the list alternately, so that each
-    // gets its share of the expensive regions (contiguous halves = sky and text: the sky's chain is done at once and the
-    // text's runs alone).  Frames batched for memory: contiguous batches, dealt to the chains in turn.
-    const uint32_t group_log2 = 6u, n_groups = (total_wgs + 63u) >> 6;
-    const bool interleave = lanes > 1 && n_batches == lanes;
-    uint32_t lane_batches[RT_LANES] = {0};
-    for (uint32_t b = 0, w0 = 0; interleave ? b < lanes : w0 < total_wgs; b++, w0 += batch_wgs) {
-      const uint32_t j = b % lanes;
-      RtDevParams& Q = Pl[j];
-      hipStream_t st = j ? w.lane[j].stream : stream;
-      if (lane_batches[j]++) HIP_TRY(hipMemsetAsync(counts[j] + 1, 0, (size_t)(levels + 1) * 4, st));  // the chain's next batch: its level counters
-      uint32_t nw = 0;
-      if (interleave) {
-        // groups j, j + lanes, ...; workgroups past the end of the list find no pixel and leave
-        nw = ((n_groups + lanes - 1u - j) / lanes) << group_log2;
-        Q.batch_first_wg = j << group_log2, Q.batch_stride = lanes, Q.batch_group_log2 = group_log2;
-      } else {
-        nw = std::min(total_wgs - w0, batch_wgs);
-        Q.batch_first_wg = w0, Q.batch_stride = 1, Q.batch_group_log2 = 0;
-      }
-      Q.q_in = nullptr, Q.q_in_count = nullptr;
-      Q.q_out = levels ? q[j][0] : nullptr;
-      Q.q_out_count = counts[j] + RT_CNT_LEVEL(1);
-      Q.q_capacity = q_sort_cap;  // (merged levels: the chain's two queues are one, and RT_CNT_LEVEL(1) is its running total)
-      Q.seg_lo = Q.seg_hi = nullptr;
-      hipError_t e;
-      // the (wavefront, light) sets K2 queued for level k, one launch per class (grids: last frame's counts of this shape)
-      auto run_sets = [&](uint32_t k, uint32_t n_sets_host) -> int {
-        // class bytes -> class queues (level 0: the launch's set ids are known here; deeper levels: from the device-side hit count)
-        const uint32_t n_sets_guess = k == 0 ? n_sets_host : (guess ? (s->est[j][RT_CNT_HITS(levels, k)] / 64u + 2u) * s->dev.n_lights : set_cap);
-        Q.set_n = k == 0 ? n_sets_host : 0u;
-        hipError_t ec = (hipError_t)rt_launch_compact(Q, std::min<uint32_t>((n_sets_guess + 2047u) / 2048u + 1u, (set_cap + 2047u) / 2048u), st);
-        if (ec != hipSuccess) return fail(RT_ERR_HIP, "compaction launch failed: %s", hipGetErrorString(ec));
-        for (int c = 0; c < 3; c++) {
-          if (c == 0 && rt_phases_arrive_inline()) continue;  // (ARRIVE sets are finished by K2 itself in this build)
-          const uint32_t cap_sets = (set_cap + 3u) / 4u;
-          const uint32_t g = guess ? grid_for(s->est[j][RT_CNT_SETS(levels, k, c)], 4u, cap_sets) : cap_sets;
-          hipError_t es = (hipError_t)rt_launch_sets(s->dev, Q, k == 0, c, g, st);
-          if (es != hipSuccess) return fail(RT_ERR_HIP, "set-kernel launch failed: %s", hipGetErrorString(es));
-          trace_point(st, "rt_sets kernel: level, class, workgroups", k, (uint32_t)c, g);
-        }
-        return RT_OK;
-      };
-      if (split) {
-        if (lane_batches[j] > 1) HIP_TRY(hipMemsetAsync(counts[j] + RT_CNT_SETS(levels, 0, 0), 0, (size_t)3 * (levels + 1) * 4, st));  // next batch: its set counters
-        Q.set_count = counts[j] + RT_CNT_SETS(levels, 0, 0);
-        Q.set_items = nw * 256u;
-        if ((size_t)nw * 256u > hitrec_items) return fail(RT_ERR_HIP, "internal: primary batch of %u workgroups exceeds the hit-record buffer", nw);
-        e = (hipError_t)rt_launch_hit(s->dev, Q, nw, st);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-        trace_point(st, "rt_hit_kernel: first workgroup, workgroups", w0, nw);
-        e = (hipError_t)rt_launch_classify(s->dev, Q, true, nw, st);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-        trace_point(st, "rt_classify0_kernel: first workgroup, workgroups, set capacity", w0, nw, set_cap);
-        if ((rc = run_sets(0, nw * 4u * s->dev.n_lights)) != RT_OK) return rc;
-      } else if (merged) {
-        // The camera rays' hits and children first (rt_hit_spawn_kernel: 44 VGPRs, no scratch), so that the levels below can be traced
-        // at once -- latency-bound launches -- while the hits are SHADED on a stream of the chain's (rt_primary_pre_kernel: issue bound).
-        rt_scene::Lane& L = w.lane[j];
-        if ((size_t)nw * 256u > hitrec_items) return fail(RT_ERR_HIP, "internal: primary batch of %u workgroups exceeds the hit-record buffer", nw);
-        if (!L.shade_stream[0]) HIP_TRY(hipStreamCreateWithFlags(&L.shade_stream[0], hipStreamNonBlocking));
-        if (!L.shade_done[0]) HIP_TRY(hipEventCreateWithFlags(&L.shade_done[0], hipEventDisableTiming));
-        if (!L.hit_ev) HIP_TRY(hipEventCreateWithFlags(&L.hit_ev, hipEventDisableTiming));
-        Q.hitrec = (uint2*)L.hitrec.p;
-        Q.hit_spawns = 1u;
-        e = (hipError_t)rt_launch_hit(s->dev, Q, nw, st);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-        trace_point(st, "rt_hit_spawn_kernel: first workgroup, workgroups, queue capacity", w0, nw, q_sort_cap);
-        HIP_TRY(hipEventRecord(L.hit_ev, st));
-        HIP_TRY(hipStreamWaitEvent(L.shade_stream[0], L.hit_ev, 0));
-        joiner.shading = true;
-        RtDevParams Pp = Q;
-        Pp.q_out = nullptr, Pp.q_out_count = nullptr, Pp.hit_spawns = 0u;
-        e = (hipError_t)rt_launch_primary(s->dev, Pp, nw, L.shade_stream[0]);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-        trace_point(L.shade_stream[0], "rt_primary_pre_kernel: first workgroup, workgroups", w0, nw);
-        Q.hit_spawns = 0u;
-      } else {
-        e = (hipError_t)rt_launch_primary(s->dev, Q, nw, st);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-        trace_point(st, "rt_primary_stream_kernel: first workgroup, workgroups, queue capacity", w0, nw, s->q_cap);
-      }
-      if (merged) {
-        // ---- every level traced first: rt_trace_spawn_kernel finds the hits of the slice [seg[k], seg[k + 1]) of the chain's ONE queue and
-        // appends their children behind it; the slice's end is a stream-ordered snapshot of the queue's running total
-        // (no rt_hard_kernel in between: the camera rays are being shaded on the chain's shade stream meanwhile and defer pairs of their
-        // own; every deferred pair of the frame waits in the pair queue for the one launch behind the join)
-        rt_scene::Lane& L = w.lane[j];
-        uint32_t* total = counts[j] + RT_CNT_LEVEL(1);
-        if (lane_batches[j] > 1) HIP_TRY(hipMemsetAsync(counts[j] + RT_CNT_SEG(levels, 0), 0, (size_t)(levels + 2u) * 4, st));
-        if (pipelined) {
-          for (int k = 0; k < 2; k++) {
-            if (!L.shade_stream[k]) HIP_TRY(hipStreamCreateWithFlags(&L.shade_stream[k], hipStreamNonBlocking));
-            if (!L.shade_done[k]) HIP_TRY(hipEventCreateWithFlags(&L.shade_done[k], hipEventDisableTiming));
-          }
-          while (L.level_ev.size() < levels) {
-            hipEvent_t ev = nullptr;
-            HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            L.level_ev.push_back(ev);
-          }
-        }
-        Q.q_in = q[j][0];
-        Q.q_out = q[j][0];
-        Q.q_out_count = total;
-        Q.q_in_count = total;
-        for (uint32_t k = 1; k <= levels; k++) {
-          HIP_TRY(hipMemcpyAsync(counts[j] + RT_CNT_SEG(levels, k + 1u), total, 4, hipMemcpyDeviceToDevice, st));
-          Q.seg_lo = counts[j] + RT_CNT_SEG(levels, k);
-          Q.seg_hi = counts[j] + RT_CNT_SEG(levels, k + 1u);
-          Q.q_out = q[j][0], Q.q_out_count = total;
-          const uint32_t n_k = guess ? s->est[j][RT_CNT_SEG(levels, k + 1u)] - s->est[j][RT_CNT_SEG(levels, k)] : 0u;
-          const uint32_t g_rays = guess ? grid_for(n_k, 256u, cap_wgs) : cap_wgs;
-          e = (hipError_t)rt_launch_trace(s->dev, Q, g_rays, st);
-          if (e != hipSuccess) return fail(RT_ERR_HIP, "trace launch failed: %s", hipGetErrorString(e));
-          trace_point(st, "rt_trace_spawn_kernel: level, workgroups, chain", k, g_rays, j);
-          if (pipelined) {
-            // the level's own hit-point order (its slice of sh_idx), then its shading on one of the chain's two shade streams: the
-            // next levels are traced meanwhile, and the head of level k + 1's shading fills the drain of level k's
-            Q.sort_hits = counts[j] + RT_CNT_HITS(levels, k);
-            e = (hipError_t)rt_launch_sort(Q, g_rays, st);
-            if (e != hipSuccess) return fail(RT_ERR_HIP, "sort launch failed: %s", hipGetErrorString(e));
-            HIP_TRY(hipEventRecord(L.level_ev[k - 1u], st));
-            hipStream_t ss = L.shade_stream[k & 1u];
-            HIP_TRY(hipStreamWaitEvent(ss, L.level_ev[k - 1u], 0));
-            joiner.shading = true;
-            RtDevParams S = Q;
-            S.q_out = nullptr, S.q_out_count = nullptr;  // (the children exist already)
-            const uint32_t g_hits = guess ? grid_for(s->est[j][RT_CNT_HITS(levels, k)], 256u, cap_wgs) : cap_wgs;
-            e = (hipError_t)rt_launch_shade(s->dev, S, g_hits, ss);
-            if (e != hipSuccess) return fail(RT_ERR_HIP, "shade launch failed: %s", hipGetErrorString(e));
-            trace_point(ss, "rt_shade_kernel: level, workgroups, chain (pipelined)", k, g_hits, j);
-          }
-        }
-        Q.seg_lo = Q.seg_hi = nullptr;
-        Q.q_out = nullptr, Q.q_out_count = nullptr;
-        if (pipelined) {
-          for (int k = 0; k < 2; k++) {  // join: the pairs the shade launches deferred, and the resolve, need all of them
-            HIP_TRY(hipEventRecord(L.shade_done[k], L.shade_stream[k]));
-            HIP_TRY(hipStreamWaitEvent(st, L.shade_done[k], 0));
-          }
-          joiner.shading = false;  // (joined on the device: the chain's stream now orders everything behind the shade launches)
-        } else {
-          Q.hitrec = nullptr;
-          // ---- MERGED: one hit-point order over the rays of all levels, one shade launch (no children: they exist already)
-          Q.sort_hits = counts[j] + RT_CNT_HITS(levels, 1);
-          const uint32_t g_all = guess ? grid_for(s->est[j][RT_CNT_LEVEL(1)], 256u, cap_wgs) : cap_wgs;
-          const uint32_t g_hits = guess ? grid_for(s->est[j][RT_CNT_HITS(levels, 1)], 256u, cap_wgs) : cap_wgs;
-          e = (hipError_t)rt_launch_sort(Q, g_all, st);
-          if (e != hipSuccess) return fail(RT_ERR_HIP, "sort launch failed: %s", hipGetErrorString(e));
-          e = (hipError_t)rt_launch_shade(s->dev, Q, g_hits, st);
-          if (e != hipSuccess) return fail(RT_ERR_HIP, "shade launch failed: %s", hipGetErrorString(e));
-          trace_point(st, "rt_shade_kernel (all levels): workgroups, chain", g_hits, j);
-          HIP_TRY(hipEventRecord(L.shade_done[0], L.shade_stream[0]));  // join: the camera rays' shading
-          HIP_TRY(hipStreamWaitEvent(st, L.shade_done[0], 0));
-          joiner.shading = false;
-        }
-      }
-      for (uint32_t k = 1; k <= levels && !merged; k++) {
-        if ((rc = run_hard(j, st)) != RT_OK) return rc;  // the pairs the launch before deferred
-        Q.q_in = q[j][(k - 1u) & 1u];
-        Q.q_in_count = counts[j] + RT_CNT_LEVEL(k);
-        Q.sort_hits = counts[j] + RT_CNT_HITS(levels, k);
-        if (k < levels) {
-          Q.q_out = q[j][k & 1u];
-          Q.q_out_count = counts[j] + RT_CNT_LEVEL(k + 1u);
-        } else {
-          Q.q_out = nullptr;  // rays of the last level have depth 1: no children possible
-          Q.q_out_count = nullptr;
-        }
-        const uint32_t g_rays = guess ? grid_for(s->est[j][RT_CNT_LEVEL(k)], 256u, cap_wgs) : cap_wgs;
-        const uint32_t g_hits = guess ? grid_for(s->est[j][RT_CNT_HITS(levels, k)], 256u, cap_wgs) : cap_wgs;
-        e = (hipError_t)rt_launch_trace(s->dev, Q, g_rays, st);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "trace launch failed: %s", hipGetErrorString(e));
-        trace_point(st, "rt_trace_kernel: level, workgroups, chain", k, g_rays, j);
-        e = (hipError_t)rt_launch_sort(Q, g_rays, st);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "sort launch failed: %s", hipGetErrorString(e));
-        trace_point(st, "sort kernels: level, buckets, chain", k, n_buckets, j);
-        if (split) {
-          Q.set_count = counts[j] + RT_CNT_SETS(levels, k, 0);
-          e = (hipError_t)rt_launch_classify(s->dev, Q, false, g_hits, st);
-          if (e != hipSuccess) return fail(RT_ERR_HIP, "classify launch failed: %s", hipGetErrorString(e));
-          trace_point(st, "rt_classify_kernel: level, workgroups, chain", k, g_hits, j);
-          if ((rc = run_sets(k, 0u)) != RT_OK) return rc;
-        } else {
-          e = (hipError_t)rt_launch_shade(s->dev, Q, g_hits, st);
-          if (e != hipSuccess) return fail(RT_ERR_HIP, "shade launch failed: %s", hipGetErrorString(e));
-          trace_point(st, "rt_shade_kernel: level, workgroups, chain", k, g_hits, j);
-        }
-      }
-      if ((rc = run_hard(j, st)) != RT_OK) return rc;  // pairs deferred by the last level's shading
-    }
-    if (lanes > 1) {  // join: the resolve needs every chain's sums
-      for (uint32_t j = 1; j < lanes; j++) {
-        HIP_TRY(hipEventRecord(w.lane[j].done_ev, w.lane[j].stream));
-        HIP_TRY(hipStreamWaitEvent(stream, w.lane[j].done_ev, 0));
-      }
-      joiner.joined = true;
-    }
-    hipError_t e = (hipError_t)rt_launch_resolve(Pl[0], stream);
-    if (e != hipSuccess) return fail(RT_ERR_HIP, "resolve launch failed: %s", hipGetErrorString(e));
-    trace_point(stream, "rt_resolve_kernel: attempt", (uint32_t)attempt);
+    uint32_t* cnt = f.counts[j] = (uint32_t*)L.qcount.p;
+    HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)f.n_cnt * 4, f.stream));
+    Q.acc = (long long*)w.acc.p, Q.q_capacity = s->q_cap, Q.q_overflow = cnt + RT_CNT_OVERFLOW;
+    Q.hard_q = f.hard ? (float4*)L.hard.p : nullptr, Q.hard_capacity = s->hard_cap;
+    Q.hard_count = cnt + RT_CNT_HARD(f.levels), Q.hard_stat = cnt + RT_CNT_HARD_STAT(f.levels);
+    f.q[j][0] = (float4*)L.queues.p, f.q[j][1] = (float4*)L.queues.p + (size_t)s->q_cap * RT_QUEUE_QUADS;
+  }
+  s->queue_bytes = 0;
+  for (auto& o : s->ws) s->queue_bytes += o.bytes();
+  return RT_OK;
+}
 
-    // ---- the frame's counters come back asynchronously (grids of the next frame); an unverified shape waits for them
-    if (w.cnt_pending && (!s->stream_verified || blocking)) {  // (an older read-back still owns the pinned buffer)
-      HIP_TRY(hipEventSynchronize(w.cnt_ev));
-      w.cnt_pending = false;
+// the pairs chain j deferred so far, traced by rt_hard_kernel
+static int run_hard(Frame& f, uint32_t j, hipStream_t st) {
+  if (!f.hard) return RT_OK;
+  RtDevParams& Q = f.Pl[j];
+  const uint32_t g = f.guess ? grid_for(f.s->est[j][RT_CNT_HARD_STAT(f.levels) + 1u], f.pairs_per_wg, f.hard_cap_wgs) : std::min(f.hard_cap_wgs, 16384u);
+  RC_TRY(launched(rt_launch_hard(f.s->dev, Q, g, st), st, "hard-pair launch", "rt_hard_kernel: workgroups, pair capacity, chain", g, f.s->hard_cap, j));
+  HIP_TRY(hipMemsetAsync(Q.hard_count, 0, 4, st));  // (stream ordered: behind the kernel that read it)
+  return RT_OK;
+}
+
+// the (wavefront, light) sets K2 queued for level k of chain j, one launch per class (grids: last frame's counts of this shape)
+static int run_sets(Frame& f, uint32_t j, hipStream_t st, uint32_t k, uint32_t n_sets_host) {
+  rt_scene* s = f.s;
+  RtDevParams& Q = f.Pl[j];
+  // class bytes -> class queues (level 0: the launch's set ids are known here; deeper levels: from the device-side hit count)
+  const uint32_t n_sets_guess = k == 0 ? n_sets_host : (f.guess ? (s->est[j][RT_CNT_HITS(f.levels, k)] / 64u + 2u) * s->dev.n_lights : f.set_cap);
+  Q.set_n = k == 0 ? n_sets_host : 0u;
+  RC_TRY(launched(rt_launch_compact(Q, std::min<uint32_t>((n_sets_guess + 2047u) / 2048u + 1u, (f.set_cap + 2047u) / 2048u), st), st, "compaction launch"));
+  const uint32_t cap_sets = (f.set_cap + 3u) / 4u;
+  for (int c = 0; c < 3; c++) {
+    if (c == 0 && rt_phases_arrive_inline()) continue;  // (ARRIVE sets are finished by K2 itself in this build)
+    const uint32_t g = f.guess ? grid_for(s->est[j][RT_CNT_SETS(f.levels, k, c)], 4u, cap_sets) : cap_sets;
+    RC_TRY(launched(rt_launch_sets(s->dev, Q, k == 0, c, g, st), st, "set-kernel launch", "rt_sets kernel: level, class, workgroups", k, (uint32_t)c, g));
+  }
+  return RT_OK;
+}
+
+// ---- the primary launches of one batch of chain j (workgroups w0 .. w0 + nw of the list; `next`: not the chain's first batch)
+static int enqueue_primary(Frame& f, uint32_t j, hipStream_t st, uint32_t w0, uint32_t nw, bool next) {
+  rt_scene* s = f.s;
+  RtDevParams& Q = f.Pl[j];
+  if ((f.split || f.merged) && (size_t)nw * 256u > f.hitrec_items)
+    return fail(RT_ERR_HIP, "internal: primary batch of %u workgroups exceeds the hit-record buffer", nw);
+  if (f.split) {
+    if (next) HIP_TRY(hipMemsetAsync(f.counts[j] + RT_CNT_SETS(f.levels, 0, 0), 0, (size_t)3 * (f.levels + 1) * 4, st));  // its set counters
+    Q.set_count = f.counts[j] + RT_CNT_SETS(f.levels, 0, 0), Q.set_items = nw * 256u;
+    RC_TRY(launched(rt_launch_hit(s->dev, Q, nw, st), st, "kernel launch", "rt_hit_kernel: first workgroup, workgroups", w0, nw));
+    RC_TRY(launched(rt_launch_classify(s->dev, Q, true, nw, st), st, "kernel launch", "rt_classify0_kernel: first workgroup, workgroups, set capacity", w0, nw, f.set_cap));
+    return run_sets(f, j, st, 0, nw * 4u * s->dev.n_lights);
+  }
+  if (!f.merged)
+    return launched(rt_launch_primary(s->dev, Q, nw, st), st, "kernel launch", "rt_primary_stream_kernel: first workgroup, workgroups, queue capacity", w0, nw, s->q_cap);
+  // The camera rays' hits and children first (rt_hit_spawn_kernel: 44 VGPRs, no scratch), so that the levels below can be traced
+  // at once -- latency-bound launches -- while the hits are SHADED on a stream of the chain's (rt_primary_pre_kernel: issue bound).
+  rt_scene::Lane& L = f.w->lane[j];
+  for (int k = 0; k < (f.pipelined ? 2 : 1); k++) {  // (pipelined levels are shaded on two streams alternately)
+    if (!L.shade_stream[k]) HIP_TRY(hipStreamCreateWithFlags(&L.shade_stream[k], hipStreamNonBlocking));
+    if (!L.shade_done[k]) HIP_TRY(hipEventCreateWithFlags(&L.shade_done[k], hipEventDisableTiming));
+  }
+  if (!L.hit_ev) HIP_TRY(hipEventCreateWithFlags(&L.hit_ev, hipEventDisableTiming));
+  Q.hitrec = (uint2*)L.hitrec.p, Q.hit_spawns = 1u;
+  RC_TRY(launched(rt_launch_hit(s->dev, Q, nw, st), st, "kernel launch", "rt_hit_spawn_kernel: first workgroup, workgroups, queue capacity", w0, nw, f.q_sort_cap));
+  HIP_TRY(hipEventRecord(L.hit_ev, st));
+  HIP_TRY(hipStreamWaitEvent(L.shade_stream[0], L.hit_ev, 0));
+  f.shading = true;
+  RtDevParams Pp = Q;
+  Pp.q_out = nullptr, Pp.q_out_count = nullptr, Pp.hit_spawns = 0u;
+  RC_TRY(launched(rt_launch_primary(s->dev, Pp, nw, L.shade_stream[0]), L.shade_stream[0], "kernel launch", "rt_primary_pre_kernel: first workgroup, workgroups", w0, nw));
+  Q.hit_spawns = 0u;
+  return RT_OK;
+}
+
+// ---- merged / pipelined levels of chain j: every level traced first -- rt_trace_spawn_kernel finds the hits of the slice
+// [seg[k], seg[k + 1]) of the chain's ONE queue and appends their children behind it; the slice's end is a stream-ordered snapshot
+// of the queue's running total.  (No rt_hard_kernel in between: the camera rays are being shaded on the chain's shade stream
+// meanwhile and defer pairs of their own; every deferred pair of the frame waits in the pair queue for the one launch behind the join.)
+static int enqueue_merged_levels(Frame& f, uint32_t j, hipStream_t st, bool next) {
+  rt_scene* s = f.s;
+  rt_scene::Lane& L = f.w->lane[j];
+  RtDevParams& Q = f.Pl[j];
+  const uint32_t levels = f.levels;
+  uint32_t *const cnt = f.counts[j], *const total = cnt + RT_CNT_LEVEL(1);
+  if (next) HIP_TRY(hipMemsetAsync(cnt + RT_CNT_SEG(levels, 0), 0, (size_t)(levels + 2u) * 4, st));
+  while (f.pipelined && L.level_ev.size() < levels) {
+    hipEvent_t ev = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    L.level_ev.push_back(ev);
+  }
+  Q.q_in = f.q[j][0], Q.q_in_count = total;
+  for (uint32_t k = 1; k <= levels; k++) {
+    HIP_TRY(hipMemcpyAsync(cnt + RT_CNT_SEG(levels, k + 1u), total, 4, hipMemcpyDeviceToDevice, st));
+    Q.seg_lo = cnt + RT_CNT_SEG(levels, k), Q.seg_hi = cnt + RT_CNT_SEG(levels, k + 1u);
+    Q.q_out = f.q[j][0], Q.q_out_count = total;
+    const uint32_t n_k = f.guess ? s->est[j][RT_CNT_SEG(levels, k + 1u)] - s->est[j][RT_CNT_SEG(levels, k)] : 0u;
+    const uint32_t g_rays = f.guess ? grid_for(n_k, 256u, f.cap_wgs) : f.cap_wgs;
+    RC_TRY(launched(rt_launch_trace(s->dev, Q, g_rays, st), st, "trace launch", "rt_trace_spawn_kernel: level, workgroups, chain", k, g_rays, j));
+    if (!f.pipelined) continue;
+    // the level's own hit-point order (its slice of sh_idx), then its shading on one of the chain's two shade streams: the
+    // next levels are traced meanwhile, and the head of level k + 1's shading fills the drain of level k's
+    Q.sort_hits = cnt + RT_CNT_HITS(levels, k);
+    RC_TRY(launched(rt_launch_sort(Q, g_rays, st), st, "sort launch"));
+    HIP_TRY(hipEventRecord(L.level_ev[k - 1u], st));
+    hipStream_t ss = L.shade_stream[k & 1u];
+    HIP_TRY(hipStreamWaitEvent(ss, L.level_ev[k - 1u], 0));
+    f.shading = true;
+    RtDevParams S = Q;
+    S.q_out = nullptr, S.q_out_count = nullptr;  // (the children exist already)
+    const uint32_t g_hits = f.ray_grid(j, RT_CNT_HITS(levels, k));
+    RC_TRY(launched(rt_launch_shade(s->dev, S, g_hits, ss), ss, "shade launch", "rt_shade_kernel: level, workgroups, chain (pipelined)", k, g_hits, j));
+  }
+  Q.seg_lo = Q.seg_hi = nullptr, Q.q_out = nullptr, Q.q_out_count = nullptr;
+  if (!f.pipelined) {
+    // ---- MERGED: one hit-point order over the rays of all levels, one shade launch (no children: they exist already)
+    Q.hitrec = nullptr;
+    Q.sort_hits = cnt + RT_CNT_HITS(levels, 1);
+    const uint32_t g_all = f.ray_grid(j, RT_CNT_LEVEL(1)), g_hits = f.ray_grid(j, RT_CNT_HITS(levels, 1));
+    RC_TRY(launched(rt_launch_sort(Q, g_all, st), st, "sort launch"));
+    RC_TRY(launched(rt_launch_shade(s->dev, Q, g_hits, st), st, "shade launch", "rt_shade_kernel (all levels): workgroups, chain", g_hits, j));
+  }
+  // join: the camera rays' shading (pipelined: and every level's) -- the pairs it deferred, and the resolve, need all of it
+  for (int k = 0; k < (f.pipelined ? 2 : 1); k++) {
+    HIP_TRY(hipEventRecord(L.shade_done[k], L.shade_stream[k]));
+    HIP_TRY(hipStreamWaitEvent(st, L.shade_done[k], 0));
+  }
+  f.shading = false;  // (joined on the device: the chain's stream now orders everything behind the shade launches)
+  return RT_OK;
+}
+
+// ---- chained levels of chain j: trace -> sort -> shade (or classify -> sets) per level, the pairs deferred before each level first
+static int enqueue_chained_levels(Frame& f, uint32_t j, hipStream_t st) {
+  rt_scene* s = f.s;
+  RtDevParams& Q = f.Pl[j];
+  const uint32_t levels = f.levels;
+  uint32_t* const cnt = f.counts[j];
+  for (uint32_t k = 1; k <= levels; k++) {
+    RC_TRY(run_hard(f, j, st));  // the pairs the launch before deferred
+    Q.q_in = f.q[j][(k - 1u) & 1u], Q.q_in_count = cnt + RT_CNT_LEVEL(k), Q.sort_hits = cnt + RT_CNT_HITS(levels, k);
+    Q.q_out = k < levels ? f.q[j][k & 1u] : nullptr;  // (rays of the last level have depth 1: no children possible)
+    Q.q_out_count = k < levels ? cnt + RT_CNT_LEVEL(k + 1u) : nullptr;
+    const uint32_t g_rays = f.ray_grid(j, RT_CNT_LEVEL(k)), g_hits = f.ray_grid(j, RT_CNT_HITS(levels, k));
+    RC_TRY(launched(rt_launch_trace(s->dev, Q, g_rays, st), st, "trace launch", "rt_trace_kernel: level, workgroups, chain", k, g_rays, j));
+    RC_TRY(launched(rt_launch_sort(Q, g_rays, st), st, "sort launch", "sort kernels: level, buckets, chain", k, f.n_buckets, j));
+    if (f.split) {
+      Q.set_count = cnt + RT_CNT_SETS(levels, k, 0);
+      RC_TRY(launched(rt_launch_classify(s->dev, Q, false, g_hits, st), st, "classify launch", "rt_classify_kernel: level, workgroups, chain", k, g_hits, j));
+      RC_TRY(run_sets(f, j, st, k, 0u));
+    } else {
+      RC_TRY(launched(rt_launch_shade(s->dev, Q, g_hits, st), st, "shade launch", "rt_shade_kernel: level, workgroups, chain", k, g_hits, j));
     }
-    if (!w.cnt_pending) {
-      for (uint32_t j = 0; j < lanes; j++)
-        HIP_TRY(hipMemcpyAsync(w.cnt_host + (size_t)j * RT_CNT_STRIDE, counts[j], (size_t)n_cnt * 4, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipEventRecord(w.cnt_ev, stream));
-      w.cnt_pending = true;
-      w.cnt_host_levels = levels;
-      w.cnt_host_lanes = lanes;
-      w.cnt_host_valid = n_batches == lanes;
-      w.cnt_key_gen = s->key_gen;
-    }
-    if (s->stream_verified && !blocking) return RT_OK;
+  }
+  return RT_OK;
+}
+
+// ---- the batches of every chain.  One batch per chain (the rule): the chains INTERLEAVE, groups of 64 workgroups of the list
+// alternately, so that each gets its share of the expensive regions (contiguous halves = sky and text: the sky's chain is done at
+// once and the text's runs alone).  Frames batched for memory: contiguous batches, dealt to the chains in turn.
+static int enqueue_chains(Frame& f) {
+  rt_scene* s = f.s;
+  rt_scene::StreamWs& w = *f.w;
+  if (f.lanes > 1) {  // fork: the other chains start behind everything enqueued on the caller's stream so far
+    HIP_TRY(hipEventRecord(w.fork_ev, f.stream));
+    for (uint32_t j = 1; j < f.lanes; j++) HIP_TRY(hipStreamWaitEvent(w.lane[j].stream, w.fork_ev, 0));
+    f.forked = true, f.joined = false;
+  }
+  const uint32_t batch_wgs = s->batch_items / 256u, group_log2 = 6u, n_groups = (f.total_wgs + 63u) >> 6;
+  const bool interleave = f.lanes > 1 && f.n_batches == f.lanes;
+  uint32_t lane_batches[RT_LANES] = {0};
+  for (uint32_t b = 0, w0 = 0; interleave ? b < f.lanes : w0 < f.total_wgs; b++, w0 += batch_wgs) {
+    const uint32_t j = b % f.lanes;
+    RtDevParams& Q = f.Pl[j];
+    hipStream_t st = j ? w.lane[j].stream : f.stream;
+    const bool next = lane_batches[j]++ > 0;
+    if (next) HIP_TRY(hipMemsetAsync(f.counts[j] + 1, 0, (size_t)(f.levels + 1) * 4, st));  // the chain's next batch: its level counters
+    // (interleaved: groups j, j + lanes, ...; workgroups past the end of the list find no pixel and leave)
+    const uint32_t nw = interleave ? ((n_groups + f.lanes - 1u - j) / f.lanes) << group_log2 : std::min(f.total_wgs - w0, batch_wgs);
+    if (interleave) Q.batch_first_wg = j << group_log2, Q.batch_stride = f.lanes, Q.batch_group_log2 = group_log2;
+    else Q.batch_first_wg = w0, Q.batch_stride = 1, Q.batch_group_log2 = 0;
+    Q.q_in = nullptr, Q.q_in_count = nullptr, Q.seg_lo = Q.seg_hi = nullptr;
+    Q.q_out = f.levels ? f.q[j][0] : nullptr, Q.q_out_count = f.counts[j] + RT_CNT_LEVEL(1);
+    Q.q_capacity = f.q_sort_cap;  // (merged levels: the chain's two queues are one, and RT_CNT_LEVEL(1) is its running total)
+    RC_TRY(enqueue_primary(f, j, st, w0, nw, next));
+    RC_TRY(f.merged ? enqueue_merged_levels(f, j, st, next) : enqueue_chained_levels(f, j, st));
+    RC_TRY(run_hard(f, j, st));  // pairs deferred by the last level's shading (merged levels: every pair of the batch)
+  }
+  return RT_OK;
+}
+
+// ---- join, resolve, and the frame's counters: they come back asynchronously (grids of the next frame); an unverified shape (or a
+// blocking call) waits for them.  `again`: children or pairs were dropped, the queues grew -- render the frame again.
+static int finish_frame(Frame& f, int attempt, bool& again) {
+  rt_scene* s = f.s;
+  rt_scene::StreamWs& w = *f.w;
+  const uint32_t levels = f.levels, lanes = f.lanes;
+  for (uint32_t j = 1; j < lanes; j++) {  // join: the resolve needs every chain's sums
+    HIP_TRY(hipEventRecord(w.lane[j].done_ev, w.lane[j].stream));
+    HIP_TRY(hipStreamWaitEvent(f.stream, w.lane[j].done_ev, 0));
+  }
+  f.joined = true;
+  RC_TRY(launched(rt_launch_resolve(f.Pl[0], f.stream), f.stream, "resolve launch", "rt_resolve_kernel: attempt", (uint32_t)attempt));
+  if (w.cnt_pending && (!s->stream_verified || f.blocking)) {  // (an older read-back still owns the pinned buffer)
     HIP_TRY(hipEventSynchronize(w.cnt_ev));
     w.cnt_pending = false;
-    uint32_t dropped = 0, dropped_pairs = 0, need = 0, need_pairs = 0;
-    for (uint32_t j = 0; j < lanes; j++) {
-      const uint32_t* c = w.cnt_host + (size_t)j * RT_CNT_STRIDE;
-      dropped += c[RT_CNT_OVERFLOW], dropped_pairs += c[RT_CNT_HARD_STAT(levels)];
-      // (merged levels: RT_CNT_LEVEL(1) is the running total of ONE queue of 2 q_cap rays)
-      for (uint32_t k = 1; k <= levels + 1u; k++) need = std::max(need, merged ? (c[RT_CNT_LEVEL(k)] + 1u) / 2u : c[RT_CNT_LEVEL(k)]);
-      need_pairs = std::max(need_pairs, c[RT_CNT_HARD_STAT(levels) + 1u]);
-    }
-    if (!dropped && !dropped_pairs) {
-      if (w.cnt_host_valid) memcpy(s->est, w.cnt_host, sizeof(s->est)), s->est_valid = true;
-      s->stream_verified = true;
-      // headroom for the frames that now run unverified: a quarter more pairs than this frame deferred (takes effect with the next
-      // frame's allocation; nothing was dropped, so this frame stands)
-      if (hard && n_batches == lanes && (uint64_t)need_pairs * 5u / 4u > s->hard_cap)
-        s->hard_cap = (uint32_t)std::min<uint64_t>((uint64_t)need_pairs * 5u / 4u + 256u, 0xFFFFFF00ull);
-      return RT_OK;
-    }
-    // children or pairs were dropped: the counters say what the frame needed; render it again with that
-    if (attempt >= (merged ? 12 : 6)) return fail(RT_ERR_HIP, "%u child rays / %u pair batches were dropped (queues could not be sized)", dropped, dropped_pairs);
-    if (n_batches == lanes && !forced_chunk_log2) {
-      // (one queue for all levels: the rays that were dropped would have had children of their own, so the count is a lower bound)
-      if (merged && dropped) need = std::max<uint32_t>(need + need / 4u, s->q_cap + s->q_cap / 2u);
-      if (need > s->q_cap) s->q_cap = (uint32_t)std::min<uint64_t>((uint64_t)need + need / 16u + 256u, 0xFFFFFF00ull);
-      if (need_pairs > s->hard_cap) s->hard_cap = (uint32_t)std::min<uint64_t>((uint64_t)need_pairs + need_pairs / 8u + 256u, 0xFFFFFF00ull);
-    } else {
-      // (batched or forced: the counters are those of the last batch only -- grow geometrically)
-      if (dropped) s->q_cap = (uint32_t)std::min<uint64_t>((uint64_t)s->q_cap * 2u, 0xFFFFFF00ull);
-      if (dropped_pairs) s->hard_cap = (uint32_t)std::min<uint64_t>((uint64_t)s->hard_cap * 4u, 0xFFFFFF00ull);
-    }
-    s->est_valid = false;
-    w.acc_pixels = 0;  // partial sums: clear the accumulator
-    // ... and the ray counters of the abandoned attempt (rt_stats counts what the reference casts, once)
-    if (P.counters) HIP_TRY(hipMemsetAsync(P.counters, 0, RT_COUNTER_REPLICAS * 16 * sizeof(unsigned long long), stream));
   }
+  if (!w.cnt_pending) {
+    for (uint32_t j = 0; j < lanes; j++)
+      HIP_TRY(hipMemcpyAsync(w.cnt_host + (size_t)j * RT_CNT_STRIDE, f.counts[j], (size_t)f.n_cnt * 4, hipMemcpyDeviceToHost, f.stream));
+    HIP_TRY(hipEventRecord(w.cnt_ev, f.stream));
+    w.cnt_pending = true, w.cnt_host_levels = levels, w.cnt_host_lanes = lanes, w.cnt_host_valid = f.n_batches == lanes, w.cnt_key_gen = s->key_gen;
+  }
+  if (s->stream_verified && !f.blocking) return RT_OK;
+  HIP_TRY(hipEventSynchronize(w.cnt_ev));
+  w.cnt_pending = false;
+  uint32_t dropped = 0, dropped_pairs = 0, need = 0, need_pairs = 0;
+  for (uint32_t j = 0; j < lanes; j++) {
+    const uint32_t* c = w.cnt_host + (size_t)j * RT_CNT_STRIDE;
+    dropped += c[RT_CNT_OVERFLOW], dropped_pairs += c[RT_CNT_HARD_STAT(levels)];
+    // (merged levels: RT_CNT_LEVEL(1) is the running total of ONE queue of 2 q_cap rays)
+    for (uint32_t k = 1; k <= levels + 1u; k++) need = std::max(need, f.merged ? (c[RT_CNT_LEVEL(k)] + 1u) / 2u : c[RT_CNT_LEVEL(k)]);
+    need_pairs = std::max(need_pairs, c[RT_CNT_HARD_STAT(levels) + 1u]);
+  }
+  if (!dropped && !dropped_pairs) {
+    if (w.cnt_host_valid) memcpy(s->est, w.cnt_host, sizeof(s->est)), s->est_valid = true;
+    s->stream_verified = true;
+    // headroom for the frames that now run unverified: a quarter more pairs than this frame deferred (takes effect with the next
+    // frame's allocation; nothing was dropped, so this frame stands)
+    if (f.hard && f.n_batches == lanes && (uint64_t)need_pairs * 5u / 4u > s->hard_cap) s->hard_cap = cap32((uint64_t)need_pairs * 5u / 4u + 256u);
+    return RT_OK;
+  }
+  // children or pairs were dropped: the counters say what the frame needed; render it again with that
+  if (attempt >= (f.merged ? 12 : 6)) return fail(RT_ERR_HIP, "%u child rays / %u pair batches were dropped (queues could not be sized)", dropped, dropped_pairs);
+  if (f.n_batches == lanes && !f.forced) {
+    // (one queue for all levels: the rays that were dropped would have had children of their own, so the count is a lower bound)
+    if (f.merged && dropped) need = std::max<uint32_t>(need + need / 4u, s->q_cap + s->q_cap / 2u);
+    if (need > s->q_cap) s->q_cap = cap32((uint64_t)need + need / 16u + 256u);
+    if (need_pairs > s->hard_cap) s->hard_cap = cap32((uint64_t)need_pairs + need_pairs / 8u + 256u);
+  } else {
+    // (batched or forced: the counters are those of the last batch only -- grow geometrically)
+    if (dropped) s->q_cap = cap32((uint64_t)s->q_cap * 2u);
+    if (dropped_pairs) s->hard_cap = cap32((uint64_t)s->hard_cap * 4u);
+  }
+  s->est_valid = false, w.acc_pixels = 0;  // partial sums: clear the accumulator
+  // ... and the ray counters of the abandoned attempt (rt_stats counts what the reference casts, once)
+  if (f.P.counters) HIP_TRY(hipMemsetAsync(f.P.counters, 0, RT_COUNTER_REPLICAS * 16 * sizeof(unsigned long long), f.stream));
+  again = true;
+  return RT_OK;
+}
+
+static int render_frame_impl(rt_scene* s, RtDevParams& P, hipStream_t stream, uint32_t forced_chunk_log2, bool blocking) {
+  s->queue_bytes = 0;
+  Frame f(s, P, stream, forced_chunk_log2, blocking);
+  P.resolve_counts_written = f.split ? 1u : 0u;
+  if (!f.secondary && !f.split && !f.defer) {  // one launch of the fused primary kernel
+    P.acc = nullptr, P.q_out = nullptr;
+    P.batch_first_wg = 0, P.batch_stride = 1, P.batch_group_log2 = 0;
+    return launched(rt_launch_primary(s->dev, P, f.total_wgs, stream), stream, "kernel launch", "rt_primary_kernel: workgroups", f.total_wgs);
+  }
+  if (f.total_wgs == 0) return RT_OK;  // this rank owns no tile inside the window (more ranks than tiles): nothing to trace, nothing to resolve
+  RC_TRY(plan_schedule(f));
+  RC_TRY(take_workspace(f));
+  match_stream_key(f);
+  for (int attempt = 0;; attempt++) {
+    bool oom = false, again = false;
+    RC_TRY(size_queues(f, attempt, oom));
+    if (oom) continue;
+    RC_TRY(set_up_chains(f));
+    RC_TRY(enqueue_chains(f));
+    RC_TRY(finish_frame(f, attempt, again));
+    if (!again) return RT_OK;
+  }
+}
+
+// A frame that fails half-way (HIP / launch error, out of memory) leaves partial sums in the pixel accumulator: mark
+// the accumulator dirty so that the next frame clears it.
+static int render_frame(rt_scene* s, RtDevParams& P, hipStream_t stream, uint32_t forced_chunk_log2, bool blocking = false) {
+  const int rc = render_frame_impl(s, P, stream, forced_chunk_log2, blocking);
+  if (rc != RT_OK) s->ws[s->cur_ws].acc_pixels = 0;
+  // marks the end of this frame's use of its counter block (prepare() of a later frame waits for it)
+  if (hipEventRecord(s->frame_ev[s->cur_block], stream) == hipSuccess) s->frame_pending[s->cur_block] = true;
+  s->last_block = s->cur_block;
+  return rc;
 }
 
 // prepare() + the calibration frame of RT_TILE_ORDER_COST when this frame shape has no cost map yet: the frame is rendered

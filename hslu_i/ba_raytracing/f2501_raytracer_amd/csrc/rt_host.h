@@ -25,8 +25,21 @@ int rt_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3))
 #define RT_SLOTS 4
 // chains a frame with secondary rays is split into (rt_tuning.sub_frames)
 #define RT_LANES 2
-// dwords of a chain's device-side counter block (levels <= 64: 2 * 64 + 8 level counters + 3 * 65 set-class counters)
-#define RT_CNT_STRIDE 384
+// deepest reflection / refraction recursion rt_params may ask for (levels of a frame's ray tree)
+#define RT_MAX_DEPTH 64u
+
+// A chain's device-side counter block, in dwords, for a ray tree of `levels` levels: overflow, levels, hard, hits, sets, seg.
+#define RT_CNT_OVERFLOW 0u                       // dropped children
+#define RT_CNT_LEVEL(k) (k)                      // 1 .. levels + 1: rays appended to level k (dropped ones included)
+#define RT_CNT_HARD(levels) ((levels) + 2u)      // hard pairs waiting
+#define RT_CNT_HARD_STAT(levels) ((levels) + 3u) // [0] dropped pairs, [1] largest batch of pairs
+#define RT_CNT_HITS(levels, k) ((levels) + 5u + (k))  // rays of level k that hit something
+#define RT_CNT_SETS(levels, k, c) (2u * (levels) + 8u + 3u * (k) + (c))  // phase-split pipeline: sets of class c at level k = 0 .. levels
+#define RT_CNT_SEG(levels, k) (2u * (levels) + 8u + 3u * ((levels) + 1u) + (k))  // merged levels: first queue index of level k = 1 .. levels + 1
+#define RT_CNT_TOTAL(levels) (2u * (levels) + 8u + 3u * ((levels) + 1u) + (levels) + 2u)
+// one chain's row of the host copies (rt_scene::est, StreamWs::cnt_host): the block of the deepest tree, rounded up to 64 bytes
+#define RT_CNT_STRIDE ((RT_CNT_TOTAL(RT_MAX_DEPTH) + 15u) & ~15u)
+static_assert(RT_CNT_TOTAL(RT_MAX_DEPTH) <= RT_CNT_STRIDE, "counter rows shorter than the counter block");
 
 struct DevBuf {
   void* p = nullptr;

@@ -344,14 +344,22 @@ int rt_render(rt_scene* scene, const rt_params* params, uint32_t* argb, const rt
 
 /* Same, but `argb_dev` (and aux pointers) are DEVICE pointers on the scene's device and all work
  * is enqueued on `hip_stream` (a hipStream_t, NULL = default stream).  Without reflections /
- * refractions this is one asynchronous kernel launch; with them the call drives the ray-streaming
- * passes and returns when the last pass has been enqueued (it synchronises the stream in between to
- * read queue sizes).  Ray counters: after the caller has synchronised, rt_render_collect_stats (those of the frame
+ * refractions this is one asynchronous kernel launch; with them the call enqueues the launches of
+ * every ray-streaming level and returns: a frame of a verified shape is a burst of launches that
+ * does not wait for the GPU.  The call blocks until earlier work has finished only
+ *  - on the first frame of a shape (its counters are read back to verify the queue sizes), and while
+ *    it renders that frame again after its queues grew;
+ *  - on the frame after one that dropped work (the shape is verified again);
+ *  - when a parameter table (AA offsets, light clouds, receiver flags, tile list) is uploaded while
+ *    frames that read the old one are in flight;
+ *  - when a scene switches from two chains to one (rt_tuning.sub_frames) and frees the second's queues;
+ *  - on the calibration frame of RT_TILE_ORDER_COST (once per frame shape).
+ * Ray counters: after the caller has synchronised, rt_render_collect_stats (those of the frame
  * enqueued last).
- * Consecutive frames of one scene may be enqueued on DIFFERENT streams: the library orders what they share (two
- * counter blocks used alternately; frames with secondary rays own the ray queues and wait for every earlier frame), so
- * two frames without secondary rays overlap -- the head of one fills the compute units the drain of the other leaves
- * idle. */
+ * Consecutive frames of one scene may be enqueued on DIFFERENT streams: the library orders what they share (four
+ * frame slots, each a counter block and, with secondary rays, a workspace set; a frame waits on the device for the
+ * frame that used its slot last), so two frames overlap -- the head of one fills the compute units the drain of the
+ * other leaves idle. */
 int rt_render_device(rt_scene* scene, const rt_params* params, uint32_t* argb_dev,
                      const rt_aux* aux_dev, void* hip_stream);
 int rt_render_collect_stats(rt_scene* scene, rt_stats* stats);
@@ -459,8 +467,8 @@ typedef struct rt_comm rt_comm;
 int rt_comm_unique_id(uint8_t id[RT_COMM_ID_BYTES]);
 int rt_comm_create(const uint8_t* id, uint32_t n_ranks, uint32_t rank, int device, rt_comm** out); /* n_ranks 1: id may be NULL */
 void rt_comm_destroy(rt_comm* comm);
-/* Renders this rank's tiles and takes part in the gather; everything is enqueued on hip_stream (with reflections /
- * refractions the render part synchronises the stream between ray-queue levels, as rt_render_device does).  On rank 0
+/* Renders this rank's tiles and takes part in the gather; everything is enqueued on hip_stream (the render part
+ * blocks only where rt_render_device does, e.g. on the first frame of a shape).  On rank 0
  * argb_dev (DEVICE, W*H, pre-filled by the caller) holds the complete frame once the stream has drained; on the
  * other ranks it is not touched and may be NULL.  params->n_ranks / rank are ignored (the communicator's are used). */
 /* The render runs on hip_stream, the gather on a stream the communicator owns (in call order, behind this rank's render);

@@ -9,6 +9,7 @@ import pytest
 import bench
 import oracle_lib
 from hslu_i.ba_raytracing.f2501_raytracer_amd import RenderConfig, _abi, scenes
+from hslu_i.ba_raytracing.f2501_raytracer_amd.renderer import ImageBuffer, RaytracerRenderer
 from test_parity_gpu import RGB_TOL, gpu_render, random_scene, window_mask
 
 pytestmark = pytest.mark.gpu
@@ -152,6 +153,31 @@ def test_merged_levels_against_the_oracle_and_the_chained_schedule(MODE):
     a, p, s = gpu_render(cfg, flat, win, traversal=_abi.RT_TRAVERSAL_LINEAR, **MODE)
     b, q, t = gpu_render(cfg, flat, win, traversal=_abi.RT_TRAVERSAL_LINEAR, **CHAINED)
     assert np.array_equal(a, b) and all(s[k] == t[k] for k in COUNTS)
+    # depth 64, the deepest tree rt_params allows: the largest counter block per chain.  256 x 256 pixels are 2^16 primary work
+    # items, the fewest that run two chains.  Reflections only: a ray has at most one child, so no level outgrows the first
+    # queue sizes (with refractions this window's tree outgrows the chained schedule's six attempts to size them).  Two frames
+    # per renderer: the second takes its grids from the first one's counters.
+    cfg = RenderConfig.from_features(["reflections"], depth_override=64)
+    flat = scenes.test_scene(cfg).flatten()
+    win = (256, 192, 256, 256)
+    ref, pr, sr = render_twice(cfg, flat, win, **CHAINED)[0]
+    for M in (MODE, CHAINED):
+        for kw in (dict(sub_frames=1), dict(sub_frames=2)):
+            for a, p, s in render_twice(cfg, flat, win, **M, **kw):
+                assert np.array_equal(a, ref) and np.array_equal(p["rgb"].view(np.uint32), pr["rgb"].view(np.uint32)), (M, kw)
+                assert np.array_equal(p["hit_t"].view(np.uint32), pr["hit_t"].view(np.uint32)), (M, kw)
+                assert all(s[k] == sr[k] for k in COUNTS), (M, kw)
+
+
+def render_twice(cfg, flat, win, **tuning):
+    """Two frames of one shape through one renderer (gpu_render makes a new one per frame)."""
+    r = RaytracerRenderer(cfg, device=0)
+    out = []
+    for _ in range(2):
+        buf = ImageBuffer.new(cfg.width, cfg.height)
+        planes = r.render(buf, flat, window=win, aux=True, tuning=tuning)
+        out.append((buf.buffer.copy(), planes, r.last_stats))
+    return out
 
 
 @pytest.mark.parametrize("key,MODE", [("c4", MERGED), ("c4d21", MERGED), ("c5", MERGED), ("c4", PIPELINED)],
