@@ -52,6 +52,23 @@
 // same for a wave-uniform value: gives it an SGPR of its own (kernel arguments arrive in 8/16-dword tuples, and
 // hipcc spills and reloads a tuple as a whole -- 8 v_readlane to get at one of its fields inside a loop)
 #define RT_OPAQUE_S(v) asm volatile("" : "+s"(v))
+// The kernel arguments of every kernel that runs process_ray (RtDevScene sc, RtDevParams P: kernarg offsets 0 and 88), read
+// again from the kernarg segment where a loop uses them.  The segment pointer passes through an empty asm statement at
+// each call, so the field loads after it cannot be hoisted to the kernel's entry: a field costs one s_load at its point of
+// use (scalar cache) instead of an SGPR held through the light loop -- which hipcc spills into lanes of two VGPRs and
+// reloads with v_readlane (169 SGPRs spilled, 446 reloads, before this was done).
+typedef const __attribute__((address_space(4))) char* rt_kernarg_ptr;
+__device__ __forceinline__ rt_kernarg_ptr kernarg_fresh() {
+  rt_kernarg_ptr p = (rt_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+#define RT_KERNARG_OFF_P ((sizeof(RtDevScene) + alignof(RtDevParams) - 1) / alignof(RtDevParams) * alignof(RtDevParams))
+static_assert(RT_KERNARG_OFF_P == 88, "RtDevParams follows RtDevScene at kernarg offset 88");
+__device__ __forceinline__ const RtDevScene& kernarg_scene() { return *(const RtDevScene*)(const char*)kernarg_fresh(); }
+__device__ __forceinline__ const RtDevParams& kernarg_params() {
+  return *(const RtDevParams*)((const char*)kernarg_fresh() + RT_KERNARG_OFF_P);
+}
 // Lane mask of a predicate.  HIP's __ballot(int) first widens the bool to an int in a VGPR and compares it back
 // (v_cndmask + v_cmp per vote); the builtin takes the i1 as it is (the compare result already is the mask).
 #define wave_ballot(pred) __builtin_amdgcn_ballot_w64((bool)(pred))
@@ -1481,9 +1498,10 @@ __device__ __forceinline__ void hard_push(const RtDevParams& P, lanemask m, V3 p
 // ------------------------------------------------------------------------------------------------
 // LDS stash: [field][256 threads], one dword per lane per field.  Fields 0-11: ray state parked across the light loop;
 // STREAM kernels: 12-17 = the lane's pixel contribution as three 64-bit fixed-point sums (RT_ACC_SCALE units).
-#define RT_STASH_FIELDS 18u
+#define RT_STASH_FIELDS 21u
 #define RT_STASH_CELL 11u  /* receiver cell of the hit point (RT_NO_CELL: none) */
-#define RT_STASH_FIX 12u
+#define RT_STASH_D 12u     /* 12-14: the view direction d, read where the light loop and the children use it */
+#define RT_STASH_FIX 15u
 #define RT_NO_CELL 0xFFFFFFFFu
 #define RT_MAT_TRANS_BIT 0x80000000u  /* stash field 6: material row | this bit when the material is transmissive */
 __device__ __forceinline__ long long* stash_fix(float* stash) { return (long long*)(stash + RT_STASH_FIX * 256u); }
@@ -1491,6 +1509,9 @@ __device__ __forceinline__ long long* stash_fix(float* stash) { return (long lon
 // STREAM: secondary rays exist (reflections / refractions): children are queued, pixel sums go through the fixed-point
 // accumulator, hard soft-shadow pairs are deferred.  The frames without them (configs 1-3) run a kernel that does not
 // contain any of that code.
+// sc / P MUST be the calling kernel's own, unmodified kernel arguments (its parameters 0 and 1): the light loop, the sample
+// loop and the part after the light loop read them again from the kernarg segment (kernarg_scene / kernarg_params: the
+// shadowing `sc` / `P` inside the loops, `sc1` / `P1` after them), so a changed copy passed in would not be seen there.
 template <bool CULL, bool PRE, bool STREAM>
 __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevParams& P, Wave& wv, bool have,
                                               const RayIn& r, float* stash /* LDS: [RT_STASH_FIELDS][256] */,
@@ -1557,6 +1578,9 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     st[7 * 256] = h.t;
     st[8 * 256] = __int_as_float(out.id);
     st[9 * 256] = __uint_as_float(r.pix);
+    st[(RT_STASH_D + 0) * 256] = d.x;
+    st[(RT_STASH_D + 1) * 256] = d.y;
+    st[(RT_STASH_D + 2) * 256] = d.z;
   }
   Surf sf;
   sf.p = mk(0, 0, 0);
@@ -1597,12 +1621,9 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
   const Mat m_lit = load_mat(sc, sf.mat);
   // the material row is simply read again after the loop (L2)
   stash[threadIdx.x + 6 * 256] = __uint_as_float(sf.mat | (m_lit.transmissive ? RT_MAT_TRANS_BIT : 0u));
-  const V3 mcolor = m_lit.color;
-  const float mshin = m_lit.shininess;
 
   // ---- calculate_lighting, raytracer_renderer.rs:731-874 ----------------------------------------
   V3 light_color = mk(0, 0, 0), spec_color = mk(0, 0, 0);
-  const bool has_spec = mshin > 0.0f;
   // first hit point of the wavefront and how far the others are from it (sphere pre-selection of the candidate collection)
   V3 p_first = mk(0, 0, 0);
   float p_spread = 0.0f;
@@ -1621,6 +1642,9 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
   // part of them the classifications below resolve without a traversal
   wv.cnt_shadow += sc.n_lights * N * (P.weighted ? wave_sum(hit ? r.mult : 0u) : (uint32_t)__popcll(hit_m));
   for (uint32_t l = 0; l < sc.n_lights; l++) {
+    // (the kernel arguments again, per light: see kernarg_fresh)
+    const RtDevScene& sc = kernarg_scene();
+    const RtDevParams& P = kernarg_params();
     const float4 L0 = sload<float4>(sc, sc.off_lights + l * 32u);
     const float4 L1 = sload<float4>(sc, sc.off_lights + l * 32u + 16u);
     const V3 lc = mk(L1.x, L1.y, L1.z);
@@ -1765,7 +1789,8 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       int hd, hk;
       uint32_t hmult;
       unpack_dkm(__float_as_int(st[5 * 256]), hd, hk, hmult);
-      hard_push(P, use_m, sf.p, sf.n, d, __float_as_uint(st[6 * 256]) & ~RT_MAT_TRANS_BIT, l, __float_as_uint(st[9 * 256]),
+      const V3 dv = mk(st[(RT_STASH_D + 0) * 256], st[(RT_STASH_D + 1) * 256], st[(RT_STASH_D + 2) * 256]);
+      hard_push(P, use_m, sf.p, sf.n, dv, __float_as_uint(st[6 * 256]) & ~RT_MAT_TRANS_BIT, l, __float_as_uint(st[9 * 256]),
                 mk(st[0 * 256] * a0, st[1 * 256] * a0, st[2 * 256] * a0), hmult);
       continue;
     }
@@ -1811,6 +1836,18 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     // Everything here only scales the colour (tolerance 1e-4, measured < 4e-6).  Two exact identities of the
     // reference are used to drop work: `cosi = (ltp . n) / (|ltp| + EPS)` is `diff = n . ld` up to a factor
     // 1 + EPS/|ltp| (ld = ltp / |ltp|), and its `cosi > 0` selects are implied by the `diff > 0` gate of the sum.
+    // the surface colour and shininess, read again per light from the material row (L2) instead of held through the loop
+    V3 mcolor;
+    float mshin;
+    {
+      uint32_t tix = threadIdx.x;
+      RT_OPAQUE(tix);
+      const uint32_t mrow = (__float_as_uint(stash[6u * 256u + tix]) & ~RT_MAT_TRANS_BIT) * 48u;
+      const float4 ma = vload<float4>(sc, sc.off_materials + mrow);
+      mcolor = mk(ma.x, ma.y, ma.z);
+      mshin = vload<float>(sc, sc.off_materials + mrow + 16u);
+    }
+    const bool has_spec = mshin > 0.0f;
     const V3 mc_lc = mcolor * lc;  // per light
     const V3 mmc_lc = mcolor * mc_lc;  // (the reference multiplies the surface colour in twice: contribution colour x surface colour)
     // this light's share of `direct` and `specular`, summed over its samples in sample order from zero (the same chain
@@ -1823,7 +1860,10 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     auto add_light = [&](auto filtered_tag, V3 ltp, const Shadow& S, lanemask reach_m) {
       constexpr bool FILTERED = decltype(filtered_tag)::value;
       const unsigned long long t_l = PROF_T();
-      const LightTerms T = light_sample_terms<FILTERED>(sf.n, d, mmc_lc, lI, mshin, has_spec, ltp, S);
+      uint32_t tix = threadIdx.x;
+      RT_OPAQUE(tix);
+      const V3 dv = mk(stash[(RT_STASH_D + 0) * 256u + tix], stash[(RT_STASH_D + 1) * 256u + tix], stash[(RT_STASH_D + 2) * 256u + tix]);
+      const LightTerms T = light_sample_terms<FILTERED>(sf.n, dv, mmc_lc, lI, mshin, has_spec, ltp, S);
       if (lane_of(reach_m) && T.lit) {
         // (fused accumulation: colour-only, one rounding less than the reference's multiply + add)
         dl = fma_s(T.mLc, T.lf, dl);
@@ -1867,6 +1907,8 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     } else {
       auto traced_samples = [&](auto list_tag) {
         for (uint32_t j = 0; j < N; j++) {
+          const RtDevScene& sc = kernarg_scene();  // (per sample)
+          const RtDevParams& P = kernarg_params();
 #if RT_PROFILE
           W.t_mark = PROF_T();
 #endif
@@ -1920,6 +1962,9 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
   }
   PROF_ADD(W, 6, t_all);
   // ---- back from LDS -------------------------------------------------------------------------------
+  // (and the kernel arguments from the kernarg segment: nothing is held through the light loop for this part)
+  const RtDevScene& sc1 = kernarg_scene();
+  const RtDevParams& P1 = kernarg_params();
   V3 Wt;
   float a, n_start;
   int depth, kind;
@@ -1937,14 +1982,15 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     unpack_dkm(__float_as_int(st[5 * 256]), depth, kind, out.mult);
     uint32_t mat_row = __float_as_uint(st[6 * 256]) & ~RT_MAT_TRANS_BIT;
     RT_OPAQUE(mat_row);  // keeps hipcc from carrying the row's addresses through the loop (in scratch)
-    m = load_mat(sc, mat_row);
+    m = load_mat(sc1, mat_row);
     out.t = st[7 * 256];
     out.id = __float_as_int(st[8 * 256]);
     pixel = __float_as_uint(st[9 * 256]);
+    d = mk(st[(RT_STASH_D + 0) * 256], st[(RT_STASH_D + 1) * 256], st[(RT_STASH_D + 2) * 256]);
     out.pix = pixel;
   }
   (void)kind;
-  V3 ambient = (m.color * mk(1.0f, 1.0f, 1.0f)) * P.ambient;
+  V3 ambient = (m.color * mk(1.0f, 1.0f, 1.0f)) * P1.ambient;
   // own terms of this node (:251-257): transmissive ? spec : direct + spec
   const bool T = m.transmissive;
   if (STREAM) {
@@ -1972,17 +2018,17 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     V3 co = mk(0, 0, 0), cd = mk(0, 0, 1), cW = mk(0, 0, 0);
     int cdepth = 0;
     const bool R = (m.metallic > 0.0f) || T;
-    if (hit && (P.flags & RT_FLAG_REFLECTIONS) && R) {
+    if (hit && (P1.flags & RT_FLAG_REFLECTIONS) && R) {
       float cos_theta = dot(d, sf.n);
       bool inside = cos_theta < 0.0f;
       V3 inormal = inside ? -sf.n : sf.n;
-      float n2 = inside ? m.ior : P.air_ior;
+      float n2 = inside ? m.ior : P1.air_ior;
       float eta = inside ? (n2 / n_start) : (n_start / n2);
       float cos_i = fabsf(cos_theta);
       float sin2 = eta * eta * (1.0f - cos_i * cos_i);
       bool tir = sin2 >= 1.0f;
       bool reflective = (m.metallic > 0.0f) || (T && tir);
-      cdepth = depth < 0 ? (int)P.max_depth_reflection : (depth > 0 ? depth - 1 : 0);
+      cdepth = depth < 0 ? (int)P1.max_depth_reflection : (depth > 0 ? depth - 1 : 0);
       if (reflective && cdepth > 0) {
         V3 rr = normalize(reflected(d, sf.n));
         V3 Rf = fresnel_reflectance(m, inormal, -d, n_start);
@@ -1992,7 +2038,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
         cW = Wt * Rf;
       }
     }
-    queue_push(P, spawn, co, cd, n_start, cW, cdepth, KIND_REFL, pixel, out.mult);
+    queue_push(P1, spawn, co, cd, n_start, cW, cdepth, KIND_REFL, pixel, out.mult);
   }
   // ---- calculate_refractions, :279-524 --------------------------------------------------------------
   {
@@ -2000,11 +2046,11 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     V3 co = mk(0, 0, 0), cd = mk(0, 0, 1), cW = mk(0, 0, 0);
     int cdepth = 0;
     float cior = 0.0f;
-    if (hit && (P.flags & RT_FLAG_REFRACTIONS) && T) {
+    if (hit && (P1.flags & RT_FLAG_REFRACTIONS) && T) {
       float cos_theta = dot(d, sf.n);
       bool inside = cos_theta <= 0.0f;
       V3 inormal = inside ? -sf.n : sf.n;
-      float n2 = inside ? m.ior : P.air_ior;
+      float n2 = inside ? m.ior : P1.air_ior;
       float eta = inside ? (n2 / n_start) : (n_start / n2);
       float inv_eta = 1.0f / eta;
       V3 Rf = fresnel_reflectance(m, inormal, d, inv_eta);
@@ -2016,7 +2062,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       float op = m.opacity;
       int step = (op < 0.5f) ? 2 : 1;
       int fac = (op <= 0.3f) ? 3 : ((op < 0.5f) ? 2 : 1);
-      cdepth = depth < 0 ? (int)P.max_depth_refraction / fac : (depth > step ? depth - step : 0);
+      cdepth = depth < 0 ? (int)P1.max_depth_refraction / fac : (depth > step ? depth - step : 0);
       if (!(kk < 0.0f) && cdepth > 0) {  // kk < 0: zero vector -> NaN direction -> miss (deviation D2)
         float s = inv_eta * ndi + __builtin_sqrtf(kk);
         V3 q = normalize(d * inv_eta - nn * s);
@@ -2027,7 +2073,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
         cior = n2;
       }
     }
-    queue_push(P, spawn, co, cd, cior, cW, cdepth, KIND_REFR, pixel, out.mult);
+    queue_push(P1, spawn, co, cd, cior, cW, cdepth, KIND_REFR, pixel, out.mult);
   }
   return out;
 }
@@ -2074,6 +2120,7 @@ __device__ __forceinline__ void acc_add_fixed(const RtDevParams& P, uint32_t pix
 // PRE (merged levels): the camera rays' hits were found -- and their children appended -- by rt_hit_spawn_kernel; this launch only shades
 // them, concurrently with the trace launches of the levels below on another stream.
 template <bool CULL, bool STREAM, bool COST = false, bool PRE = false>
+// sc / P: the kernel's own kernel arguments, unmodified (process_ray; after process_ray this reads P1 = kernarg_params())
 __device__ __forceinline__ void primary_body(const RtDevScene& sc, const RtDevParams& P, float4* lds_rgbh,
                                              float* lds_stash, unsigned long long* lds_cnt) {
   Wave wv;
@@ -2094,7 +2141,7 @@ __device__ __forceinline__ void primary_body(const RtDevScene& sc, const RtDevPa
   // for the slowest of its workgroup (rt_primary_wave_local is the host's copy of this rule).
   const bool wave_local = rt_primary_wave_local(n_thr);
   const uint32_t ppwave = wave_local ? 64u / n_thr : 0u;
-  auto map_thread = [&](uint32_t tid) {
+  auto map_thread = [&](const RtDevParams& P, uint32_t tid) {
     PixelMap m;
     const uint32_t ppw = wave_local ? 4u * ppwave : 256u / n_thr;  // pixels per workgroup (host guarantees n_thr <= 256)
     bool slot_used;
@@ -2124,7 +2171,7 @@ __device__ __forceinline__ void primary_body(const RtDevScene& sc, const RtDevPa
     m.pix = m.gy * P.width + m.gx;
     return m;
   };
-  const PixelMap pm = map_thread(threadIdx.x);
+  const PixelMap pm = map_thread(P, threadIdx.x);
   const bool pix_on = pm.on;
   // cost calibration (RT_TILE_ORDER_COST): the wavefront's start time waits in LDS, not in SGPRs
   if (COST && P.cost_map && (threadIdx.x & 63u) == 0) lds_cnt[16 + (threadIdx.x >> 6)] = __builtin_readcyclecounter();
@@ -2156,17 +2203,19 @@ __device__ __forceinline__ void primary_body(const RtDevScene& sc, const RtDevPa
     none.id = (int)hr.y;
   }
   RayOut out = process_ray<CULL, PRE, STREAM>(sc, P, wv, pix_on, r, lds_stash, none);
+  // the kernel arguments again, from the kernarg segment: nothing of them is held through process_ray
+  const RtDevParams& P1 = kernarg_params();
 
   // ---- per-pixel accumulation of the samples ----------------------------------------------------------
   V3 cs = out.contrib;  // = own * scale (c * scale, :974,:992)
   lds_rgbh[threadIdx.x] = make_float4(cs.x, cs.y, cs.z, out.hit ? 1.0f : 0.0f);
   uint32_t tid2 = threadIdx.x;
   RT_OPAQUE(tid2);  // keeps hipcc from carrying the first mapping through process_ray
-  const PixelMap pm2 = map_thread(tid2);
+  const PixelMap pm2 = map_thread(P1, tid2);
   const uint32_t pix = pm2.pix;
   if (pm2.k == 0 && pm2.on) {
-    if (P.aux_hit_id) P.aux_hit_id[pix] = out.id;
-    if (P.aux_hit_t && out.id >= 0) P.aux_hit_t[pix] = out.t;
+    if (P1.aux_hit_id) P1.aux_hit_id[pix] = out.id;
+    if (P1.aux_hit_t && out.id >= 0) P1.aux_hit_t[pix] = out.t;
   }
   // the samples of a pixel are the threads tid2 .. tid2 + n_thr - 1 (tid2 = the pixel's thread with k == 0)
   if (wave_local) {
@@ -2188,20 +2237,20 @@ __device__ __forceinline__ void primary_body(const RtDevScene& sc, const RtDevPa
     for (uint32_t u = 0; u < n_thr; u++) {
       if (s[u].w != 0.0f) {
         any = true;
-        const long long mu = P.weighted ? (long long)uload(&P.aa_mult[u]) : 1ll;
+        const long long mu = P1.weighted ? (long long)uload(&P1.aa_mult[u]) : 1ll;
         sx += fx[u] * mu, sy += fx[256u + u] * mu, sz += fx[512u + u] * mu;
       }
     }
     if (any) {
       wrote = true;
-      acc_add_fixed(P, pix, sx, sy, sz, 1u);
-      P.acc[4 * (size_t)pix + 3] = 1;
+      acc_add_fixed(P1, pix, sx, sy, sz, 1u);
+      P1.acc[4 * (size_t)pix + 3] = 1;
     }
   }
   if (!STREAM && pm2.k == 0 && pm2.on) {
     const float4* s = lds_rgbh + tid2;
     // sample q of the reference's sum -> the thread that traced it (wave-uniform q: scalar load)
-    auto src = [&](uint32_t q) { return P.weighted ? uload(&P.aa_src[q]) : q; };
+    auto src = [&](uint32_t q) { return P1.weighted ? uload(&P1.aa_src[q]) : q; };
     V3 color;
     bool any = false;
     if (!aa) {
@@ -2241,21 +2290,21 @@ __device__ __forceinline__ void primary_body(const RtDevScene& sc, const RtDevPa
     }
     if (any) {
       wrote = true;
-      P.argb[out_index(P, pm2.gx, pm2.gy, pix)] = pack_argb(color);
-      if (P.aux_rgb) {
-        P.aux_rgb[3 * (size_t)pix + 0] = color.x;
-        P.aux_rgb[3 * (size_t)pix + 1] = color.y;
-        P.aux_rgb[3 * (size_t)pix + 2] = color.z;
+      P1.argb[out_index(P1, pm2.gx, pm2.gy, pix)] = pack_argb(color);
+      if (P1.aux_rgb) {
+        P1.aux_rgb[3 * (size_t)pix + 0] = color.x;
+        P1.aux_rgb[3 * (size_t)pix + 1] = color.y;
+        P1.aux_rgb[3 * (size_t)pix + 2] = color.z;
       }
     }
   }
-  if (COST && P.cost_map && (threadIdx.x & 63u) == 0) {
+  if (COST && P1.cost_map && (threadIdx.x & 63u) == 0) {
     const unsigned long long dt = __builtin_readcyclecounter() - lds_cnt[16 + (threadIdx.x >> 6)];
     const uint32_t ppw = wave_local ? 4u * ppwave : 256u / n_thr;
-    const uint32_t g = rt_batch_wg(P, blockIdx.x) * ppw + (wave_local ? (threadIdx.x >> 6) * ppwave : threadIdx.x / n_thr), sup_slot = g >> 8;
-    if (sup_slot < P.n_sup) atomicAdd(&P.cost_map[P.sup_list ? P.sup_list[sup_slot] : sup_slot], (uint32_t)(dt >> 6));
+    const uint32_t g = rt_batch_wg(P1, blockIdx.x) * ppw + (wave_local ? (threadIdx.x >> 6) * ppwave : threadIdx.x / n_thr), sup_slot = g >> 8;
+    if (sup_slot < P1.n_sup) atomicAdd(&P1.cost_map[P1.sup_list ? P1.sup_list[sup_slot] : sup_slot], (uint32_t)(dt >> 6));
   }
-  wave_flush(wv, P, (uint32_t)__popcll(wave_ballot(wrote)), lds_cnt);
+  wave_flush(wv, P1, (uint32_t)__popcll(wave_ballot(wrote)), lds_cnt);
 }
 
 // Occupancy.  The kernel is LATENCY bound: a wavefront issues one instruction every ~12 cycles (dependent scalar-load ->
@@ -2616,6 +2665,7 @@ __global__ __launch_bounds__(256, 4) void rt_trace_spawn_kernel(RtDevScene sc, R
 }
 
 template <bool CULL>
+// sc / P: the kernel's own kernel arguments, unmodified (process_ray)
 __device__ __forceinline__ void shade_body(const RtDevScene& sc, const RtDevParams& P, float* lds_stash,
                                            unsigned long long* lds_cnt) {
   Wave wv;
