@@ -1,0 +1,583 @@
+"""float64 model of the render pipeline, independent of oracle/rt_oracle.c.
+
+Written from the reference's formulas: `antialiased_raytrace` (samples at coords + offset, one
+direction for all, weight 1/(8*ceil(n/8)), hit id and t of sample 0), `single_raytrace`, `calculate_lighting` +
+`PointLight::calculate_contribution_at`, `has_any_intersection` (the opacity / filter chain walked in object order),
+`calculate_reflection`, `calculate_refractions` (depth step and factor from the ray's own opacity, DESIGN D3),
+`compute_fresnel`, distance attenuation, and `to_point_light_cloud` with the seeded set choice of DESIGN D4
+(set = rt_cloud_hash(cloud_seed, pixel, light) % n_cloud_sets, points at L + p * (fw, fh, fd), intensity L[6] / N).
+Textbook ray/sphere and Moeller-Trumbore ray/triangle tests instead of the oracle's matrix-inverse form, numpy float64,
+vectorised over objects.  Only the sample tables themselves (`sampling.aa_offsets`, `sampling.cloud_sets`) are taken as
+data.  The oracle is something this model checks, never something it calls.
+
+Decision intervals.  Every discrete decision records its float64 margin (named thresholds below).  A decision whose
+margin is under its threshold is "near": fp32 arithmetic may take it the other way.
+  * a near decision on a primary or secondary hit (which object is hit, total internal reflection, inside / outside)
+    makes the pixel ambiguous (`Ambiguous`): it is excluded and counted, never passed;
+  * a shadow ray with k <= MAX_FLIPS objects whose hit is near is evaluated 2^k ways; a near cos_i > 0 / diff > 0 adds
+    "no contribution" as a further outcome.  Each shadow sample thus gives a [lo, hi] per channel; more than
+    MAX_FLIPS near objects on one shadow ray makes the pixel ambiguous.
+Lights, AA samples and child rays add with non-negative weights, so the per-sample intervals add up to a per-pixel,
+per-channel interval, and a renderer passes if every channel lies in [lo - TOL, hi + TOL].
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from hslu_i.ba_raytracing.f2501_raytracer_amd import sampling
+from hslu_i.ba_raytracing.f2501_raytracer_amd.scene import FlatScene
+
+EPS = float(np.finfo(np.float32).eps)
+
+# ---- decision margins (calibrated once on CPU against the oracle; never widened to make a case pass) ----------------
+# Each is a multiple of the fp32 error the quantity carries in a renderer (fp32 epsilon ~ 1.2e-7, scene units ~ 1).
+M_BARY = 1e-6   # barycentric u, v, 1 - u - v, relative: |u| * |det| against M_BARY * |tv| * |pv| (and alike)
+M_DET = 1e-6    # | |det| - EPS | against M_DET * |e1| * |e2|
+M_PLANE = 1e-6  # distance of a ray origin from the surface a root near 0 (or near EPS) puts it on, scene units
+M_TMAX = 1e-6   # t against the shadow ray's tmax, scene units
+M_DISC = 1e-6   # sphere discriminant, relative to b^2 + |o - c|^2 + r^2
+M_TIE = 1e-6    # two nearest-hit candidates of different objects closer than this in t
+M_COS = 1e-6    # cos_i > 0, diff > 0, inside / outside (n . v against 0), unit vectors
+M_TIR = 1e-6    # total internal reflection: sin^2 against 1, refract's k against 0
+M_OP = 1e-9     # |opacity| <= EPS in the shadow chain
+MAX_FLIPS = 2   # near objects on one shadow ray evaluated both ways; above this the pixel is dropped
+TOL = 1e-4      # one tolerance on every interval bound (BASELINE north_star bar)
+PAD = 1e-4      # AABB padding of the shadow-ray prefilter (much larger than M_TMAX: the prefilter stays conservative)
+
+
+class Ambiguous(Exception):
+    """A primary or secondary decision is within its margin: the pixel is excluded and counted."""
+
+
+def norm(v):
+    return v / np.sqrt(v @ v)
+
+
+def cloud_hash(seed, pixel, light):
+    """rt_cloud_hash (include/rt_hip.h), uint32 arithmetic."""
+    M = 0xFFFFFFFF
+    h = (seed * 0x9E3779B1) & M
+    h ^= ((pixel + 0x7F4A7C15) * 0x85EBCA6B) & M
+    h ^= ((light + 0x165667B1) * 0xC2B2AE35) & M
+    h ^= h >> 16
+    h = (h * 0x7FEB352D) & M
+    h ^= h >> 15
+    h = (h * 0x846CA68B) & M
+    h ^= h >> 16
+    return h
+
+
+class Iv:
+    """per-channel value: nominal (every decision as float64 takes it), lo, hi"""
+
+    __slots__ = ("nom", "lo", "hi")
+
+    def __init__(self, nom, lo=None, hi=None):
+        self.nom = np.asarray(nom, np.float64)
+        self.lo = self.nom.copy() if lo is None else np.asarray(lo, np.float64)
+        self.hi = self.nom.copy() if hi is None else np.asarray(hi, np.float64)
+
+    @staticmethod
+    def zero():
+        return Iv(np.zeros(3))
+
+    def __add__(self, o):
+        return Iv(self.nom + o.nom, self.lo + o.lo, self.hi + o.hi)
+
+    def scale(self, w):
+        w = np.asarray(w, np.float64)
+        assert np.all(w >= 0), w  # intervals scale only by non-negative weights
+        return Iv(self.nom * w, self.lo * w, self.hi * w)
+
+
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def _dot(a, b):
+    return np.einsum("...k,...k->...", a, b)
+
+
+def _decide(conds):
+    """conds: [(holds, near)] of one test; returns (valid, near): the test passes; some condition is near and none is
+    clearly false (so the outcome could flip)."""
+    valid = np.ones_like(conds[0][0])
+    could = np.ones_like(conds[0][0])
+    anyn = np.zeros_like(conds[0][0])
+    for c, n in conds:
+        valid &= c
+        could &= c | n
+        anyn |= n
+    return valid, could & anyn
+
+
+class Model:
+    """float64 restatement of the reference pipeline: spheres + triangles + point lights, light clouds, AA, reflections,
+    refractions.  `reflections` / `refractions` default to the config's features."""
+
+    def __init__(self, flat, cfg, reflections=None, refractions=None, aa_offsets=None, cloud=None):
+        assert not cfg.has("backface_culling"), "the model has no back-face culling"
+        self.f, self.cfg = flat, cfg
+        self.refl = cfg.has("reflections") if reflections is None else bool(reflections)
+        self.refr = cfg.has("refractions") if refractions is None else bool(refractions)
+        self.eps_d = float(cfg.eps_distance)
+        self.air = float(cfg.air_ior)
+        self.ambient = float(cfg.ambient)
+        self.fwhd = np.array([float(cfg.fw), float(cfg.fh), float(cfg.fd)])
+        self.focus = np.array([float(cfg.focus.x), float(cfg.focus.y), float(cfg.focus.z)])
+        self.aa = None
+        if cfg.has("anti_aliasing"):
+            self.aa = np.asarray(sampling.aa_offsets(cfg) if aa_offsets is None else aa_offsets, np.float64)
+        self.N = max(int(cfg.point_light_multiplicator), 1)
+        self.cloud = None
+        if self.N > 1:
+            self.cloud = np.asarray(sampling.cloud_sets(cfg) if cloud is None else cloud, np.float64)
+            assert self.cloud.shape[1:] == (self.N, 3)
+        f = flat
+        self.ns, self.nt = f.n_spheres, f.n_triangles
+        self.sc = f.sphere_center.astype(np.float64).reshape(-1, 3)
+        self.sr2 = f.sphere_r_sq.astype(np.float64)
+        self.v1, self.e1, self.e2 = (a.astype(np.float64).reshape(-1, 3) for a in (f.tri_v1, f.tri_e1, f.tri_e2))
+        self.tn = f.tri_normal.astype(np.float64).reshape(-1, 3)
+        self.e12 = np.sqrt(_dot(self.e1, self.e1) * _dot(self.e2, self.e2))
+        self.n_e1xe2 = np.sqrt(_dot(_cross(self.e1, self.e2), _cross(self.e1, self.e2)))
+        self.mats = f.materials.astype(np.float64)
+        self.obj_mat = np.concatenate([f.sphere_material.astype(np.int64), f.tri_material.astype(np.int64)])
+        m = self.mats
+        self.mat_tr = (m[:, 8] != 0) & ~(np.abs(m[:, 6]) <= EPS)
+        self.obj_tr = self.mat_tr[self.obj_mat]
+        # object AABBs (shadow-ray prefilter)
+        r = np.sqrt(self.sr2)[:, None]
+        tv = np.stack([self.v1, self.v1 + self.e1, self.v1 + self.e2], axis=1)
+        self.bmin = np.concatenate([self.sc - r, tv.min(axis=1) if self.nt else np.zeros((0, 3))])
+        self.bmax = np.concatenate([self.sc + r, tv.max(axis=1) if self.nt else np.zeros((0, 3))])
+        self.lights = f.lights.astype(np.float64).reshape(-1, 7)
+        self.counts = dict(rays_primary=0, rays_reflection=0, rays_refraction=0, rays_shadow=0)
+        self.shade = True
+        self.strict = True  # False: near decisions are taken as float64 takes them (nominal value, counting)
+
+    def amb(self, why):
+        if self.strict:
+            raise Ambiguous(why)
+
+    # ---- materials -----------------------------------------------------------------------------------------------
+    def mat(self, row):
+        m = self.mats[row]
+        return dict(color=m[0:3], metallic=m[3], shininess=m[4], ior=m[5], opacity=m[6], boost=m[7],
+                    tr=bool(self.mat_tr[row]))
+
+    def fresnel(self, m, n, v, other):
+        """compute_fresnel (material.rs): reflectance; returns (value, inside-decision near)"""
+        if not m["tr"]:
+            return np.full(3, m["metallic"]), False
+        nv = n @ v
+        c = abs(nv)
+        inside = nv < 0
+        eta = m["ior"] / other if inside else other / m["ior"]
+        sin2 = eta * eta * (1 - c * c)
+        near = abs(nv) < M_COS or (inside and abs(sin2 - 1) < M_TIR and not m["metallic"] > 0)
+        if (inside and sin2 > 1) or m["metallic"] > 0:
+            return np.full(3, m["metallic"] if m["metallic"] > 0 else 1.0), near
+        f0 = ((other - m["ior"]) / (other + m["ior"])) ** 2
+        f0v = f0 * (1 - m["metallic"]) + m["color"] * m["metallic"]
+        return f0v + (1 - f0v) * (1 - c) ** 5, near
+
+    # ---- intersections: rays (R,3) x objects ----------------------------------------------------------------------
+    def intersect(self, O, D, idx=None, tmax=None):
+        """-> ids (K,), t (R,K), valid (R,K), near (R,K), objects in object order (spheres, then triangles)."""
+        R = O.shape[0]
+        if idx is None:
+            idx = np.arange(self.ns + self.nt)
+        sid, tid = idx[idx < self.ns], idx[idx >= self.ns] - self.ns
+        ts, vs, ns_ = self._spheres(O, D, sid)
+        tt, vt, nt_ = self._triangles(O, D, tid)
+        t = np.concatenate([ts, tt], axis=1)
+        valid = np.concatenate([vs, vt], axis=1)
+        near = np.concatenate([ns_, nt_], axis=1)
+        ids = np.concatenate([sid, tid + self.ns])
+        if tmax is not None and ids.size:
+            tm = tmax[:, None]
+            c, n = t <= tm, np.abs(tm - t) < M_TMAX
+            near = (valid & n) | (near & (c | n))
+            valid = valid & c
+        assert t.shape == (R, ids.size)
+        return ids, t, valid, near
+
+    def _spheres(self, O, D, sid):
+        R = O.shape[0]
+        if sid.size == 0:
+            z = np.zeros((R, 0))
+            return z, z.astype(bool), z.astype(bool)
+        v = O[:, None, :] - self.sc[sid][None]
+        r2 = self.sr2[sid][None]
+        b = _dot(D[:, None, :], v)
+        vv = _dot(v, v)
+        cc = vv - r2
+        disc = b * b - cc
+        s = np.sqrt(np.maximum(disc, 0.0))
+        t0, t1 = -b - s, -b + s
+        r = np.sqrt(r2)
+        ncos = s / r  # |d . n| at either root
+        c_disc = (disc >= 0, np.abs(disc) < M_DISC * (b * b + vv + r2))
+        c_t1 = (t1 >= 0, np.abs(t1) * ncos < M_PLANE)
+        valid, near = _decide([c_disc, c_t1])
+        t = np.where(t0 >= 0, t0, t1)
+        # the root choice (t0 >= 0) is a decision too: a flip changes t
+        near |= valid & (np.abs(t0) * ncos < M_PLANE)
+        return t, valid, near
+
+    def _triangles(self, O, D, tid):
+        R = O.shape[0]
+        if tid.size == 0:
+            z = np.zeros((R, 0))
+            return z, z.astype(bool), z.astype(bool)
+        e1, e2, v1 = self.e1[tid][None], self.e2[tid][None], self.v1[tid][None]
+        Dd = D[:, None, :]
+        pv = _cross(Dd, e2)
+        det = _dot(e1, pv)
+        tv = O[:, None, :] - v1
+        qv = _cross(tv, e1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = _dot(tv, pv) / det
+            v = _dot(Dd, qv) / det
+            t = _dot(e2, qv) / det
+            ad = np.abs(det)
+            ntv, npv, nqv = np.sqrt(_dot(tv, tv)), np.sqrt(_dot(pv, pv)), np.sqrt(_dot(qv, qv))
+            cosn = ad / self.n_e1xe2[tid][None]  # |d . n|
+            conds = [
+                (ad > EPS, np.abs(ad - EPS) < M_DET * self.e12[tid][None]),
+                (t > EPS, np.abs(t - EPS) * cosn < M_PLANE),
+                (u >= 0, np.abs(u) * ad < M_BARY * ntv * npv),
+                (v >= 0, np.abs(v) * ad < M_BARY * nqv),
+                (u + v < 1, np.abs(1 - u - v) * ad < M_BARY * (ntv * npv + nqv + ad)),
+            ]
+        valid, near = _decide(conds)
+        return np.where(valid, t, np.inf), valid, near
+
+    def normal(self, oid, p):
+        if oid < self.ns:
+            return norm(p - self.sc[oid])
+        return self.tn[oid - self.ns]
+
+    def nearest(self, o, d):
+        """cast_ray (raytracer.rs): nearest valid hit, ties to the later object.  Raises Ambiguous if the choice is
+        near.  -> (t, id, p, n, material row) or None."""
+        ids, t, valid, near = self.intersect(o[None], d[None])
+        t, valid, near = t[0], valid[0], near[0]
+        tv = np.where(valid, t, np.inf)
+        if not valid.any():
+            if near.any():
+                self.amb("near hit on a missing ray")
+            return None
+        k = len(tv) - 1 - int(np.argmin(tv[::-1]))  # ties go to the later object
+        tb = tv[k]
+        if near[k] or (near & (t <= tb + M_TIE)).any():
+            self.amb("near decision on the nearest hit")
+        others = np.delete(tv, k)
+        if others.size and others.min() - tb < M_TIE:
+            self.amb("two objects tie for the nearest hit")
+        oid = int(ids[k])
+        p = o + d * tb
+        return tb, oid, p, self.normal(oid, p), int(self.obj_mat[oid])
+
+    # ---- shadows ---------------------------------------------------------------------------------------------------
+    def _candidates(self, so, lp):
+        """objects whose padded AABB meets the padded AABB of some segment so -> lp (conservative in float64)"""
+        lo = np.minimum(so, lp) - PAD
+        hi = np.maximum(so, lp) + PAD
+        hit = np.ones(self.bmin.shape[0], bool)
+        # one box per light cloud keeps this cheap; the union of segment boxes is covered by the box of all of them
+        keep = np.zeros(self.bmin.shape[0], bool)
+        for a in range(0, lo.shape[0], self.N):
+            blo, bhi = lo[a:a + self.N].min(axis=0), hi[a:a + self.N].max(axis=0)
+            keep |= hit & np.all(self.bmax >= blo, axis=1) & np.all(self.bmin <= bhi, axis=1)
+        return np.nonzero(keep)[0]
+
+    def _chain(self, ids, valid, io, absorb):
+        """has_any_intersection's walk in object order for a batch of rays -> occluded (R,), opacity (R,),
+        filter (R,3), opacity-decision near (R,)"""
+        R = valid.shape[0]
+        op, filt = np.ones(R), np.ones((R, 3))
+        occ, near = np.zeros(R, bool), np.zeros(R, bool)
+        for k in np.nonzero(valid.any(axis=0))[0]:
+            on = valid[:, k] & ~occ
+            op = np.where(on, np.clip(op - (1 - io[:, k]), 0.0, 1.0), op)
+            if not self.obj_tr[ids[k]]:
+                near |= on & (np.abs(np.abs(op) - EPS) < M_OP)
+                occ |= on & (np.abs(op) <= EPS)
+            filt = np.where(on[:, None], filt - absorb[:, k], filt)
+        return occ, op, filt, near
+
+    def shadows(self, p, n, m, view, LP, LC, LI):
+        """calculate_lighting over the expanded light list from hit point p -> (direct Iv, spec Iv, unoccluded (NL,))"""
+        NL = LP.shape[0]
+        self.counts["rays_shadow"] += NL
+        if not self.shade:
+            return None, None, None
+        ltp = LP - p
+        lmag = np.sqrt(_dot(ltp, ltp))
+        ld = ltp / lmag[:, None]
+        so = p + ld * self.eps_d
+        tmax = np.sqrt(_dot(LP - so, LP - so))
+        idx = self._candidates(so, LP)
+        ids, t, valid, near = self.intersect(so, ld, idx, tmax)
+        # per (ray, object) chain terms
+        K = ids.size
+        io = np.zeros((NL, K))
+        absorb = np.zeros((NL, K, 3))
+        for k in np.nonzero((valid | near).any(axis=0))[0]:
+            om = self.mat(int(self.obj_mat[ids[k]]))
+            op_m = min(max(om["opacity"] if om["tr"] else 1.0, 0.0), 1 - EPS)
+            absorb[:, k] = om["color"] * (1 - op_m)
+            if om["tr"]:
+                for r in np.nonzero(valid[:, k] | near[:, k])[0]:
+                    q = so[r] + ld[r] * t[r, k]
+                    R, fn = self.fresnel(om, self.normal(int(ids[k]), q), -ld[r], 1.0)
+                    if fn:
+                        self.amb("near inside/outside decision on a shadow ray's Fresnel term")
+                    io[r, k] = om["opacity"] * (1 - R[0])
+        occ, op, filt, opnear = self._chain(ids, valid, io, absorb)
+        if opnear.any():
+            self.amb("near |opacity| <= EPS decision")
+        # contribution (light.rs calculate_contribution_at + calculate_lighting)
+        mc, shin = m["color"], m["shininess"]
+        dist = lmag + EPS
+        cosi = _dot(ltp, n) / dist
+        sig = np.clip((np.tanh(0.95 * (EPS + dist + dist * dist)) + 1) / 2, 0.0, 1.0)
+        cint = np.where(cosi > 0, cosi * LI * sig, 0.0)
+        ccol = np.where((cosi > 0)[:, None], mc * LC, 0.0)
+        ndl = _dot(ld, n)
+        diff = np.maximum(ndl, 0.0)
+        if shin > 0:
+            rr = ld - 2 * ndl[:, None] * n
+            rr = rr / np.sqrt(_dot(rr, rr))[:, None]
+            specf = np.maximum(_dot(rr, view), 0.0) ** max(shin * 512, 1.0)
+        else:
+            specf = np.zeros(NL)
+        lit = diff > 0
+
+        def contrib(r, occ_r, op_r, filt_r):
+            if occ_r or not lit[r]:
+                return np.zeros(3), np.zeros(3)
+            Lc = ccol[r] / filt_r
+            dcol = mc * Lc * (diff[r] * cint[r] * op_r)
+            scol = LC[r] * (cint[r] * op_r * specf[r]) if shin > 0 else np.zeros(3)
+            return dcol, scol
+
+        dn, sn = np.zeros(3), np.zeros(3)
+        dlo, dhi, slo, shi = np.zeros(3), np.zeros(3), np.zeros(3), np.zeros(3)
+        cos_near = (np.abs(cosi) < M_COS) | (np.abs(ndl) < M_COS)
+        for r in range(NL):
+            dc, sc = contrib(r, occ[r], op[r], filt[r])
+            dn, sn = dn + dc, sn + sc
+            outs = [(dc, sc)]
+            flips = np.nonzero(near[r])[0]
+            if flips.size > MAX_FLIPS:
+                self.amb(f"{flips.size} near objects on one shadow ray")
+                flips = flips[:0]
+            for mask in range(1, 1 << flips.size):
+                vr = valid[r:r + 1].copy()
+                for j, k in enumerate(flips):
+                    if mask >> j & 1:
+                        vr[0, k] = not vr[0, k]
+                o2, p2, f2, n2 = self._chain(ids, vr, io[r:r + 1], absorb[r:r + 1])
+                if n2.any():
+                    self.amb("near |opacity| <= EPS decision")
+                outs.append(contrib(r, o2[0], p2[0], f2[0]))
+            if cos_near[r]:
+                outs.append((np.zeros(3), np.zeros(3)))
+            ds, ss = np.array([o[0] for o in outs]), np.array([o[1] for o in outs])
+            dlo, dhi = dlo + ds.min(axis=0), dhi + ds.max(axis=0)
+            slo, shi = slo + ss.min(axis=0), shi + ss.max(axis=0)
+        return Iv(dn, dlo, dhi), Iv(sn, slo, shi), ~occ
+
+    # ---- the light list of one pixel (to_point_light_cloud + preprocess, seeded: D4) -------------------------------
+    def light_list(self, gx, gy):
+        L = self.lights
+        if self.N == 1:
+            return L[:, 0:3].copy(), L[:, 3:6].copy(), L[:, 6].copy()
+        pix = gy * self.cfg.width + gx
+        lp, lc, li = [], [], []
+        for l in range(L.shape[0]):
+            s = cloud_hash(int(self.cfg.cloud_seed), pix, l) % self.cloud.shape[0]
+            lp.append(L[l, 0:3] + self.cloud[s] * self.fwhd)
+            lc.append(np.repeat(L[l:l + 1, 3:6], self.N, axis=0))
+            li.append(np.full(self.N, L[l, 6] / self.N))
+        return np.concatenate(lp), np.concatenate(lc), np.concatenate(li)
+
+    # ---- one ray ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def atten(t):
+        return min(max(1.0 / (1 + abs(t) + 0.1 * t * t), 0.0), 1.0)
+
+    def trace(self, o, d_raw, n_start, depth, kind, lights):
+        """single_raytrace.  depth None = a primary ray (children start at the configured depths).
+        -> (color Iv, t, id, unoccluded flags of the hit's lights) or None on a miss"""
+        if depth == 0:
+            return None
+        d = norm(d_raw)
+        if not np.all(np.isfinite(d)):
+            return None
+        self.counts[kind] += 1
+        h = self.nearest(o, d)
+        if h is None:
+            return None
+        t, oid, p, n, row = h
+        m = self.mat(row)
+        direct, spec, reach = self.shadows(p, n, m, d, *lights)
+        a = self.atten(t)
+        T, R = m["tr"], m["metallic"] > 0 or m["tr"]
+        refl = refr = Iv.zero()
+        if self.refl and R:
+            c = d @ n
+            if abs(c) < M_COS:
+                self.amb("near inside/outside decision (reflection)")
+            ins = c < 0
+            inorm = -n if ins else n
+            n2 = m["ior"] if ins else self.air
+            eta = n2 / n_start if ins else n_start / n2
+            sin2 = eta * eta * (1 - c * c)
+            if T and not m["metallic"] > 0 and abs(sin2 - 1) < M_TIR:
+                self.amb("near total internal reflection")
+            if m["metallic"] > 0 or (T and sin2 >= 1):
+                r = norm(d - 2 * (d @ n) * n)
+                Rf, fn = self.fresnel(m, inorm, -d, n_start)
+                if fn:
+                    self.amb("near Fresnel decision (reflection)")
+                cd = self.cfg.max_depth_reflection if depth is None else max(depth - 1, 0)
+                ch = self.trace(p + r * self.eps_d, r, n_start, cd, "rays_reflection", lights)
+                if ch is not None and self.shade:
+                    refl = ch[0].scale(self.atten(ch[1]) * Rf)
+        if self.refr and T:
+            c = d @ n
+            if abs(c) < M_COS:
+                self.amb("near inside/outside decision (refraction)")
+            ins = c <= 0
+            inorm = -n if ins else n
+            n2 = m["ior"] if ins else self.air
+            eta = n2 / n_start if ins else n_start / n2
+            Rf, fn = self.fresnel(m, inorm, d, 1 / eta)
+            if fn:
+                self.amb("near Fresnel decision (refraction)")
+            nn, e = -inorm, 1 / eta
+            ndi = nn @ d
+            k = 1 - e * e * (1 - ndi * ndi)
+            if abs(k) < M_TIR:
+                self.amb("near total internal reflection (refract)")
+            op = m["opacity"]
+            step = 2 if op < 0.5 else 1
+            fac = 3 if op <= 0.3 else (2 if op < 0.5 else 1)
+            cd = self.cfg.max_depth_refraction // fac if depth is None else (depth - step if depth > step else 0)
+            if k >= 0:
+                q = norm(d * e - nn * (e * ndi + np.sqrt(k)))
+                ch = self.trace(p + q * self.eps_d, q, n2, cd, "rays_refraction", lights)
+            else:  # refract() gives the zero vector: a NaN direction, no ray (DESIGN D2)
+                ch = None
+            if ch is not None and self.shade:
+                refr = ch[0].scale((1 + m["boost"]) * (1 - Rf))
+        if not self.shade:
+            return Iv.zero(), t, oid, None
+        direct = (Iv(m["color"] * self.ambient) + direct).scale(a)
+        spec = spec.scale(a)
+        return ((refl + refr + spec) if T else (direct + refl + spec)), t, oid, reach
+
+    # ---- one pixel (antialiased_raytrace / render_pixel_colors) ----------------------------------------------------
+    def render_pixel(self, gx, gy):
+        """-> dict(iv, id, t, written, reach) ; raises Ambiguous"""
+        coords = np.array([gx * self.fwhd[0], gy * self.fwhd[1], 0.0])
+        D = coords - self.focus
+        lights = self.light_list(gx, gy)
+        if self.aa is None:
+            r = self.trace(coords, D, self.air, None, "rays_primary", lights)
+            if r is None:
+                return dict(iv=None, id=-1, t=0.0, written=False, reach=None)
+            return dict(iv=r[0], id=r[2], t=r[1], written=True, reach=r[3])
+        n = self.aa.shape[0]
+        w = 1.0 / (8 * -(-n // 8))
+        acc, any_hit, first = Iv.zero(), False, None
+        for k in range(n):
+            o = coords + np.array([self.aa[k, 0], self.aa[k, 1], 0.0])
+            r = self.trace(o, D, self.air, None, "rays_primary", lights)
+            if k == 0:
+                first = r
+            if r is not None:
+                any_hit = True
+                acc = acc + r[0].scale(w)
+        return dict(iv=acc if any_hit else None, id=-1 if first is None else first[2], t=0.0 if first is None else first[1],
+                    written=any_hit, reach=None if first is None else first[3])
+
+    def pixel(self, gx, gy):
+        """nominal colour of a pixel (every decision as float64 takes it), None on a miss"""
+        saved, self.strict = self.strict, False
+        try:
+            r = self.render_pixel(gx, gy)
+        finally:
+            self.strict = saved
+        return None if r["iv"] is None else r["iv"].nom
+
+    def count_frame(self, window=None):
+        """the frame's ray counters and written pixels, as the reference casts them (no shading)"""
+        x0, y0, w, h = window or (0, 0, self.cfg.width, self.cfg.height)
+        saved = self.shade, self.strict
+        self.shade, self.strict = False, False
+        self.counts = dict.fromkeys(self.counts, 0)
+        written = 0
+        try:
+            for gy in range(y0, y0 + h):
+                for gx in range(x0, x0 + w):
+                    written += int(self.render_pixel(gx, gy)["written"])
+        finally:
+            self.shade, self.strict = saved
+        return dict(self.counts, pixels_written=written)
+
+
+def build_scene(cfg, soft=False):
+    """The known-answer scene: a wall of two triangles, a glass, an opaque and a metallic sphere, two lights.
+    soft=True adds what soft shadows and AA must get right: a glass pane of two triangles sharing an edge, between the
+    wall and light 0 and behind the glass sphere (object order differs from t order on its shadow rays, and shadow rays
+    cross the shared edge); a third light whose cloud box holds a small opaque sphere (cloud points inside an occluder);
+    a fourth light grazing the wall (cos_i near 0)."""
+    f32 = np.float32
+    sh, sd = float(cfg.scene_height), float(cfg.scene_depth)
+    mats = np.asarray([
+        [0.8, 0.7, 0.6, 0.0, 0.3, 1.0, 0.0, 0.0, 0],      # 0 wall: diffuse + specular
+        [0.6, 0.9, 0.7, 0.0, 0.2, 1.5, 0.7, 0.1, 1],      # 1 glass: transmissive, opacity 0.7, boost 0.1
+        [0.9, 0.3, 0.2, 0.0, 0.0, 1.0, 0.0, 0.0, 0],      # 2 opaque diffuse
+        [0.9, 0.9, 0.95, 0.8, 0.5, 1.0, 0.0, 0.0, 0],     # 3 metallic mirror
+        [0.7, 0.8, 0.9, 0.0, 0.1, 1.3, 0.4, 0.0, 1],      # 4 thin glass pane: opacity 0.4
+    ], f32)
+    # wall: two big triangles at z = 0.8 sd facing the camera (normal -z)
+    z = 0.8 * sd
+    quad = [(-1.0, -1.0, z), (3.0, -1.0, z), (-1.0, 3.0, z)], [(3.0, 3.0, z), (-1.0, 3.0, z), (3.0, -1.0, z)]
+    tri_mat = [0, 0]
+    sc = [[0.30, 0.45 * sh, 0.45 * sd], [0.62, 0.40 * sh, 0.40 * sd], [0.80, 0.70 * sh, 0.35 * sd]]
+    sr = [0.11, 0.07, 0.08]
+    sm = [1, 2, 3]
+    lights = [[0.45, 0.15 * sh, 0.0, 1.0, 0.95, 0.9, 0.8], [0.1, 0.8 * sh, 0.1 * sd, 0.9, 1.0, 1.0, 0.5]]
+    if soft:
+        # glass pane between the wall and light 0, behind the glass sphere (seen from the wall): z = 0.65 sd
+        zp = 0.65 * sd
+        a, b, c, d = (0.05, 0.35 * sh, zp), (0.45, 0.35 * sh, zp), (0.45, 0.85 * sh, zp), (0.05, 0.85 * sh, zp)
+        quad = quad + ([a, b, c], [a, c, d])  # shared edge a-c
+        tri_mat += [4, 4]
+        # light 2 with a small opaque sphere inside its cloud box
+        n = max(int(cfg.point_light_multiplicator), 1)
+        R = float(f32(1.725) + f32(n) / f32(20.0)) if n > 1 else 0.0
+        box = np.array([float(cfg.fw), float(cfg.fh), float(cfg.fd)]) * R
+        L2 = np.array([0.75, 0.2 * sh, 0.15 * sd])
+        sc.append((L2 + 0.5 * box).tolist())
+        sr.append(0.3 * float(box.min()) if n > 1 else 0.01)
+        sm.append(2)
+        lights.append([*L2.tolist(), 0.8, 0.85, 1.0, 0.7])
+        # light 3 grazing the wall: its cloud straddles the wall's plane
+        lights.append([0.9, 0.5 * sh, z - 0.5 * float(box[2]), 1.0, 0.9, 0.7, 0.6])
+    v1 = np.asarray([q[0] for q in quad], f32)
+    e1 = np.asarray([np.subtract(q[1], q[0]) for q in quad], f32)
+    e2 = np.asarray([np.subtract(q[2], q[0]) for q in quad], f32)
+    nrm = np.cross(e1.astype(np.float64), e2.astype(np.float64))
+    nrm = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(f32)
+    nrm[:2] = [0, 0, -1]
+    sc, sr = np.asarray(sc, f32), np.asarray(sr, f32)
+    return FlatScene(sc, (sr * sr).astype(f32), (1 / sr).astype(f32), np.asarray(sm, np.uint32),
+                     v1, e1, e2, nrm, np.asarray(tri_mat, np.uint32), mats, np.asarray(lights, f32))
