@@ -9,7 +9,7 @@ framebuffer are resident in HBM before the timed region.  At N > 1 the frame is 
 its tiles into a rank-compact staging buffer and the packed pixels are gathered to rank 0 with ONE
 ncclSend / ncclRecv group (C ABI: rt_comm_* / rt_render_gather_device) inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Frames are enqueued on two streams alternately (two frames in flight, each into its own frame buffer): a launch cannot
@@ -20,6 +20,12 @@ frame; the K steps are bracketed by barrier + synchronise.
 Rank 0 prints ONE JSON line.  `value` = (primary + reflection + refraction rays of one frame as the
 reference casts them, all ranks) / (max-over-ranks seconds per frame), in Mray/s; `value_traced` = the rays the GPU
 traced (repeated AA samples once) over the same time.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the K timed steps, --dump-outputs.  --full adds
+what takes runs or work of its own, all after the timed region: frames alone on one stream (`ms_per_frame_alone`,
+per-rank kernel and gather times, `roofline`), the D2H copy, `boundary` costs, the frame under the library's default
+scene budget (`lean_scene`), configs 4 and 5 (`other_workloads`) and the CPU baseline (`cpu_baseline`); --no-* drop
+single parts of it.
 
 --dump-outputs DIR writes the frame of the last timed step, as the caller's buffer holds it, to DIR (dump_outputs below):
 the scene and its sample tables are seeded, so two builds run with the same arguments can be compared output for output.
@@ -40,8 +46,8 @@ import numpy as np  # noqa: E402
 
 # Device memory a scene may spend on its optional acceleration tables (rt_scene_desc.device_budget_bytes).  The library's
 # default is 128 MiB, under which semesterbild keeps its receiver flags (22 MB) but not the per-cell candidate lists (0.86 GB
-# for 2 % of a frame); the bench opts into them and says so (config.scene_budget_bytes, config.scene_memory; the frame time
-# under the library's default budget is reported beside it as `lean_scene`).
+# for 2 % of a frame); the bench opts into them and says so (config.scene_budget_bytes, config.scene_memory; with --full the
+# frame time under the library's default budget is reported beside it as `lean_scene`).
 SCENE_BUDGET = 2 << 30
 ALG_BYTES_PER_RAY = 64.0  # 32 B ray in + 32 B hit out
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
@@ -139,6 +145,71 @@ def pmc_summary(workload, build_id):
         out["_kernel"] = vals.get("kernel", "")
         return out
     return None
+
+
+def roofline(workload, own, rays, shadow_rays, sec_per_step, flat, build_id, n_iso, world):
+    """`roofline` of --full: the bounds of the dominant kernel from `own["kernel_ms"]` (the mean of n_iso frames alone on one
+    stream) and, on one GPU, from the PMC summary of this build (pmc_summary)."""
+    kernel_ms = own["kernel_ms"]
+    # (1) the HBM bound SURVEY 8(d) prescribes: algorithmic 64 B per ray actually traced by this rank's launches
+    achieved = own["rays_traced"] * ALG_BYTES_PER_RAY / (kernel_ms * 1e-3) / 1e9
+    pmc = pmc_summary(workload, build_id) if world == 1 else None
+    traffic = None
+    if pmc and "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
+        # KiB -> B; FETCH_SIZE x 2 on gfx950 (MI355X_MICROARCH.md, HBM)
+        traffic = pmc["FETCH_SIZE"] * 1024.0 * 2.0 + pmc["WRITE_SIZE"] * 1024.0
+    # (2) the bound that applies: vector-instruction issue.  Instructions of the dominant kernel per launch x
+    # issue cycles (2 per plain VALU instruction on a SIMD-32, 4 per transcendental) / (1024 SIMDs x cycles)
+    valu = None
+    if pmc and "SQ_INSTS_VALU" in pmc and "GRBM_GUI_ACTIVE" in pmc:
+        cycles = pmc["GRBM_GUI_ACTIVE"] / 8.0  # summed over the 8 XCDs
+        trans = pmc.get("SQ_INSTS_VALU_TRANS_F32", 0.0)
+        issue = (pmc["SQ_INSTS_VALU"] - trans) * VALU_CYC + trans * TRANS_CYC
+        valu = {
+            "bound": "valu_issue", "kernel": pmc["_kernel"], "achieved": issue / cycles, "peak": float(N_SIMD),
+            "unit": "SIMD issue cycles per cycle", "frac": issue / (N_SIMD * cycles),
+            "insts_valu": pmc["SQ_INSTS_VALU"], "insts_valu_trans": trans if "SQ_INSTS_VALU_TRANS_F32" in pmc else None,
+            "insts_salu": pmc.get("SQ_INSTS_SALU"), "insts_smem": pmc.get("SQ_INSTS_SMEM"),
+            "kernel_cycles": cycles, "source": pmc["_file"],
+        }
+    # (3) flops, SURVEY 8(d): what the reference's brute-force scan would have spent on this frame's rays (every ray
+    # AND every shadow ray tests every object, raytracer.rs:48,180), and what the kernels actually executed (fp32
+    # vector instructions of the dominant kernel from the PMC summary x the lanes active in them; fma = 2 flop)
+    per_scan = FLOP_SPHERE * flat.n_spheres + FLOP_TRIANGLE * flat.n_triangles
+    brute = (rays + shadow_rays) * per_scan
+    flops = {
+        "peak_tflops": FP32_VECTOR_PEAK_TFLOPS, "unit": "Gflop/s",
+        "brute_force_equivalent": brute / sec_per_step / 1e9,
+        "brute_force_equivalent_frac_of_peak": brute / sec_per_step / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
+        "flop_per_scan": per_scan,
+        "note": "brute-force equivalent = (rays + shadow rays, as the reference casts them) x (35 S + 85 T); above the "
+                "vector peak means the BVH and the beam tests removed that work, not that the ALUs did it",
+        "bvh_actual": None, "bvh_actual_frac_of_peak": None,
+    }
+    if pmc and all(k in pmc for k in ("SQ_INSTS_VALU_FMA_F32", "SQ_INSTS_VALU_MUL_F32", "SQ_INSTS_VALU_ADD_F32")):
+        lanes = 64.0
+        if pmc.get("SQ_ACTIVE_INST_VALU") and pmc.get("SQ_THREAD_CYCLES_VALU"):
+            lanes = min(64.0, pmc["SQ_THREAD_CYCLES_VALU"] / pmc["SQ_ACTIVE_INST_VALU"])
+        wave_flop = 2.0 * pmc["SQ_INSTS_VALU_FMA_F32"] + pmc["SQ_INSTS_VALU_MUL_F32"] + pmc["SQ_INSTS_VALU_ADD_F32"] + \
+            pmc.get("SQ_INSTS_VALU_TRANS_F32", 0.0)
+        actual = wave_flop * lanes  # per frame of the dominant kernel
+        flops.update(bvh_actual=actual / (kernel_ms * 1e-3) / 1e9,
+                     bvh_actual_frac_of_peak=actual / (kernel_ms * 1e-3) / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
+                     bvh_actual_flop_per_frame=actual, active_lanes_per_valu_inst=lanes, source=pmc["_file"])
+    return {
+        "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+        "traffic_source": pmc["_file"] if (pmc and traffic is not None) else None,
+        "kernel": DOMINANT_KERNEL[workload], "kernel_ms": kernel_ms,
+        "kernel_ms_note": f"mean of {n_iso} launches alone on one stream, HIP events on that stream, after the timed region",
+        "algorithmic_bytes": own["rays_traced"] * ALG_BYTES_PER_RAY,
+        "note": "64 B per TRACED ray (SURVEY 8d ray-stream model); no ray touches HBM in this kernel, so this "
+                "fraction cannot rank it -- the applicable bound is `valu_issue` below",
+        "valu_issue": valu if valu is not None else
+        {"bound": "valu_issue", "frac": None,
+         "note": f"no profiles/*_{workload}_pmc.csv was collected on build {build_id} (tools/profile.sh)"},
+        "flops": flops,
+    }
 
 
 def cpu_info():
@@ -282,10 +353,13 @@ def main():
     ap.add_argument("--steps", type=int, default=200)  # ~1 s of frames: enough for a GPU-busy sampler to see them
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-boundary-costs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: frames alone on one stream and the "
+                         "roofline, D2H, boundary costs, the lean scene, configs 4 and 5, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`")
+    ap.add_argument("--no-boundary-costs", action="store_true", help="--full: skip `boundary` and `lean_scene`")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="default run (config 3, one GPU): skip the short timings of configs 4 and 5 appended as `other_workloads`")
+                    help="--full (config 3, one GPU): skip the short timings of configs 4 and 5 appended as `other_workloads`")
     ap.add_argument("--in-flight", type=int, default=0, choices=[0, 1, 2, 3, 4],
                     help="frames in flight (streams used alternately).  0 = 2: the head of a frame fills the CUs the drain of the one "
                          "before leaves idle (frames with secondary rays: every ray-tree level is a launch with a drain of its own)")
@@ -383,35 +457,38 @@ def main():
     elapsed = time.perf_counter() - t0
     # the last timed step's frame, before the frames below reuse its buffer
     last_frame = fbs[(args.steps - 1) % n_fly].cpu().numpy() if (args.dump_outputs and rank == 0) else None
-    # The dominant kernel's launch duration, for the roofline: frames one after the other on ONE stream, each bracketed by
-    # events on that stream (with two frames in flight a launch shares the GPU with its neighbour and its duration says
-    # nothing about the kernel).  Outside the timed region.
-    n_iso = max(1, min(args.steps, 20))
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_iso)]
-    n_fly_timed, n_fly = n_fly, 1
-    for i in range(n_iso):
-        frame(0, *evs[i])
-    barrier()
-    n_fly = n_fly_timed
-    frame_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))  # device time of one step alone on its stream
-    infos = []
-    if rccl is not None:
-        infos.append(rccl.last())
+    n_fly_timed, frame_ms, n_iso, infos = n_fly, 0.0, 0, []
+    if args.full:
+        # The dominant kernel's launch duration, for the roofline: frames one after the other on ONE stream, each bracketed by
+        # events on that stream (with two frames in flight a launch shares the GPU with its neighbour and its duration says
+        # nothing about the kernel).  Outside the timed region.
+        n_iso = max(1, min(args.steps, 20))
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_iso)]
+        n_fly = 1
+        for i in range(n_iso):
+            frame(0, *evs[i])
+        barrier()
+        n_fly = n_fly_timed
+        frame_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))  # device time of one step alone on its stream
+        if rccl is not None:
+            infos.append(rccl.last())
 
+    # (the ray counters of the last frame rendered: every frame of the workload casts the same rays)
     st = _abi.rt_stats()
     _lib.check(lib.rt_render_collect_stats(ds.handle, C.byref(st)))
-    own = dict(rank=rank, rays=st.rays_primary + st.rays_reflection + st.rays_refraction, rays_traced=st.rays_traced,
-               frame_ms=frame_ms)
-    if infos:
-        gi = infos[-1]
-        own.update(kernel_ms=gi["render_ms"], gather_ms=gi["gather_ms"], bytes_sent=gi["bytes_sent"],
-                   bytes_received=gi["bytes_received"], tiles_owned=gi["tiles_owned"], rccl_ranks=gi["n_ranks"],
-                   rccl_rank=gi["rank"], transport={0: "none", 1: "rccl", 2: "local"}[gi["transport"]])
-    elif host_gather is not None:
-        own.update(kernel_ms=frame_ms, gather_ms=float(np.mean(gather_ms_host[-args.steps:])), bytes_sent=host_gather.bytes_sent,
-                   transport="gloo-host (rehearsal)")
-    else:
-        own.update(kernel_ms=frame_ms, gather_ms=0.0, bytes_sent=0, transport="none")
+    own = dict(rank=rank, rays=st.rays_primary + st.rays_reflection + st.rays_refraction, rays_traced=st.rays_traced)
+    if args.full:
+        own.update(frame_ms=frame_ms)
+        if infos:
+            gi = infos[-1]
+            own.update(kernel_ms=gi["render_ms"], gather_ms=gi["gather_ms"], bytes_sent=gi["bytes_sent"],
+                       bytes_received=gi["bytes_received"], tiles_owned=gi["tiles_owned"], rccl_ranks=gi["n_ranks"],
+                       rccl_rank=gi["rank"], transport={0: "none", 1: "rccl", 2: "local"}[gi["transport"]])
+        elif host_gather is not None:
+            own.update(kernel_ms=frame_ms, gather_ms=float(np.mean(gather_ms_host[-args.steps:])), bytes_sent=host_gather.bytes_sent,
+                       transport="gloo-host (rehearsal)")
+        else:
+            own.update(kernel_ms=frame_ms, gather_ms=0.0, bytes_sent=0, transport="none")
     counts = torch.tensor([st.rays_primary, st.rays_reflection, st.rays_refraction, st.rays_shadow,
                            st.pixels_written, st.rays_traced], dtype=torch.int64, device=dev)
     tmax = torch.tensor([elapsed, frame_ms], dtype=torch.float64, device=dev)
@@ -430,63 +507,13 @@ def main():
 
     if rank == 0:
         mrays = rays / sec_per_step / 1e6
-        kernel_ms = own["kernel_ms"]
         build_id = lib.rt_build_id().decode()
-        # ---- roofline of the dominant kernel ------------------------------------------------------------------------
-        # (1) the HBM bound SURVEY 8(d) prescribes: algorithmic 64 B per ray actually traced by this rank's launches
-        achieved = own["rays_traced"] * ALG_BYTES_PER_RAY / (kernel_ms * 1e-3) / 1e9
-        pmc = pmc_summary(args.workload, build_id) if world == 1 else None
-        traffic = None
-        if pmc and "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
-            # KiB -> B; FETCH_SIZE x 2 on gfx950 (MI355X_MICROARCH.md, HBM)
-            traffic = pmc["FETCH_SIZE"] * 1024.0 * 2.0 + pmc["WRITE_SIZE"] * 1024.0
-        # (2) the bound that applies: vector-instruction issue.  Instructions of the dominant kernel per launch x
-        # issue cycles (2 per plain VALU instruction on a SIMD-32, 4 per transcendental) / (1024 SIMDs x cycles)
-        valu = None
-        if pmc and "SQ_INSTS_VALU" in pmc and "GRBM_GUI_ACTIVE" in pmc:
-            cycles = pmc["GRBM_GUI_ACTIVE"] / 8.0  # summed over the 8 XCDs
-            trans = pmc.get("SQ_INSTS_VALU_TRANS_F32", 0.0)
-            issue = (pmc["SQ_INSTS_VALU"] - trans) * VALU_CYC + trans * TRANS_CYC
-            valu = {
-                "bound": "valu_issue", "kernel": pmc["_kernel"], "achieved": issue / cycles, "peak": float(N_SIMD),
-                "unit": "SIMD issue cycles per cycle", "frac": issue / (N_SIMD * cycles),
-                "insts_valu": pmc["SQ_INSTS_VALU"], "insts_valu_trans": trans if "SQ_INSTS_VALU_TRANS_F32" in pmc else None,
-                "insts_salu": pmc.get("SQ_INSTS_SALU"), "insts_smem": pmc.get("SQ_INSTS_SMEM"),
-                "kernel_cycles": cycles, "source": pmc["_file"],
-            }
-        # (3) flops, SURVEY 8(d): what the reference's brute-force scan would have spent on this frame's rays (every ray
-        # AND every shadow ray tests every object, raytracer.rs:48,180), and what the kernels actually executed (fp32
-        # vector instructions of the dominant kernel from the PMC summary x the lanes active in them; fma = 2 flop)
-        per_scan = FLOP_SPHERE * flat.n_spheres + FLOP_TRIANGLE * flat.n_triangles
-        brute = (rays + counts[3]) * per_scan
-        flops = {
-            "peak_tflops": FP32_VECTOR_PEAK_TFLOPS, "unit": "Gflop/s",
-            "brute_force_equivalent": brute / sec_per_step / 1e9,
-            "brute_force_equivalent_frac_of_peak": brute / sec_per_step / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
-            "flop_per_scan": per_scan,
-            "note": "brute-force equivalent = (rays + shadow rays, as the reference casts them) x (35 S + 85 T); above the "
-                    "vector peak means the BVH and the beam tests removed that work, not that the ALUs did it",
-            "bvh_actual": None, "bvh_actual_frac_of_peak": None,
-        }
-        if pmc and all(k in pmc for k in ("SQ_INSTS_VALU_FMA_F32", "SQ_INSTS_VALU_MUL_F32", "SQ_INSTS_VALU_ADD_F32")):
-            lanes = 64.0
-            if pmc.get("SQ_ACTIVE_INST_VALU") and pmc.get("SQ_THREAD_CYCLES_VALU"):
-                lanes = min(64.0, pmc["SQ_THREAD_CYCLES_VALU"] / pmc["SQ_ACTIVE_INST_VALU"])
-            wave_flop = 2.0 * pmc["SQ_INSTS_VALU_FMA_F32"] + pmc["SQ_INSTS_VALU_MUL_F32"] + pmc["SQ_INSTS_VALU_ADD_F32"] + \
-                pmc.get("SQ_INSTS_VALU_TRANS_F32", 0.0)
-            actual = wave_flop * lanes  # per frame of the dominant kernel
-            flops.update(bvh_actual=actual / (kernel_ms * 1e-3) / 1e9,
-                         bvh_actual_frac_of_peak=actual / (kernel_ms * 1e-3) / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
-                         bvh_actual_flop_per_frame=actual, active_lanes_per_valu_inst=lanes, source=pmc["_file"])
         out = {
             "metric": ("Mray/s (primary+secondary, rays counted as the reference casts them), semesterbild@high_resolution"
                        if args.workload == "c3" else "Mray/s (primary+secondary, rays counted as the reference casts them)"),
             "value": mrays, "unit": "Mray/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            # `value` / `ms_per_step` are PIPELINED throughput (frames_in_flight frames on alternating streams)
             "ms_per_step": sec_per_step * 1e3, "higher_is_better": True, "scaling": "strong",
-            # `value` / `ms_per_step` are PIPELINED throughput (frames_in_flight frames on alternating streams).  One frame alone on
-            # one stream (device time between HIP events on that stream, mean of the isolated frames after the timed region;
-            # slowest rank at N > 1, gather included):
-            "ms_per_frame_alone": frame_ms_slowest, "value_alone": rays / (frame_ms_slowest * 1e-3) / 1e6,
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             # the rays the GPU actually traced (bit-identical repeats of the AA sample table are traced once)
             "value_traced": counts[5] / sec_per_step / 1e6,
@@ -503,55 +530,48 @@ def main():
                 "first_scene_create_ms_incl_hip_init": first_scene_create_ms,
                 "scene_budget_bytes": SCENE_BUDGET, "scene_memory": ds.memory_info(), "phases": args.phases,
             },
-            "roofline": {
-                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                "traffic_source": pmc["_file"] if (pmc and traffic is not None) else None,
-                "kernel": DOMINANT_KERNEL[args.workload], "kernel_ms": kernel_ms,
-                "kernel_ms_note": f"mean of {n_iso} launches alone on one stream, HIP events on that stream, after the timed region",
-                "algorithmic_bytes": own["rays_traced"] * ALG_BYTES_PER_RAY,
-                "note": "64 B per TRACED ray (SURVEY 8d ray-stream model); no ray touches HBM in this kernel, so this "
-                        "fraction cannot rank it -- the applicable bound is `valu_issue` below",
-                "valu_issue": valu if valu is not None else
-                {"bound": "valu_issue", "frac": None,
-                 "note": f"no profiles/*_{args.workload}_pmc.csv was collected on build {build_id} (tools/profile.sh)"},
-                "flops": flops,
-            },
             "ranks": per_rank,
         }
-        if world == 1:
-            # device -> host copy of the packed frame (the boundary's rt_render pays it; never part of `value`)
-            host = torch.empty(npix, dtype=torch.int32).pin_memory()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            d2h = []
-            for _ in range(4):
-                e0.record()
-                host.copy_(fbs[0], non_blocking=True)
-                e1.record()
+        if args.full:
+            # One frame alone on one stream (device time between HIP events on that stream, mean of the isolated frames after
+            # the timed region; slowest rank at N > 1, gather included)
+            out.update(ms_per_frame_alone=frame_ms_slowest, value_alone=rays / (frame_ms_slowest * 1e-3) / 1e6,
+                       roofline=roofline(args.workload, own, rays, counts[3], sec_per_step, flat, build_id, n_iso, world))
+            if world == 1:
+                # device -> host copy of the packed frame (the boundary's rt_render pays it; never part of `value`)
+                host = torch.empty(npix, dtype=torch.int32).pin_memory()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                d2h = []
+                for _ in range(4):
+                    e0.record()
+                    host.copy_(fbs[0], non_blocking=True)
+                    e1.record()
+                    torch.cuda.synchronize(dev)
+                    d2h.append(e0.elapsed_time(e1))
+                out["d2h_ms"] = float(np.median(d2h[1:]))
+                out["config"]["mray_per_s_incl_d2h"] = rays / (sec_per_step + out["d2h_ms"] * 1e-3) / 1e6
+                if not args.no_boundary_costs:
+                    out["boundary"] = boundary_costs(cfg, flat, lib, _abi, _lib, local_rank)
+            if world == 1 and args.workload == "c3" and not args.no_boundary_costs:
+                # the same frame under the library's DEFAULT scene budget (128 MiB: receiver flags, no per-cell candidate lists)
+                lean = DeviceScene(flat, device=local_rank)
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(12)]
+                for a, b in ev:
+                    a.record(streams[0])
+                    _lib.check(lib.rt_render_device(lean.handle, C.byref(p), C.c_void_p(fbs[0].data_ptr()), None,
+                                                    C.c_void_p(streams[0].cuda_stream)))
+                    b.record(streams[0])
                 torch.cuda.synchronize(dev)
-                d2h.append(e0.elapsed_time(e1))
-            out["d2h_ms"] = float(np.median(d2h[1:]))
-            out["config"]["mray_per_s_incl_d2h"] = rays / (sec_per_step + out["d2h_ms"] * 1e-3) / 1e6
-            if not args.no_boundary_costs:
-                out["boundary"] = boundary_costs(cfg, flat, lib, _abi, _lib, local_rank)
-        if world == 1 and args.workload == "c3" and not args.no_boundary_costs:
-            # the same frame under the library's DEFAULT scene budget (128 MiB: receiver flags, no per-cell candidate lists)
-            lean = DeviceScene(flat, device=local_rank)
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(12)]
-            for a, b in ev:
-                a.record(streams[0])
-                _lib.check(lib.rt_render_device(lean.handle, C.byref(p), C.c_void_p(fbs[0].data_ptr()), None, C.c_void_p(streams[0].cuda_stream)))
-                b.record(streams[0])
-            torch.cuda.synchronize(dev)
-            out["lean_scene"] = {"ms_per_frame_alone": float(np.mean([a.elapsed_time(b) for a, b in ev[2:]])), "scene_memory": lean.memory_info(),
-                                 "note": "rt_scene_desc.device_budget_bytes = 0 (library default)"}
-            lean.close()
-        if world == 1 and args.workload == "c3" and not args.no_other_workloads:
-            # the other BASELINE configs under the same clock (a few frames each; their own bench lines: --workload c4 / c5)
-            out["other_workloads"] = {k: time_workload(k, lib, _abi, _lib, DeviceScene, torch, dev, local_rank, (streams * 2)[:2]) for k in ("c4", "c5")}
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(cfg, flat)
-            out["cpu_baseline"]["gpu_over_cpu"] = mrays / out["cpu_baseline"]["value"]
+                out["lean_scene"] = {"ms_per_frame_alone": float(np.mean([a.elapsed_time(b) for a, b in ev[2:]])),
+                                     "scene_memory": lean.memory_info(), "note": "rt_scene_desc.device_budget_bytes = 0 (library default)"}
+                lean.close()
+            if world == 1 and args.workload == "c3" and not args.no_other_workloads:
+                # the other BASELINE configs under the same clock (a few frames each; their own bench lines: --workload c4 / c5)
+                out["other_workloads"] = {k: time_workload(k, lib, _abi, _lib, DeviceScene, torch, dev, local_rank, (streams * 2)[:2])
+                                          for k in ("c4", "c5")}
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(cfg, flat)
+                out["cpu_baseline"]["gpu_over_cpu"] = mrays / out["cpu_baseline"]["value"]
         if last_frame is not None:
             out["outputs"] = dump_outputs(args.dump_outputs, last_frame, cfg.width, cfg.height)
         print(json.dumps(out))
