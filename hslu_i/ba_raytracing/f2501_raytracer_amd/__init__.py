@@ -7,3 +7,4 @@ from .config import DEFAULT_FEATURES, RenderConfig, expand_features  # noqa: F40
 from .f32math import Isometry3, Rotor3, Similarity3, Vec3  # noqa: F401
 from .scene import (BoundedPlane, ColorType, FlatScene, Material, PointLight, Scene, SphereData,  # noqa: F401
                     TransmissionProperties, TriangleData, maximize_value)
+from .renderer import DeviceScene, IntersectionTest, RayHits  # noqa: F401

@@ -115,6 +115,20 @@ class rt_scene_info(C.Structure):
     ]
 
 
+class rt_ray_batch(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("n_rays", C.c_uint32), ("origin", C.c_void_p), ("direction", C.c_void_p),
+                ("max_distance", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class rt_ray_hits(C.Structure):
+    _fields_ = [("id", C.c_void_p), ("t", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("material", C.c_void_p)]
+
+
+class rt_ray_occlusion(C.Structure):
+    _fields_ = [("has_intersection", C.c_void_p), ("completely_occluded", C.c_void_p), ("combined_opacity", C.c_void_p),
+                ("color_filter", C.c_void_p)]
+
+
 def fptr(a: np.ndarray):
     assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(_fp)

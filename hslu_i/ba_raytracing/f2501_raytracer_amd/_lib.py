@@ -5,7 +5,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._abi import rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_scene_desc, rt_scene_info, rt_stats
+from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_scene_desc,
+                   rt_scene_info, rt_stats)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_HIP_LIB selects a diagnostic build of the same library (tools/, A/B timing); default: in-tree
@@ -15,6 +16,7 @@ EXPORTS = (
     "rt_scene_destroy", "rt_last_error", "rt_scene_bvh_info", "rt_scene_memory_info", "rt_build_id", "rt_selftest_exact_math",
     "rt_gather_layout", "rt_render_multi", "rt_render_multi_begin", "rt_render_multi_end", "rt_multi_release", "rt_comm_unique_id", "rt_comm_create", "rt_comm_destroy",
     "rt_render_gather_device", "rt_comm_last_gather", "rt_render_begin", "rt_render_poll", "rt_render_end",
+    "rt_cast_rays", "rt_cast_rays_device", "rt_any_intersection", "rt_any_intersection_device",
 )
 
 _lib = None
@@ -81,6 +83,11 @@ def load():
     lib.rt_render_gather_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_params), C.c_void_p, C.c_void_p]
     lib.rt_comm_last_gather.restype = C.c_int
     lib.rt_comm_last_gather.argtypes = [C.c_void_p, C.POINTER(rt_gather_info)]
+    for name, out in (("rt_cast_rays", rt_ray_hits), ("rt_any_intersection", rt_ray_occlusion)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(rt_ray_batch), C.POINTER(out)]
+        getattr(lib, name + "_device").restype = C.c_int
+        getattr(lib, name + "_device").argtypes = [C.c_void_p, C.POINTER(rt_ray_batch), C.POINTER(out), C.c_void_p]
     _lib = lib
     return lib
 

@@ -204,6 +204,28 @@ struct RtDevParams {
   uint32_t hit_spawns;  // rt_launch_hit: 1 = rt_hit_spawn_kernel (the camera rays' children are appended where their hits are found)
 };
 
+// ---- ray queries (rt_cast_rays*, rt_any_intersection*: csrc/rt_query.h) -------------------------------------------------
+// Kernel argument of the two query kernels besides RtDevScene: the caller's batch (device pointers) and the output
+// planes (nullptr = not written).  A query reads only the scene's immutable arrays, never RtDevParams or a frame slot.
+struct RtQueryArgs {
+  const float* origin;        // [n][3]
+  const float* direction;     // [n][3], any length
+  const float* max_distance;  // [n] (any-hit only; nullptr = +inf)
+  int32_t* id;                // nearest hit
+  float* t;
+  float* point;               // [n][3]
+  float* normal;              // [n][3]
+  uint32_t* material;
+  uint8_t* has_intersection;  // any hit
+  uint8_t* occluded;
+  float* opacity;
+  float* filter;              // [n][3]
+  uint32_t n;
+  uint32_t cull;              // RT_FLAG_BACKFACE_CULLING given
+};
+int rt_launch_query_nearest(const RtDevScene& sc, const RtQueryArgs& q, void* stream);
+int rt_launch_query_any(const RtDevScene& sc, const RtQueryArgs& q, void* stream);
+
 #define RT_QUEUE_QUADS 4u   // float4 per ray record
 #define RT_SORT_TILE 4096u  // buckets per workgroup of the offset scan
 #define RT_SORT_BITS_DEFAULT 22u

@@ -2982,6 +2982,7 @@ __global__ __launch_bounds__(256) void rt_selftest_math_kernel(const float* in, 
 }
 
 #include "rt_phases.h"
+#include "rt_query.h"
 
 }  // namespace
 
@@ -3094,6 +3095,24 @@ int rt_launch_shade(const RtDevScene& sc, const RtDevParams& p, uint32_t n_wgs, 
 int rt_launch_hard(const RtDevScene& sc, const RtDevParams& p, uint32_t n_wgs, void* stream) {
   if (n_wgs == 0) n_wgs = 1;
   hipLaunchKernelGGL(rt_hard_kernel, dim3(n_wgs), dim3(256), 0, (hipStream_t)stream, sc, p);
+  return (int)hipGetLastError();
+}
+
+// ray queries (rt_query.h): grid-stride kernels, at most 32 workgroups per CU in flight
+static uint32_t query_wgs(uint32_t n) {
+  const uint32_t w = (uint32_t)(((uint64_t)n + 255u) / 256u);
+  return w < 8192u ? w : 8192u;
+}
+
+int rt_launch_query_nearest(const RtDevScene& sc, const RtQueryArgs& q, void* stream) {
+  if (q.n == 0) return 0;
+  hipLaunchKernelGGL(rt_query_nearest_kernel, dim3(query_wgs(q.n)), dim3(256), 0, (hipStream_t)stream, sc, q);
+  return (int)hipGetLastError();
+}
+
+int rt_launch_query_any(const RtDevScene& sc, const RtQueryArgs& q, void* stream) {
+  if (q.n == 0) return 0;
+  hipLaunchKernelGGL(rt_query_any_kernel, dim3(query_wgs(q.n)), dim3(256), 0, (hipStream_t)stream, sc, q);
   return (int)hipGetLastError();
 }
 

@@ -8,7 +8,7 @@ Reference: `trait Renderer<W,H,C>::render(&self, buffer: &ImageBuffer<W,H>, scen
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Any, Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -44,6 +44,24 @@ class ImageBuffer:
         return np.stack([(b >> 16) & 0xFF, (b >> 8) & 0xFF, b & 0xFF], axis=-1).astype(np.uint8)
 
 
+class RayHits(NamedTuple):
+    """Nearest hit per ray (`SurfaceInteraction`, surface_interaction.rs:13-30): canonical object id (-1 = miss), t
+    (+inf on a miss), point, normal (0 on a miss) and material row (0xFFFFFFFF on a miss; -1 in an int32 tensor)."""
+    id: Any
+    t: Any
+    point: Any
+    normal: Any
+    material: Any
+
+
+class IntersectionTest(NamedTuple):
+    """`IntersectionTest` (raytracer.rs:17-22) per segment.  color_filter is unspecified where completely_occluded."""
+    has_intersection: Any
+    completely_occluded: Any
+    combined_opacity: Any
+    color_filter: Any
+
+
 class DeviceScene:
     """Owns an `rt_scene*` (device copies + BVH)."""
 
@@ -72,6 +90,109 @@ class DeviceScene:
         info = _abi.rt_scene_info()
         _lib.check(_lib.load().rt_scene_memory_info(self.handle, C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in info._fields_}
+
+    def cast_rays(self, origins, directions, backface_culling: bool = False) -> "RayHits":
+        """`Raytracer::cast_ray` (raytracer.rs:162-220) for a batch of rays: the nearest hit of each.  origins /
+        directions: (n, 3) float32, numpy arrays (the host entry point; numpy results) or torch tensors on this scene's
+        device (the _device entry point on torch.cuda.current_stream(); tensor results, no synchronisation)."""
+        torch_in, n, o, d, _ = self._batch(origins, directions, None)
+        if torch_in:
+            import torch
+
+            dev = o.device
+            out = RayHits(torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+                          torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev),
+                          torch.empty(n, dtype=torch.int32, device=dev))
+            ptr = lambda a: a.data_ptr()  # noqa: E731
+        else:
+            out = RayHits(np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32),
+                          np.empty(n, np.uint32))
+            ptr = lambda a: a.ctypes.data  # noqa: E731
+        b = self._batch_struct(n, o, d, None, backface_culling, ptr)
+        h = _abi.rt_ray_hits(ptr(out.id), ptr(out.t), ptr(out.point), ptr(out.normal), ptr(out.material))
+        lib = _lib.load()
+        if torch_in:
+            _lib.check(lib.rt_cast_rays_device(self.handle, C.byref(b), C.byref(h), self._stream_of(o)))
+            # (the material rows travel as int32 in a tensor: torch has no uint32 arithmetic; a miss is -1 = 0xFFFFFFFF)
+        else:
+            _lib.check(lib.rt_cast_rays(self.handle, C.byref(b), C.byref(h)))
+        return out
+
+    def any_intersection(self, origins, directions, max_distance=None, backface_culling: bool = False) -> "IntersectionTest":
+        """`Raytracer::has_any_intersection` (raytracer.rs:24-106) for a batch of segments: every hit at t <= max_distance
+        (None = +inf) counts.  Same input kinds as cast_rays."""
+        torch_in, n, o, d, m = self._batch(origins, directions, max_distance)
+        if torch_in:
+            import torch
+
+            dev = o.device
+            out = IntersectionTest(torch.empty(n, dtype=torch.bool, device=dev), torch.empty(n, dtype=torch.bool, device=dev),
+                                   torch.empty(n, dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev))
+            ptr = lambda a: a.data_ptr()  # noqa: E731
+        else:
+            out = IntersectionTest(np.empty(n, np.bool_), np.empty(n, np.bool_), np.empty(n, np.float32), np.empty((n, 3), np.float32))
+            ptr = lambda a: a.ctypes.data  # noqa: E731
+        b = self._batch_struct(n, o, d, m, backface_culling, ptr)
+        oc = _abi.rt_ray_occlusion(ptr(out.has_intersection), ptr(out.completely_occluded), ptr(out.combined_opacity),
+                                   ptr(out.color_filter))
+        lib = _lib.load()
+        if torch_in:
+            _lib.check(lib.rt_any_intersection_device(self.handle, C.byref(b), C.byref(oc), self._stream_of(o)))
+        else:
+            _lib.check(lib.rt_any_intersection(self.handle, C.byref(b), C.byref(oc)))
+        return out
+
+    # (bool arrays and tensors hold one byte per element, 0 or 1: the uint8 planes of rt_ray_occlusion)
+
+    def _batch(self, origins, directions, max_distance):
+        """-> (torch?, n, origins, directions, max_distance) validated and contiguous."""
+        if isinstance(origins, np.ndarray) or isinstance(directions, np.ndarray):
+            o = np.ascontiguousarray(origins, np.float32)
+            d = np.ascontiguousarray(directions, np.float32)
+            if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+                raise ValueError(f"origins / directions must both be (n, 3), got {o.shape} and {d.shape}")
+            m = None
+            if max_distance is not None:
+                m = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (o.shape[0],)), np.float32)
+            return False, o.shape[0], o, d, m
+        import torch
+
+        if not (isinstance(origins, torch.Tensor) and isinstance(directions, torch.Tensor)):
+            raise ValueError("origins / directions must be numpy arrays or torch tensors")
+        want = torch.device("cuda", self.device)
+        ts = [("origins", origins), ("directions", directions)]
+        if max_distance is not None:
+            if not isinstance(max_distance, torch.Tensor):
+                raise ValueError("max_distance must be a tensor when the rays are tensors")
+            ts.append(("max_distance", max_distance))
+        for name, t in ts:
+            if t.dtype != torch.float32:
+                raise ValueError(f"{name} must be float32, got {t.dtype}")
+            if t.device != want:
+                raise ValueError(f"{name} must be on {want} (the scene's device), got {t.device}")
+        if origins.dim() != 2 or origins.shape[1] != 3 or directions.shape != origins.shape:
+            raise ValueError(f"origins / directions must both be (n, 3), got {tuple(origins.shape)} and {tuple(directions.shape)}")
+        n = origins.shape[0]
+        if max_distance is not None and tuple(max_distance.shape) != (n,):
+            raise ValueError(f"max_distance must be ({n},), got {tuple(max_distance.shape)}")
+        m = max_distance.contiguous() if max_distance is not None else None
+        return True, n, origins.contiguous(), directions.contiguous(), m
+
+    @staticmethod
+    def _batch_struct(n, o, d, m, backface_culling, ptr):
+        b = _abi.rt_ray_batch()
+        b.abi_version = _abi.RT_ABI_VERSION
+        b.n_rays = int(n)
+        b.origin, b.direction = ptr(o), ptr(d)
+        b.max_distance = ptr(m) if m is not None else None
+        b.flags = _abi.RT_FLAG_BACKFACE_CULLING if backface_culling else 0
+        return b
+
+    @staticmethod
+    def _stream_of(t):
+        import torch
+
+        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
     def close(self):
         if self._h is not None:

@@ -22,6 +22,13 @@
  *   rt_params         <- the compile-time feature/const table: src/lib.rs:30-92,
  *                        src/renderer/raytracer_renderer.rs:55-127
  *   rt_scene_destroy  <- Drop of Scene
+ *   rt_cast_rays      <- Raytracer::cast_ray, src/raytracing/raytracer.rs:162-220 (nearest hit as a
+ *                        SurfaceInteraction, src/raytracing/surface_interaction.rs:13-30), for a batch of
+ *                        HOST rays; blocks
+ *   rt_cast_rays_device          <- same, DEVICE arrays, enqueued on the caller's stream
+ *   rt_any_intersection          <- Raytracer::has_any_intersection, raytracer.rs:24-106 (IntersectionTest,
+ *                                   raytracer.rs:17-22), for a batch of HOST segments; blocks
+ *   rt_any_intersection_device   <- same, DEVICE arrays, enqueued on the caller's stream
  *   rt_last_error     <- (reference panics: `unwrap()/expect()`); here: error codes + message
  *
  * All arithmetic on the path is fp32.  Hit ids are canonical object indices: spheres first
@@ -382,6 +389,64 @@ typedef struct rt_progress rt_progress;
 int rt_render_begin(rt_scene* scene, const rt_params* params, uint32_t* argb, uint32_t band_rows, rt_progress** out);
 int rt_render_poll(rt_progress* progress, uint32_t* rows_done, int* finished);
 int rt_render_end(rt_progress* progress, rt_stats* stats);
+
+/* ---- ray queries on a scene already on the device ------------------------------------------------------------------------
+ *
+ * One ray per element; the reference's Ray::new_with_mask normalises the direction (ray.rs:52-57), and so do these calls:
+ * `direction` may have any length, `t` is the distance along the normalised direction.  Hit ids are canonical object
+ * indices as everywhere in this ABI (spheres, then triangles, each in insertion order).
+ *
+ * cast_ray's `start_refraction_index` and IS_ANTIALIASING_RAY do not take part in which object is hit (they only travel
+ * with the ray for the shading after it), so they have no counterpart here.
+ *
+ * Dead rays (deviation D2 of the render): a direction that normalises to NaN (zero length, a NaN or inf component) or a
+ * non-finite origin is a miss, and for rt_any_intersection* "has_intersection 0, completely_occluded 0, combined_opacity
+ * 1.0, color_filter (1, 1, 1)".  A NaN or negative max_distance admits no hit.
+ *
+ * Validation (RT_ERR_INVALID_ARG + rt_last_error, before any HIP call): NULL scene, batch or output struct; wrong
+ * abi_version; a flag bit other than RT_FLAG_BACKFACE_CULLING; NULL origin / direction with n_rays > 0; every output
+ * plane NULL.
+ *
+ * A query reads only the scene's immutable data: it may run on any stream while frames of the same scene render on others
+ * (rt_render_begin's included), and it leaves every render state alone. */
+typedef struct rt_ray_batch {
+  uint32_t abi_version;       /* RT_ABI_VERSION */
+  uint32_t n_rays;            /* 0 is a valid no-op */
+  const float* origin;        /* [n_rays][3] */
+  const float* direction;     /* [n_rays][3], any length (normalised as Ray::new_with_mask does, ray.rs:52-57) */
+  const float* max_distance;  /* [n_rays], rt_any_intersection* only (raytracer.rs:28); NULL = +inf */
+  uint32_t flags;             /* RT_FLAG_BACKFACE_CULLING or 0 (sphere.rs:137-151, triangle.rs:154-168) */
+} rt_ray_batch;
+
+/* nearest hit per ray (cast_ray).  Every member nullable: a NULL plane is not written. */
+typedef struct rt_ray_hits {
+  int32_t* id;        /* canonical object index of the nearest valid hit, -1 on a miss; on equal t the LATER object wins
+                         (the simd_le of raytracer.rs:194) */
+  float* t;           /* distance along the normalised direction; +inf on a miss */
+  float* point;       /* [n][3] fma(d, t, o) (Ray::at, ray.rs:60-66); 0 on a miss */
+  float* normal;      /* [n][3] sphere: normalize(p - centre); triangle: its stored face normal; 0 on a miss */
+  uint32_t* material; /* material row; 0xFFFFFFFF on a miss */
+} rt_ray_hits;
+
+/* visibility / transmittance per segment (has_any_intersection).  Every member nullable. */
+typedef struct rt_ray_occlusion {
+  uint8_t* has_intersection;    /* some valid hit at t <= max_distance (raytracer.rs:53-55) */
+  uint8_t* completely_occluded; /* one of those hits is on a material without opacity (raytracer.rs:75-80) */
+  float* combined_opacity;      /* 0 if occluded, else max(0, 1 - sum(1 - io)) over the hits, summed in 2^-28 fixed point
+                                   (independent of the order the hits are found in) */
+  float* color_filter;          /* [n][3] 1 - sum(absorption) over the hits (2^-24 fixed point) for a ray that is NOT
+                                   occluded.  UNSPECIFIED for an occluded ray: the reference stops at its first opaque hit in
+                                   object order, and nothing reads the filter after that */
+} rt_ray_occlusion;
+
+/* HOST arrays: the batch is copied through device memory allocated for the call (and freed); returns when the results
+ * are in host memory. */
+int rt_cast_rays(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_hits* hits);
+int rt_any_intersection(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_occlusion* out);
+/* DEVICE arrays on the scene's device: enqueued on `hip_stream` (a hipStream_t, NULL = default stream); allocates
+ * nothing and returns once the work is enqueued. */
+int rt_cast_rays_device(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_hits* hits, void* hip_stream);
+int rt_any_intersection_device(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_occlusion* out, void* hip_stream);
 
 /* thread-local message for the last non-RT_OK return on this thread */
 const char* rt_last_error(void);
