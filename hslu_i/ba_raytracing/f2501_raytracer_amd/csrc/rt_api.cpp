@@ -1327,7 +1327,9 @@ static int render_frame_impl(rt_scene* s, RtDevParams& P, hipStream_t stream, ui
   if (!f.secondary && !f.split && !f.defer) {  // one launch of the fused primary kernel
     P.acc = nullptr, P.q_out = nullptr;
     P.batch_first_wg = 0, P.batch_stride = 1, P.batch_group_log2 = 0;
-    return launched(rt_launch_primary(s->dev, P, f.total_wgs, stream), stream, "kernel launch", "rt_primary_kernel: workgroups", f.total_wgs);
+    char label[64];  // (names the kernel that runs: rt_primary_kernel or the one compiled for this configuration)
+    snprintf(label, sizeof(label), "%s: workgroups", rt_primary_variant_name(rt_primary_variant_used(s->dev, P)));
+    return launched(rt_launch_primary(s->dev, P, f.total_wgs, stream), stream, "kernel launch", label, f.total_wgs);
   }
   if (f.total_wgs == 0) return RT_OK;  // this rank owns no tile inside the window (more ranks than tiles): nothing to trace, nothing to resolve
   RC_TRY(plan_schedule(f));

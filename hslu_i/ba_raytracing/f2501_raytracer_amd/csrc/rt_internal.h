@@ -237,10 +237,47 @@ __host__ __device__
 #endif
 static inline bool rt_primary_wave_local(uint32_t n_thr) { return n_thr <= 64u && (64u / n_thr) * n_thr >= 60u; }
 
+// Which kernel renders a frame without secondary rays (rt_launch_primary, p.acc == nullptr).  rt_primary_kernel decides its
+// configuration at run time; the rt_primary_soft* kernels are compiled for one (CfgSoft in rt_kernels.hip) and may only
+// run a frame for which EVERY constant they were compiled with holds -- this function is that rule, and the only copy of it.
+enum RtPrimaryVariant {
+  RT_PRIMARY_GENERIC = 0,    // rt_primary_kernel
+  RT_PRIMARY_SOFT10,         // rt_primary_soft10_kernel: receiver flags and per-cell candidate lists
+  RT_PRIMARY_SOFT19,
+  RT_PRIMARY_SOFT28,
+  RT_PRIMARY_SOFT10_FLAGS,   // rt_primary_soft10_flags_kernel: receiver flags only (the default scene budget)
+  RT_PRIMARY_SOFT19_FLAGS,
+  RT_PRIMARY_SOFT28_FLAGS,
+  RT_PRIMARY_VARIANTS
+};
+static inline int rt_primary_variant(const RtDevScene& sc, const RtDevParams& p, bool force_generic) {
+  if (force_generic) return RT_PRIMARY_GENERIC;
+  if (p.flags & RT_FLAG_BACKFACE_CULLING) return RT_PRIMARY_GENERIC;
+  // BVH: one shared candidate walk per (wavefront, light)
+  if (p.traversal != RT_TRAVERSAL_BVH || sc.n_triangles == 0u || !(p.cloud_delta > 0.0f) || p.cand_cap == 0u) return RT_PRIMARY_GENERIC;
+  if (p.n_cloud_sets == 0u || (p.n_cloud_sets & (p.n_cloud_sets - 1u)) != 0u) return RT_PRIMARY_GENERIC;  // POW2_SETS
+  if (sc.n_spheres >= 32u) return RT_PRIMARY_GENERIC;                                                       // FEW_SPHERES
+  if (!p.recv_flags) return RT_PRIMARY_GENERIC;  // TABLES: flags, or flags and lists (lists never come without flags)
+  const bool lists = p.cell_lists != nullptr;
+  switch (p.light_mult) {
+    case 10u: return lists ? RT_PRIMARY_SOFT10 : RT_PRIMARY_SOFT10_FLAGS;
+    case 19u: return lists ? RT_PRIMARY_SOFT19 : RT_PRIMARY_SOFT19_FLAGS;
+    case 28u: return lists ? RT_PRIMARY_SOFT28 : RT_PRIMARY_SOFT28_FLAGS;
+    default: return RT_PRIMARY_GENERIC;
+  }
+}
+static inline const char* rt_primary_variant_name(int v) {
+  static const char* const names[RT_PRIMARY_VARIANTS] = {"rt_primary_kernel", "rt_primary_soft10_kernel", "rt_primary_soft19_kernel",
+                                                         "rt_primary_soft28_kernel", "rt_primary_soft10_flags_kernel",
+                                                         "rt_primary_soft19_flags_kernel", "rt_primary_soft28_flags_kernel"};
+  return v >= 0 && v < RT_PRIMARY_VARIANTS ? names[v] : "";
+}
+
 // kernel launchers (rt_kernels.hip); return hipError_t as int
 uint32_t rt_primary_pixels_per_wg(const RtDevParams& p);
 uint32_t rt_primary_total_wgs(const RtDevParams& p);
 int rt_launch_primary(const RtDevScene& sc, const RtDevParams& p, uint32_t n_wgs, void* stream);
+int rt_primary_variant_used(const RtDevScene& sc, const RtDevParams& p);  // RtPrimaryVariant rt_launch_primary picks when p.acc == nullptr
 // secondary kernels: n_wgs = the host's guess of the grid (every kernel walks its device-side count with a grid-stride loop)
 int rt_launch_trace(const RtDevScene& sc, const RtDevParams& p, uint32_t n_wgs, void* stream);
 int rt_launch_sort(const RtDevParams& p, uint32_t n_wgs_place, void* stream);  // histogram -> offsets -> sh_idx (rt_sort.hip)

@@ -41,6 +41,8 @@
 // v_rcp/v_rsq (1 ulp) and exp2/log2-based tanh/pow.
 #include <hip/hip_runtime.h>
 
+#include <stdlib.h>
+
 #include <type_traits>
 
 #include "rt_internal.h"
@@ -580,9 +582,36 @@ struct WaveCtx {
 };
 
 // ------------------------------------------------------------------------------------------------
+// Compile-time configuration of process_ray and its callees.  What a frame's light loop branches on is the same for every
+// lane, wavefront and frame of a scene: the sample count, the traversal, which receiver tables exist, the shape of the
+// cloud table, the sphere count.  A kernel compiled for one such configuration (CfgSoft, rt_primary_soft*_kernel) carries
+// neither the tests, nor the kernel-argument reads behind them, nor the paths not taken; CfgGeneric decides everything at
+// run time, as every other kernel does.  rt_primary_variant (rt_internal.h) is the host's side of this: it sends a frame
+// to a specialised kernel only when every constant below holds for it.
+// ------------------------------------------------------------------------------------------------
+enum { CFG_TABLES_RUNTIME = -1, CFG_TABLES_FLAGS = 1, CFG_TABLES_LISTS = 2 };
+struct CfgGeneric {
+  static constexpr uint32_t N = 0u;          // samples per light; 0: P.light_mult
+  static constexpr bool BVH = false;         // true: P.traversal == RT_TRAVERSAL_BVH, triangles exist, cloud_delta > 0, cand_cap != 0
+  static constexpr int TABLES = CFG_TABLES_RUNTIME;  // FLAGS: recv_flags without cell_lists; LISTS: both; RUNTIME: as the pointers say
+  static constexpr bool POW2_SETS = false;   // true: n_cloud_sets is a power of two
+  static constexpr bool FEW_SPHERES = false; // true: n_spheres < 32
+};
+template <uint32_t N_, int TABLES_>
+struct CfgSoft {
+  static constexpr uint32_t N = N_;
+  static constexpr bool BVH = true;
+  static constexpr int TABLES = TABLES_;
+  static constexpr bool POW2_SETS = true;
+  static constexpr bool FEW_SPHERES = true;
+};
+// (The tests below are written where they stand as `C::X || run-time test` / `!C::X && run-time test` / `C::X ? constant : run-time
+// value`: the front end folds the constant side away, so CfgGeneric compiles to exactly what the run-time test alone compiles to.)
+
+// ------------------------------------------------------------------------------------------------
 // nearest hit: spheres linearly (wave-uniform loop), triangles through the BVH or linearly
 // ------------------------------------------------------------------------------------------------
-template <bool CULL>
+template <bool CULL, class C = CfgGeneric>
 __device__ __forceinline__ Hit nearest_hit(const RtDevScene& sc, const RtDevParams& P, WaveCtx& W,
                                            bool alive, V3 o, V3 d) {
   Hit best;
@@ -596,7 +625,7 @@ __device__ __forceinline__ Hit nearest_hit(const RtDevScene& sc, const RtDevPara
   // r + so + (|c - o_0| + so + r) * sd of ray 0.  One test for all spheres; the survivors are tested per lane.
   uint32_t pre = 0xFFFFFFFFu;
   if (sc.n_spheres > 2u && grp) {
-    const uint32_t ns = sc.n_spheres < 32u ? sc.n_spheres : 32u;
+    const uint32_t ns = C::FEW_SPHERES ? sc.n_spheres : (sc.n_spheres < 32u ? sc.n_spheres : 32u);
     const int fl = __ffsll((long long)grp) - 1;
     auto first = [&](float v) { return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), fl)); };
     const V3 o0 = mk(first(o.x), first(o.y), first(o.z)), d0 = mk(first(d.x), first(d.y), first(d.z));
@@ -632,10 +661,11 @@ __device__ __forceinline__ Hit nearest_hit(const RtDevScene& sc, const RtDevPara
     }
   };
   // in index order (ties go to the later object, raytracer.rs:193-213)
-  for (uint32_t bits = pre & (sc.n_spheres >= 32u ? 0xFFFFFFFFu : ((1u << sc.n_spheres) - 1u)); bits; bits &= bits - 1u)
+  for (uint32_t bits = pre & ((!C::FEW_SPHERES && sc.n_spheres >= 32u) ? 0xFFFFFFFFu : ((1u << sc.n_spheres) - 1u)); bits; bits &= bits - 1u)
     test_sphere((uint32_t)__builtin_ctz(bits));
-  for (uint32_t i = 32u; i < sc.n_spheres; i++) test_sphere(i);
-  if (sc.n_triangles == 0) return best;
+  if constexpr (!C::FEW_SPHERES)
+    for (uint32_t i = 32u; i < sc.n_spheres; i++) test_sphere(i);
+  if (!C::BVH && sc.n_triangles == 0) return best;
   const int tri_base = (int)sc.n_spheres;
 
   auto test_tri = [&](uint32_t slot, lanemask lanes) {
@@ -660,7 +690,7 @@ __device__ __forceinline__ Hit nearest_hit(const RtDevScene& sc, const RtDevPara
     }
   };
 
-  if (P.traversal == RT_TRAVERSAL_LINEAR) {
+  if (!C::BVH && P.traversal == RT_TRAVERSAL_LINEAR) {
     // the literal scan visits every triangle once: skip the extra references of split triangles
     for (uint32_t s = 0; s < sc.n_slots; s++)
       if (!(sload<uint32_t>(sc, sc.off_tri_id + s * 4u) & RT_TRI_DUPLICATE)) test_tri(s, grp);
@@ -809,7 +839,7 @@ enum { COLLECT_OWN = 0, COLLECT_FLAGS = 1 };
 // MODE: COLLECT_OWN -- a wavefront's own collection at render time; COLLECT_FLAGS -- fat beams of receiver cells (fb): no
 // list and no umbra, the result is L.umbra = lanes some triangle survives for, L.spheres = lanes (low / high word of the
 // mask in count / spheres) some sphere is near.
-template <bool CULL, int MODE = COLLECT_OWN>
+template <bool CULL, int MODE = COLLECT_OWN, class C = CfgGeneric>
 __device__ __forceinline__ CandList collect_light_candidates(const RtDevScene& sc, WaveCtx& W, bool alive, V3 p, V3 c,
                                                               const RtDevParams& P, V3 p_first, float p_spread, uint32_t cand_cap,
                                                               const FatBeam* fb = nullptr, bool walk_tris = true,
@@ -985,7 +1015,7 @@ __device__ __forceinline__ CandList collect_light_candidates(const RtDevScene& s
   } else {
     uint32_t mask = 0;
     const float inv_len2 = __builtin_amdgcn_rcpf(fmaxf(dot(dseg, dseg), 1e-30f));
-    const uint32_t ns = sc.n_spheres < 32u ? sc.n_spheres : 32u;
+    const uint32_t ns = C::FEW_SPHERES ? sc.n_spheres : (sc.n_spheres < 32u ? sc.n_spheres : 32u);
     // Pre-selection across lanes: lane i looks at sphere i and asks whether its centre is within reach of the
     // segment of the wavefront's first hit point -- with the wavefront's spread of hit points (p_spread) added to the
     // reach, since segment l stays within |p_l - p_first| of it.  One test for all spheres instead of one per
@@ -1022,7 +1052,7 @@ __device__ __forceinline__ CandList collect_light_candidates(const RtDevScene& s
       const bool leaving = (amin > 1e-6f * w1) && (cc_lo > 0.0f);
       if (wave_ballot(alive && near && !leaving)) mask |= 1u << i;
     }
-    L.spheres = mask | (sc.n_spheres > 32u ? 0xFFFFFFFFu : 0u);
+    L.spheres = mask | ((!C::FEW_SPHERES && sc.n_spheres > 32u) ? 0xFFFFFFFFu : 0u);
   }
   if (!walk_tris) return L;  // (wave-uniform: every lane sits in a receiver cell no triangle can shadow for this light)
   // direction octant of the wavefront (sign of inv = sign of dseg, -0 included)
@@ -1134,7 +1164,7 @@ __device__ __forceinline__ CandList collect_light_candidates(const RtDevScene& s
 }
 
 // LIST: the caller has checked (once per light, not once per sample) that a shared candidate list exists
-template <bool CULL, bool LIST>
+template <bool CULL, bool LIST, class C = CfgGeneric>
 __device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevParams& P, WaveCtx& W,
                                              lanemask grp, V3 o, V3 d_raw, float tmax, const CandList& cand) {
   Shadow S;
@@ -1163,10 +1193,11 @@ __device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevPa
     }
   };
   // spheres 0..31 through the bits of the (wavefront, light) mask, in index order; any further ones unconditionally
-  for (uint32_t bits = cand.spheres & (sc.n_spheres >= 32u ? 0xFFFFFFFFu : ((1u << sc.n_spheres) - 1u)); bits; bits &= bits - 1u)
+  for (uint32_t bits = cand.spheres & ((!C::FEW_SPHERES && sc.n_spheres >= 32u) ? 0xFFFFFFFFu : ((1u << sc.n_spheres) - 1u)); bits; bits &= bits - 1u)
     test_sphere((uint32_t)__builtin_ctz(bits));
-  for (uint32_t i = 32u; i < sc.n_spheres; i++) test_sphere(i);
-  if (!LIST && sc.n_triangles == 0) return S;
+  if constexpr (!C::FEW_SPHERES)
+    for (uint32_t i = 32u; i < sc.n_spheres; i++) test_sphere(i);
+  if (!LIST && !C::BVH && sc.n_triangles == 0) return S;
 #if RT_PROFILE
   RT_OPAQUE(S.dec);
 #endif
@@ -1190,7 +1221,7 @@ __device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevPa
     }
   };
 
-  if (!LIST && P.traversal == RT_TRAVERSAL_LINEAR) {
+  if (!LIST && !C::BVH && P.traversal == RT_TRAVERSAL_LINEAR) {
     for (uint32_t s = 0; s < sc.n_slots; s++)
       if (!(sload<uint32_t>(sc, sc.off_tri_id + s * 4u) & RT_TRI_DUPLICATE)) test_tri(s, grp);
     return S;
@@ -1512,7 +1543,7 @@ __device__ __forceinline__ long long* stash_fix(float* stash) { return (long lon
 // sc / P MUST be the calling kernel's own, unmodified kernel arguments (its parameters 0 and 1): the light loop, the sample
 // loop and the part after the light loop read them again from the kernarg segment (kernarg_scene / kernarg_params: the
 // shadowing `sc` / `P` inside the loops, `sc1` / `P1` after them), so a changed copy passed in would not be seen there.
-template <bool CULL, bool PRE, bool STREAM>
+template <bool CULL, bool PRE, bool STREAM, class C = CfgGeneric>
 __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevParams& P, Wave& wv, bool have,
                                               const RayIn& r, float* stash /* LDS: [RT_STASH_FIELDS][256] */,
                                               Hit pre) {
@@ -1525,7 +1556,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
   out.mult = 1;
   WaveCtx& W = wv.ctx;
   const V3 epsv = mk(P.eps_distance, P.eps_distance, P.eps_distance);
-  const uint32_t N = P.light_mult < 1u ? 1u : P.light_mult;
+  const uint32_t N = C::N != 0u ? C::N : (P.light_mult < 1u ? 1u : P.light_mult);
   const bool stream = STREAM && P.q_out != nullptr;
   if (STREAM) {
     long long* fx = stash_fix(stash) + threadIdx.x;
@@ -1546,7 +1577,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     WSTAT(wv.cnt_pass += 1);
     WSTAT(wv.cnt_lanes += (uint32_t)__popcll(bal));
     const unsigned long long t_n = PROF_T();
-    h = nearest_hit<CULL>(sc, P, W, alive, r.o, d);
+    h = nearest_hit<CULL, C>(sc, P, W, alive, r.o, d);
 #if RT_PROFILE
     RT_OPAQUE(h.t);
 #endif
@@ -1590,7 +1621,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
   if (N > 1) {
     // receiver flags of the cell the hit point lies in (bit l: no triangle can shadow it for light l, bit 8 + l: no sphere)
     uint32_t rflags = 0u, cell = RT_NO_CELL;
-    if (P.recv_flags && hit && h.id >= (int)sc.n_spheres) {
+    if ((C::TABLES != CFG_TABLES_RUNTIME || P.recv_flags) && hit && h.id >= (int)sc.n_spheres) {
       const uint32_t ro = sc.off_recv + (uint32_t)(h.id - (int)sc.n_spheres) * 48u;
       const float4 ru = vload<float4>(sc, ro), rv = vload<float4>(sc, ro + 16u);
       const uint2 rr = vload<uint2>(sc, ro + 32u);  // {R, first cell}
@@ -1601,7 +1632,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       // (cells beyond the hypotenuse carry no flags; the cells are computed 5 % larger than they are, which covers the
       // rounding of u and v)
       if (rr.x != 0u && ci + cj < rr.x) cell = rr.y + ci + rr.x * cj, rflags = P.recv_flags[cell];
-    } else if (P.recv_flags && hit && h.id >= 0) {
+    } else if ((C::TABLES != CFG_TABLES_RUNTIME || P.recv_flags) && hit && h.id >= 0) {
       // a sphere: the cell of the direction centre -> p in the sphere's cube map (face = largest component)
       const uint2 sr = vload<uint2>(sc, sc.off_srecv + (uint32_t)h.id * 8u);  // {Rs, first cell}
       const float4 sp = vload<float4>(sc, sc.off_spheres + (uint32_t)h.id * 16u);
@@ -1656,7 +1687,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       const uint32_t pixel = __float_as_uint(stash[9u * 256u + tix]);
       const uint32_t hsh = rt_cloud_hash(P.cloud_seed, pixel, l);
       // (a power-of-two table -- the default 1024 -- needs no integer division: ~25 vector instructions per light)
-      const uint32_t set = (P.n_cloud_sets & (P.n_cloud_sets - 1u)) == 0u ? (hsh & (P.n_cloud_sets - 1u)) : (hsh % P.n_cloud_sets);
+      const uint32_t set = (C::POW2_SETS || (P.n_cloud_sets & (P.n_cloud_sets - 1u)) == 0u) ? (hsh & (P.n_cloud_sets - 1u)) : (hsh % P.n_cloud_sets);
       cs = P.cloud_sets + (size_t)set * N;
       lI = (1.0f / (float)N) * L0.w;
     }
@@ -1688,11 +1719,11 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     if ((RT_SKIP & 4) && N > 1) {  // removal ablation: no candidate collection either
       cand.count = 0;
       cand.spheres = 0;
-    } else if (N > 1 && P.cloud_delta > 0.0f && P.traversal == RT_TRAVERSAL_BVH && sc.n_triangles) {
+    } else if (N > 1 && (C::BVH || P.cloud_delta > 0.0f) && (C::BVH || P.traversal == RT_TRAVERSAL_BVH) && (C::BVH || sc.n_triangles)) {
       V3 centre = mk(L0.x + P.cloud_centre[0], L0.y + P.cloud_centre[1], L0.z + P.cloud_centre[2]);
       const unsigned long long t_c = PROF_T();
       bool walk_tris = true, test_spheres = true;
-      if (!CULL && P.recv_flags) {
+      if (!CULL && (C::TABLES != CFG_TABLES_RUNTIME || P.recv_flags)) {
         uint32_t tix = threadIdx.x;
         RT_OPAQUE(tix);
         const uint32_t rf = __float_as_uint(stash[10u * 256u + tix]) >> l;
@@ -1703,7 +1734,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       // their union replaces the BVH walk (typically one to three distinct cells per wavefront: lanes of one cell share a list).
       uint32_t pre_reg = 0, pre_count = 0;  // lane i of pre_reg = i-th slot of the union
       bool have_pre = false;
-      if (!CULL && P.cell_lists && walk_tris) {
+      if (!CULL && (C::TABLES == CFG_TABLES_LISTS || (C::TABLES == CFG_TABLES_RUNTIME && P.cell_lists)) && walk_tris) {
         uint32_t tix = threadIdx.x;
         RT_OPAQUE(tix);
         const uint32_t cidx = __float_as_uint(stash[RT_STASH_CELL * 256u + tix]);
@@ -1738,8 +1769,8 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       prof_walked = (walk_tris && !have_pre) ? 1u : 0u, prof_listed = have_pre ? 1u : 0u, prof_pre = have_pre ? pre_count : 0u;
 #endif
       if (test_spheres) {
-        cand = collect_light_candidates<CULL>(sc, W, use, sf.p, centre, P, p_first, p_spread, P.cand_cap, nullptr, walk_tris,
-                                              have_pre, pre_reg, pre_count);
+        cand = collect_light_candidates<CULL, COLLECT_OWN, C>(sc, W, use, sf.p, centre, P, p_first, p_spread, P.cand_cap, nullptr, walk_tris,
+                                                              have_pre, pre_reg, pre_count);
       } else {
         cand.count = 0;  // every lane's cell is clear of triangles and spheres for this light: nothing to test
         cand.spheres = 0;
@@ -1899,6 +1930,9 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       // sample) are not needed; what is left of ld and |ltp| only scales the colour
       Shadow S;
       shadow_init(S);
+      // (not unrolled: with a constant N hipcc would unroll all ten samples -- 43 spilled VGPRs; by two it measured no gain
+      // and spilled 70 VGPRs with N = 19, profiles/r06_specialised_primary.md)
+#pragma unroll 1
       for (uint32_t j = 0; j < N; j++) {
         const V3 ltp = light_position(j) - sf.p;
         WSTAT(W.s_passes++);
@@ -1917,7 +1951,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
           const V3 ld = ltp * exact_rcp(mag(ltp));  // normalize(ltp): the shadow ray's geometry is exact
           const V3 so = sf.p + ld * epsv;
           const float tmax = mag(lp - so);
-          const Shadow S = shadow_ray<CULL, decltype(list_tag)::value>(sc, P, W, use_m, so, ld, tmax, cand);
+          const Shadow S = shadow_ray<CULL, decltype(list_tag)::value, C>(sc, P, W, use_m, so, ld, tmax, cand);
           const lanemask reach_m = use_m & ~S.occ;
 #if RT_PROFILE == 3
           set_occ += (uint32_t)__popcll(use_m & S.occ);
@@ -1929,7 +1963,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
         }
       };
       // (decided once per light: per-sample uniform branches cost issue slots and mask registers)
-      if (cand.count != RT_CAND_OVERFLOW && P.traversal != RT_TRAVERSAL_LINEAR && sc.n_triangles)
+      if (cand.count != RT_CAND_OVERFLOW && (C::BVH || P.traversal != RT_TRAVERSAL_LINEAR) && (C::BVH || sc.n_triangles))
         traced_samples(std::true_type{});
       else
         traced_samples(std::false_type{});
@@ -2119,7 +2153,7 @@ __device__ __forceinline__ void acc_add_fixed(const RtDevParams& P, uint32_t pix
 // the shipped kernels carry none of it.
 // PRE (merged levels): the camera rays' hits were found -- and their children appended -- by rt_hit_spawn_kernel; this launch only shades
 // them, concurrently with the trace launches of the levels below on another stream.
-template <bool CULL, bool STREAM, bool COST = false, bool PRE = false>
+template <bool CULL, bool STREAM, bool COST = false, bool PRE = false, class C = CfgGeneric>
 // sc / P: the kernel's own kernel arguments, unmodified (process_ray; after process_ray this reads P1 = kernarg_params())
 __device__ __forceinline__ void primary_body(const RtDevScene& sc, const RtDevParams& P, float4* lds_rgbh,
                                              float* lds_stash, unsigned long long* lds_cnt) {
@@ -2202,7 +2236,7 @@ __device__ __forceinline__ void primary_body(const RtDevScene& sc, const RtDevPa
     none.t = __uint_as_float(hr.x);
     none.id = (int)hr.y;
   }
-  RayOut out = process_ray<CULL, PRE, STREAM>(sc, P, wv, pix_on, r, lds_stash, none);
+  RayOut out = process_ray<CULL, PRE, STREAM, C>(sc, P, wv, pix_on, r, lds_stash, none);
   // the kernel arguments again, from the kernarg segment: nothing of them is held through process_ray
   const RtDevParams& P1 = kernarg_params();
 
@@ -2326,6 +2360,25 @@ __global__ __launch_bounds__(256, RT_MIN_WAVES) void rt_primary_kernel(RtDevScen
   else
     primary_body<false, false>(sc, P, lds_rgbh, lds_stash, lds_cnt);
 }
+
+// The same frame compiled for its configuration (CfgSoft): soft shadows with 10, 19 or 28 samples per light, no backface
+// culling, BVH traversal, a power-of-two cloud table, fewer than 32 spheres, and the receiver tables of the scene budget --
+// flags and per-cell lists (`_kernel`), or flags alone (`_flags_kernel`, the default budget).  One instantiation per kernel.
+// rt_primary_variant (rt_internal.h) decides which frame may run one; every other frame runs rt_primary_kernel.
+#define RT_PRIMARY_SOFT_KERNEL(name, n, tables)                                                              \
+  __global__ __launch_bounds__(256, RT_MIN_WAVES) void name(RtDevScene sc, RtDevParams P) {                  \
+    __shared__ float4 lds_rgbh[256];                                                                         \
+    __shared__ __attribute__((aligned(16))) float lds_stash[RT_STASH_FIX * 256];                             \
+    __shared__ unsigned long long lds_cnt[20];                                                               \
+    primary_body<false, false, false, false, CfgSoft<n, tables>>(sc, P, lds_rgbh, lds_stash, lds_cnt);       \
+  }
+RT_PRIMARY_SOFT_KERNEL(rt_primary_soft10_kernel, 10u, CFG_TABLES_LISTS)
+RT_PRIMARY_SOFT_KERNEL(rt_primary_soft19_kernel, 19u, CFG_TABLES_LISTS)
+RT_PRIMARY_SOFT_KERNEL(rt_primary_soft28_kernel, 28u, CFG_TABLES_LISTS)
+RT_PRIMARY_SOFT_KERNEL(rt_primary_soft10_flags_kernel, 10u, CFG_TABLES_FLAGS)
+RT_PRIMARY_SOFT_KERNEL(rt_primary_soft19_flags_kernel, 19u, CFG_TABLES_FLAGS)
+RT_PRIMARY_SOFT_KERNEL(rt_primary_soft28_flags_kernel, 28u, CFG_TABLES_FLAGS)
+#undef RT_PRIMARY_SOFT_KERNEL
 
 // the same with secondary rays (children queued, accumulator, hard pairs): launched when reflections / refractions are on
 __global__ __launch_bounds__(256, RT_MIN_WAVES) void rt_primary_stream_kernel(RtDevScene sc, RtDevParams P) {
@@ -3060,6 +3113,14 @@ uint32_t rt_primary_total_wgs(const RtDevParams& p) {
   return (uint32_t)(((uint64_t)p.n_sup * 256u + ppw - 1u) / ppw);
 }
 
+// the primary kernel of a frame without secondary rays: rt_primary_variant, unless RT_PRIMARY_GENERIC=1 in the environment
+// (read once per process) sends every frame to rt_primary_kernel (A/B timing, equality tests)
+int rt_primary_variant_used(const RtDevScene& sc, const RtDevParams& p) {
+  static const char* const v = getenv("RT_PRIMARY_GENERIC");
+  static const bool force_generic = v && *v && *v != '0';
+  return rt_primary_variant(sc, p, force_generic);
+}
+
 int rt_launch_primary(const RtDevScene& sc, const RtDevParams& p, uint32_t n_wgs, void* stream) {
   if (n_wgs == 0) return 0;  // nothing owned inside the window
 #if RT_COST_KERNEL
@@ -3072,8 +3133,19 @@ int rt_launch_primary(const RtDevScene& sc, const RtDevParams& p, uint32_t n_wgs
     hipLaunchKernelGGL(rt_primary_pre_kernel, dim3(n_wgs), dim3(256), 0, (hipStream_t)stream, sc, p);
   else if (p.acc)
     hipLaunchKernelGGL(rt_primary_stream_kernel, dim3(n_wgs), dim3(256), 0, (hipStream_t)stream, sc, p);
-  else
-    hipLaunchKernelGGL(rt_primary_kernel, dim3(n_wgs), dim3(256), 0, (hipStream_t)stream, sc, p);
+  else {
+    void (*kernel)(RtDevScene, RtDevParams) = rt_primary_kernel;
+    switch (rt_primary_variant_used(sc, p)) {
+      case RT_PRIMARY_SOFT10: kernel = rt_primary_soft10_kernel; break;
+      case RT_PRIMARY_SOFT19: kernel = rt_primary_soft19_kernel; break;
+      case RT_PRIMARY_SOFT28: kernel = rt_primary_soft28_kernel; break;
+      case RT_PRIMARY_SOFT10_FLAGS: kernel = rt_primary_soft10_flags_kernel; break;
+      case RT_PRIMARY_SOFT19_FLAGS: kernel = rt_primary_soft19_flags_kernel; break;
+      case RT_PRIMARY_SOFT28_FLAGS: kernel = rt_primary_soft28_flags_kernel; break;
+      default: break;
+    }
+    hipLaunchKernelGGL(kernel, dim3(n_wgs), dim3(256), 0, (hipStream_t)stream, sc, p);
+  }
   return (int)hipGetLastError();
 }
 

@@ -14,7 +14,10 @@ import shutil
 import sys
 
 tag, wl = sys.argv[1], (sys.argv[2] if len(sys.argv) > 2 else "c3")
-kname = {"c1": "rt_primary_kernel", "c2": "rt_primary_kernel", "c3": "rt_primary_kernel"}.get(wl, "rt_shade_kernel")
+# configs 1-3 are one launch of a primary kernel per frame: rt_primary_kernel, or the rt_primary_soft* kernel compiled for the
+# frame's configuration (rt_primary_variant) -- whichever of them the trace shows (the one with the most GPU time)
+PRIMARY = ("rt_primary_kernel", "rt_primary_soft")
+kname = {"c1": None, "c2": None, "c3": None}.get(wl, "rt_shade_kernel")
 src = os.path.join("gpurun_out", f"prof_{tag}_{wl}")
 os.makedirs("profiles", exist_ok=True)
 build_id = open(os.path.join(src, "build_id.txt")).read().split()[0]
@@ -23,7 +26,11 @@ shutil.copy(ks, os.path.join("profiles", f"{tag}_{wl}_kernel_stats.csv"))
 rows = list(csv.DictReader(open(ks)))
 nf = os.path.join(src, "n_frames.txt")
 n_frames = int(open(nf).read().split()[0]) if os.path.exists(nf) else 4  # frames per profiled run (tools/profile.sh)
-kern = [r for r in rows if kname in r["Name"]][0]
+if kname is None:
+    kern = max((r for r in rows if any(p in r["Name"] for p in PRIMARY)), key=lambda r: float(r["TotalDurationNs"]))
+    kname = kern["Name"].split("::")[-1].split("(")[0]
+else:
+    kern = [r for r in rows if kname in r["Name"]][0]
 calls = int(kern["Calls"])
 per_frame = calls / n_frames
 avg_ms = float(kern["AverageNs"]) / 1e6
