@@ -1,15 +1,17 @@
-// rt_api.cpp -- the C ABI of include/rt_hip.h over the HIP runtime.
+// rt_api.cpp -- the C ABI of include/rt_hip.h over the HIP runtime: everything on the host that is stateful.
 //
 // rt_scene owns the device copies of the flattened Scene (reference src/scene/scene.rs:24-27), the
 // BVH, and reusable device workspaces (parameter tables, counters, ray queues, accumulator), so a
 // render call performs no allocation when its shape repeats (graph-capture friendly: rt_render_device
 // only enqueues async work on the caller's stream).
+// What is in this file: scene creation as an upload of what rt_pack_scene laid out (rt_scene_pack.cpp), prepare() -- when
+// a frame's parameter tables are rebuilt and when they may be overwritten; their contents come from rt_tables.cpp -- and
+// the frame scheduler.  Byte layouts and table arithmetic are NOT here: they make no HIP call and are tested on the CPU.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,22 +21,9 @@
 #include "rt_host.h"
 
 static void trace_point(hipStream_t stream, const char* what, uint32_t a = 0, uint32_t b = 0, uint32_t c = 0);  // RT_TRACE_LAUNCHES
-
-thread_local std::string g_err;
-
-int rt_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
+#define RC_TRY(expr) do { const int rc_ = (expr); if (rc_ != RT_OK) return rc_; } while (0)
 
 extern "C" {
-
-const char* rt_last_error(void) { return g_err.c_str(); }
 
 #ifndef RT_BUILD_ID
 #define RT_BUILD_ID "unknown"
@@ -96,23 +85,22 @@ void rt_scene_destroy(rt_scene* s) {
   delete s;
 }
 
+static int upload(DevBuf& b, const void* src, size_t bytes) {
+  int rc = b.ensure(bytes);
+  if (rc != RT_OK) return rc;
+  if (bytes) {
+    hipError_t e = hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(RT_ERR_HIP, "hipMemcpy H2D failed: %s", hipGetErrorString(e));
+  }
+  return RT_OK;
+}
+
+// what the scene looks like in device memory is decided by rt_pack_scene (rt_scene_pack.cpp); this uploads it
 int rt_scene_create(const rt_scene_desc* d, int device, rt_scene** out) {
   if (!d || !out) return fail(RT_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
-  if (d->abi_version != RT_ABI_VERSION)
-    return fail(RT_ERR_INVALID_ARG, "rt_scene_desc.abi_version %u != %u", d->abi_version, RT_ABI_VERSION);
-  if (d->n_spheres && (!d->sphere_center || !d->sphere_r_sq || !d->sphere_material))
-    return fail(RT_ERR_INVALID_ARG, "sphere arrays missing");
-  if (d->n_triangles && (!d->tri_v1 || !d->tri_e1 || !d->tri_e2 || !d->tri_normal || !d->tri_material))
-    return fail(RT_ERR_INVALID_ARG, "triangle arrays missing");
-  if ((d->n_spheres || d->n_triangles) && (!d->n_materials || !d->materials))
-    return fail(RT_ERR_INVALID_ARG, "materials missing");
-  if (d->n_lights && !d->lights) return fail(RT_ERR_INVALID_ARG, "lights missing");
-  for (uint32_t i = 0; i < d->n_spheres; i++)
-    if (d->sphere_material[i] >= d->n_materials) return fail(RT_ERR_INVALID_ARG, "sphere %u: material out of range", i);
-  for (uint32_t i = 0; i < d->n_triangles; i++)
-    if (d->tri_material[i] >= d->n_materials) return fail(RT_ERR_INVALID_ARG, "triangle %u: material out of range", i);
-
+  int rc = rt_check_scene_desc(d);
+  if (rc != RT_OK) return rc;
   int ndev = rt_device_count();
   if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
   if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
@@ -121,301 +109,26 @@ int rt_scene_create(const rt_scene_desc* d, int device, rt_scene** out) {
   rt_scene* s = new rt_scene();
   s->device = device;
   s->budget = d->device_budget_bytes ? d->device_budget_bytes : RT_SCENE_BUDGET_DEFAULT;
-  auto bail = [&](int rc) {
+  RtPackedScene pk;
+  rc = rt_pack_scene(d, s->budget, &pk);
+  if (rc == RT_OK && pk.n_cells) {  // receiver flags: their kernel's input now, the flags when a frame first needs them (prepare())
+    rc = upload(s->flag_geo, pk.flag_geo.data(), pk.flag_geo.size() * 4);
+    if (rc == RT_OK) rc = s->flags.ensure((size_t)pk.n_cells * 2 + 64);
+  }
+  if (rc == RT_OK) rc = s->counters.ensure(RT_SLOTS * RT_COUNTER_REPLICAS * 16 * sizeof(unsigned long long));
+  if (rc == RT_OK) rc = upload(s->blob, pk.blob.data(), pk.blob.size());
+  if (rc != RT_OK) {
     rt_scene_destroy(s);
     return rc;
-  };
-  auto upload = [&](DevBuf& b, const void* src, size_t bytes) -> int {
-    int rc = b.ensure(bytes);
-    if (rc != RT_OK) return rc;
-    if (bytes) {
-      hipError_t e = hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) return fail(RT_ERR_HIP, "hipMemcpy H2D failed: %s", hipGetErrorString(e));
-    }
-    return RT_OK;
-  };
-
-  const uint32_t ns = d->n_spheres, nt = d->n_triangles;
-  int rc;
-  // All scene arrays live in ONE device allocation (`blob`): the kernels address them as base + 32-bit byte
-  // offset, which the scalar loads take as an SGPR offset (2 scalar instructions per address instead of 4, and
-  // one base pointer instead of nine in SGPRs).
-  std::vector<unsigned char> blob;
-  auto put = [&](uint32_t* off, const void* src, size_t bytes) {
-    blob.resize((blob.size() + 255) / 256 * 256);
-    *off = (uint32_t)blob.size();
-    if (bytes) blob.insert(blob.end(), (const unsigned char*)src, (const unsigned char*)src + bytes);
-    blob.resize(blob.size() + 64);  // the widest scalar load may read past the last record
-  };
-  {
-    // {cx, cy, cz, r_sq} per sphere, then one float per sphere: an upper bound of the radius (candidate culling)
-    std::vector<float> sp(5 * (size_t)ns);
-    for (uint32_t i = 0; i < ns; i++) {
-      sp[4 * i + 0] = d->sphere_center[3 * i + 0];
-      sp[4 * i + 1] = d->sphere_center[3 * i + 1];
-      sp[4 * i + 2] = d->sphere_center[3 * i + 2];
-      sp[4 * i + 3] = d->sphere_r_sq[i];
-      sp[4 * (size_t)ns + i] = std::sqrt(std::fabs(d->sphere_r_sq[i])) * (1.0f + 4e-7f);
-    }
-    put(&s->dev.off_spheres, sp.data(), 16 * (size_t)ns);
-    put(&s->dev.off_sphere_rad, sp.data() + 4 * (size_t)ns, 4 * (size_t)ns);
-    put(&s->dev.off_sphere_mat, d->sphere_material, (size_t)ns * 4);
   }
-  RtBvh bvh;
-  std::vector<uint8_t> no_split(nt, 0);  // = transmissive
-  {
-    // transmissive triangles must be referenced exactly once (their shadow contributions add up)
-    for (uint32_t i = 0; i < nt; i++) {
-      const float* r = d->materials + (size_t)d->tri_material[i] * RT_MATERIAL_STRIDE;
-      no_split[i] = (r[RT_MAT_HAS_OPACITY] != 0.0f && !(std::fabs(r[RT_MAT_OPACITY]) <= 1.1920929e-7f)) ? 1 : 0;
-    }
-    rt_build_bvh(d->tri_v1, d->tri_e1, d->tri_e2, no_split.data(), nt, d->bvh, &bvh);
-  }
-  {
-    // bounds of everything a ray can hit (Morton keys of secondary hit points)
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    auto grow = [&](float x, float y, float z) {
-      const float v[3] = {x, y, z};
-      for (int a = 0; a < 3; a++)
-        if (std::isfinite(v[a])) lo[a] = std::fmin(lo[a], v[a]), hi[a] = std::fmax(hi[a], v[a]);
-    };
-    for (uint32_t i = 0; i < ns; i++) {
-      const float* c = d->sphere_center + 3 * (size_t)i;
-      const float r = std::sqrt(std::fabs(d->sphere_r_sq[i]));
-      grow(c[0] - r, c[1] - r, c[2] - r), grow(c[0] + r, c[1] + r, c[2] + r);
-    }
-    for (uint32_t i = 0; i < nt; i++) {
-      const float *v = d->tri_v1 + 3 * (size_t)i, *a = d->tri_e1 + 3 * (size_t)i, *b = d->tri_e2 + 3 * (size_t)i;
-      grow(v[0], v[1], v[2]), grow(v[0] + a[0], v[1] + a[1], v[2] + a[2]), grow(v[0] + b[0], v[1] + b[1], v[2] + b[2]);
-    }
-    for (int a = 0; a < 3; a++) {
-      if (!(lo[a] <= hi[a])) lo[a] = 0.f, hi[a] = 1.f;
-      s->aabb_lo[a] = lo[a], s->aabb_hi[a] = hi[a];
-    }
-  }
-  const uint32_t n_slots = (uint32_t)bvh.tri_order.size();
-  {
-    // leaf-order intersection records; shading records: [0,n_slots) leaf order, then canonical order
-    std::vector<float> isect(12 * (size_t)n_slots), shade(4 * ((size_t)n_slots + nt));
-    auto put_shade = [&](size_t dst, uint32_t t) {
-      float* sh = &shade[4 * dst];
-      sh[0] = d->tri_normal[3 * (size_t)t + 0];
-      sh[1] = d->tri_normal[3 * (size_t)t + 1];
-      sh[2] = d->tri_normal[3 * (size_t)t + 2];
-      uint32_t m = d->tri_material[t];
-      memcpy(&sh[3], &m, 4);
-    };
-    for (uint32_t t = 0; t < nt; t++) put_shade((size_t)n_slots + t, t);
-    for (uint32_t slot = 0; slot < n_slots; slot++) {
-      uint32_t t = bvh.tri_order[slot] & ~RT_TRI_DUPLICATE;
-      const float* v1 = d->tri_v1 + 3 * (size_t)t;
-      const float* e1 = d->tri_e1 + 3 * (size_t)t;
-      const float* e2 = d->tri_e2 + 3 * (size_t)t;
-      // X = e1 x e2 in ultraviolet's cross form, bit-equal to cross(-e1, -e2) (triangle.rs:174-177).
-      // volatile keeps the host compiler from contracting mul+add into an fma.
-      volatile float a0 = e1[1] * e2[2], b0 = e1[2] * e2[1];
-      volatile float a1 = e1[2] * e2[0], b1 = e1[0] * e2[2];
-      volatile float a2 = e1[0] * e2[1], b2 = e1[1] * e2[0];
-      float X[3] = {a0 + (-b0), a1 + (-b1), a2 + (-b2)};
-      float* q = &isect[12 * (size_t)slot];
-      q[0] = v1[0], q[1] = v1[1], q[2] = v1[2], q[3] = e1[0];
-      q[4] = e1[1], q[5] = e1[2], q[6] = e2[0], q[7] = e2[1];
-      q[8] = e2[2], q[9] = X[0], q[10] = X[1], q[11] = X[2];
-      put_shade(slot, t);
-    }
-    put(&s->dev.off_tri_isect, isect.data(), isect.size() * 4);
-    {
-      // Receiver cells: every triangle carries an R x R grid over its (u, v) coordinates, cells of about 1/1024 of the
-      // scene's diagonal (R = 1 for the small triangles of a mesh, up to 1024 for a wall).  The flags themselves depend on
-      // the light clouds and are computed by rt_flags_kernel when a frame first needs them (prepare()).
-      double diag2 = 0.0, pmax = 0.0;
-      for (int a = 0; a < 3; a++) {
-        diag2 += (double)(s->aabb_hi[a] - s->aabb_lo[a]) * (s->aabb_hi[a] - s->aabb_lo[a]);
-        pmax = std::fmax(pmax, std::fmax(std::fabs((double)s->aabb_lo[a]), std::fabs((double)s->aabb_hi[a])));
-      }
-      std::vector<float> recv(12 * (size_t)nt), geo(12 * (size_t)nt);
-      uint64_t total = 0;
-      // (a scene of many wall-sized triangles: coarser cells until the flags stay below 2^26 cells = 128 MiB)
-      double cell_used = 0.0;
-      for (double cell = std::sqrt(diag2) / 1024.0;; cell *= 2.0) {
-        total = 0;
-        cell_used = cell;
-        for (uint32_t t = 0; t < nt; t++) {
-          const float *v1 = d->tri_v1 + 3 * (size_t)t, *e1 = d->tri_e1 + 3 * (size_t)t, *e2 = d->tri_e2 + 3 * (size_t)t;
-          const double n[3] = {(double)e1[1] * e2[2] - (double)e1[2] * e2[1], (double)e1[2] * e2[0] - (double)e1[0] * e2[2],
-                               (double)e1[0] * e2[1] - (double)e1[1] * e2[0]};
-          const double nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
-          double l1 = 0, l2 = 0;
-          for (int a = 0; a < 3; a++) l1 += (double)e1[a] * e1[a], l2 += (double)e2[a] * e2[a];
-          uint32_t Rr = 0;
-          float* q = &recv[12 * (size_t)t];
-          for (int k = 0; k < 12; k++) q[k] = 0.f;
-          if (nn > 0.0 && std::isfinite(nn) && cell > 0.0) {
-            Rr = (uint32_t)std::fmin(1024.0, std::fmax(1.0, std::ceil(std::sqrt(std::fmax(l1, l2)) / cell)));
-            // u = (p - v1) . (e2 x n) / n.n,  v = (p - v1) . (n x e1) / n.n
-            const double au[3] = {(e2[1] * n[2] - e2[2] * n[1]) / nn, (e2[2] * n[0] - e2[0] * n[2]) / nn, (e2[0] * n[1] - e2[1] * n[0]) / nn};
-            const double av[3] = {(n[1] * e1[2] - n[2] * e1[1]) / nn, (n[2] * e1[0] - n[0] * e1[2]) / nn, (n[0] * e1[1] - n[1] * e1[0]) / nn};
-            const double au0 = -(v1[0] * au[0] + v1[1] * au[1] + v1[2] * au[2]), av0 = -(v1[0] * av[0] + v1[1] * av[1] + v1[2] * av[2]);
-            q[0] = (float)au[0], q[1] = (float)au[1], q[2] = (float)au[2], q[3] = (float)au0;
-            q[4] = (float)av[0], q[5] = (float)av[1], q[6] = (float)av[2], q[7] = (float)av0;
-            for (int k = 0; k < 8; k++)
-              if (!std::isfinite(q[k])) Rr = 0;
-            // The kernel evaluates the maps in fp32: a sliver's are ill-conditioned.  The cells are computed 5 % larger
-            // than they are; keep the error of u * R, v * R below 4 % of a cell (R = 1 needs no coordinates at all).
-            const double err = 4e-7 * std::fmax((std::fabs(au[0]) + std::fabs(au[1]) + std::fabs(au[2])) * pmax + std::fabs(au0),
-                                                (std::fabs(av[0]) + std::fabs(av[1]) + std::fabs(av[2])) * pmax + std::fabs(av0));
-            if (Rr > 1u && err * Rr > 0.04) Rr = (uint32_t)std::fmax(1.0, std::floor(0.04 / err));
-          }
-          const uint32_t first = (uint32_t)total;
-          memcpy(&q[8], &Rr, 4), memcpy(&q[9], &first, 4);
-          float* g = &geo[12 * (size_t)t];
-          g[0] = v1[0], g[1] = v1[1], g[2] = v1[2], memcpy(&g[3], &Rr, 4);
-          g[4] = e1[0], g[5] = e1[1], g[6] = e1[2], memcpy(&g[7], &first, 4);
-          g[8] = e2[0], g[9] = e2[1], g[10] = e2[2], g[11] = 0.f;
-          total += (uint64_t)Rr * Rr;
-        }
-        // (the flags -- 2 bytes per cell, plus this kernel input of 48 bytes per triangle -- must fit the scene's budget for optional tables)
-        if (total <= (1ull << 26) && total * 2u + geo.size() * 4u <= s->budget) break;
-        if (total <= nt) break;  // (one cell per triangle: coarser does not exist)
-      }
-      // a budget not even the coarsest flags fit: no receiver cells at all (rt_stats.notes: RT_NOTE_RECV_FLAGS_OFF_SCENE)
-      const bool cells_fit = total <= (1ull << 26) && total * 2u + geo.size() * 4u <= s->budget;
-      if (!cells_fit) total = 0;
-      put(&s->dev.off_recv, recv.data(), recv.size() * 4);
-      s->n_tri_cells = (uint32_t)total;
-      {
-        // sphere receivers: a cube map of directions per sphere, cells of about the same size on its surface
-        std::vector<uint32_t> srecv(2 * (size_t)ns + 2, 0u);
-        for (uint32_t i = 0; i < ns; i++) {
-          const double r = std::sqrt(std::fabs((double)d->sphere_r_sq[i]));
-          uint32_t Rs = 0;
-          if (cells_fit && std::isfinite(r) && r > 0.0 && cell_used > 0.0) Rs = (uint32_t)std::fmin(256.0, std::fmax(1.0, std::ceil(1.5708 * r / cell_used)));
-          if (total + 6ull * Rs * Rs > (1ull << 27) || (total + 6ull * Rs * Rs) * 2u + geo.size() * 4u > s->budget) Rs = 0;
-          srecv[2 * i] = Rs, srecv[2 * i + 1] = (uint32_t)total;
-          total += 6ull * Rs * Rs;
-        }
-        put(&s->dev.off_srecv, srecv.data(), srecv.size() * 4);
-      }
-      s->n_cells = (uint32_t)total;
-      if (s->n_cells) {
-        if ((rc = upload(s->flag_geo, geo.data(), geo.size() * 4)) != RT_OK) return bail(rc);
-        if ((rc = s->flags.ensure((size_t)s->n_cells * 2 + 64)) != RT_OK) return bail(rc);
-      }
-    }
-    put(&s->dev.off_tri_shade, shade.data(), shade.size() * 4);
-    std::vector<uint32_t> ids(bvh.tri_order);
-    for (uint32_t slot = 0; slot < n_slots; slot++)
-      if (no_split[ids[slot] & ~RT_TRI_DUPLICATE]) ids[slot] |= RT_TRI_TRANSMISSIVE;
-    put(&s->dev.off_tri_id, ids.data(), (size_t)n_slots * 4);
-    put(&s->dev.off_nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(RtNode));
-    {
-      // per-octant copies for the soft-shadow candidate walk: planes pre-selected (lo = entry, hi = exit), the
-      // child that is entered first along the octant's diagonal stored first
-      const size_t nn = bvh.nodes.size();
-      std::vector<RtNode> oct(8 * nn);
-      for (uint32_t o = 0; o < 8; o++)
-        for (size_t i = 0; i < nn; i++) {
-          const RtNode& src = bvh.nodes[i];
-          RtNode d0 = src;
-          float key[2] = {0.f, 0.f};
-          for (int a = 0; a < 3; a++) {
-            const bool neg = (o >> a) & 1u;
-            if (src.c0 != RT_NODE_EMPTY) {
-              d0.lo0[a] = neg ? src.hi0[a] : src.lo0[a];
-              d0.hi0[a] = neg ? src.lo0[a] : src.hi0[a];
-              key[0] += neg ? -src.hi0[a] : src.lo0[a];
-            }
-            if (src.c1 != RT_NODE_EMPTY) {
-              d0.lo1[a] = neg ? src.hi1[a] : src.lo1[a];
-              d0.hi1[a] = neg ? src.lo1[a] : src.hi1[a];
-              key[1] += neg ? -src.hi1[a] : src.lo1[a];
-            }
-          }
-          if (src.c0 != RT_NODE_EMPTY && src.c1 != RT_NODE_EMPTY && key[1] < key[0]) {
-            RtNode sw = d0;
-            memcpy(sw.lo0, d0.lo1, 12), memcpy(sw.hi0, d0.hi1, 12), sw.c0 = d0.c1, sw.n0 = d0.n1;
-            memcpy(sw.lo1, d0.lo0, 12), memcpy(sw.hi1, d0.hi0, 12), sw.c1 = d0.c0, sw.n1 = d0.n0;
-            d0 = sw;
-          }
-          oct[o * nn + i] = d0;
-        }
-      put(&s->dev.off_nodes_oct, oct.data(), oct.size() * sizeof(RtNode));
-    }
-    {
-      // threaded copy (depth first, skip links) for the stackless per-lane walk of incoherent wavefronts
-      std::vector<RtThrNode> thr;
-      struct Emit {
-        const std::vector<RtNode>& nodes;
-        std::vector<RtThrNode>& out;
-        void child(const float* lo, const float* hi, uint32_t c, uint32_t n) {
-          if (c == RT_NODE_EMPTY) return;
-          const size_t idx = out.size();
-          RtThrNode t;
-          memcpy(t.lo, lo, 12), memcpy(t.hi, hi, 12);
-          t.skip = 0;
-          t.leaf = n ? ((n << 24) | c) : 0u;
-          out.push_back(t);
-          if (!n) node(c);
-          out[idx].skip = (uint32_t)out.size();
-        }
-        void node(uint32_t i) {
-          const RtNode nd = nodes[i];
-          child(nd.lo0, nd.hi0, nd.c0, nd.n0);
-          child(nd.lo1, nd.hi1, nd.c1, nd.n1);
-        }
-      } emit{bvh.nodes, thr};
-      if (!bvh.nodes.empty()) emit.node(0);
-      if (n_slots >= (1u << 24)) return bail(fail(RT_ERR_UNSUPPORTED, "more than 2^24 triangle references"));
-      s->dev.n_thr = (uint32_t)thr.size();
-      put(&s->dev.off_nodes_thr, thr.data(), thr.size() * sizeof(RtThrNode));
-    }
-  }
-  {
-    std::vector<float> m(12 * (size_t)d->n_materials, 0.f);
-    for (uint32_t i = 0; i < d->n_materials; i++) {
-      const float* r = d->materials + (size_t)i * RT_MATERIAL_STRIDE;
-      float* o = &m[12 * (size_t)i];
-      o[0] = r[RT_MAT_R], o[1] = r[RT_MAT_G], o[2] = r[RT_MAT_B], o[3] = r[RT_MAT_METALLIC];
-      o[4] = r[RT_MAT_SHININESS], o[5] = r[RT_MAT_IOR], o[6] = r[RT_MAT_OPACITY], o[7] = r[RT_MAT_BOOST];
-      o[8] = r[RT_MAT_HAS_OPACITY];
-      // constants of compute_fresnel against other_ior = 1.0 (every shadow ray, raytracer.rs:64-66): the two IEEE
-      // divisions of a wave-uniform material would otherwise run on the vector ALU per occluder hit per sample.
-      // volatile: no host-side contraction; the same single-precision operations the kernel would execute.
-      volatile float ior = r[RT_MAT_IOR], one = 1.0f;
-      volatile float inv_ior = one / ior;
-      volatile float q = (one - ior) / (one + ior);
-      volatile float f0 = q * q;
-      o[9] = inv_ior, o[10] = f0;
-    }
-    put(&s->dev.off_materials, m.data(), m.size() * 4);
-    std::vector<float> l(8 * (size_t)d->n_lights, 0.f);
-    for (uint32_t i = 0; i < d->n_lights; i++) {
-      const float* r = d->lights + (size_t)i * RT_LIGHT_STRIDE;
-      float* o = &l[8 * (size_t)i];
-      o[0] = r[0], o[1] = r[1], o[2] = r[2], o[3] = r[6];
-      o[4] = r[3], o[5] = r[4], o[6] = r[5];
-    }
-    put(&s->dev.off_lights, l.data(), l.size() * 4);
-  }
-  if ((rc = s->counters.ensure(RT_SLOTS * RT_COUNTER_REPLICAS * 16 * sizeof(unsigned long long))) != RT_OK) return bail(rc);
-  s->bytes_bvh = bvh.nodes.size() * sizeof(RtNode) * 9u + (size_t)s->dev.n_thr * sizeof(RtThrNode);
-
-  if (blob.size() >= (size_t)1 << 32) return bail(fail(RT_ERR_UNSUPPORTED, "scene data exceeds 4 GiB"));
-  if ((rc = upload(s->blob, blob.data(), blob.size())) != RT_OK) return bail(rc);
+  s->dev = pk.dev;
   s->dev.base = (const char*)s->blob.p;
-  s->dev.n_spheres = ns;
-  s->dev.n_triangles = nt;
-  s->dev.n_slots = n_slots;
-  s->dev.n_lights = d->n_lights;
-  s->dev.n_nodes = (uint32_t)bvh.nodes.size();
-  s->info.n_nodes = (uint32_t)bvh.nodes.size();
-  s->info.n_leaves = bvh.n_leaves;
-  s->info.max_depth = bvh.max_depth;
-  s->info.max_leaf_size = bvh.max_leaf;
-  s->info.bytes_nodes = bvh.nodes.size() * sizeof(RtNode);
-  s->info.bytes_triangles = (size_t)n_slots * (48 + 16 + 4) + (size_t)nt * 16;
-  s->info.n_references = n_slots;
-  if (bvh.max_depth + 2 > 64) return bail(fail(RT_ERR_UNSUPPORTED, "BVH depth %u exceeds the traversal stack", bvh.max_depth));
+  s->info = pk.info;
+  s->n_cells = pk.n_cells;
+  s->n_tri_cells = pk.n_tri_cells;
+  s->bytes_bvh = pk.bytes_bvh;
+  memcpy(s->aabb_lo, pk.aabb_lo, sizeof(s->aabb_lo));
+  memcpy(s->aabb_hi, pk.aabb_hi, sizeof(s->aabb_hi));
   *out = s;
   return RT_OK;
 }
@@ -478,13 +191,44 @@ int rt_validate_params(const rt_params* p) {
   return RT_OK;
 }
 
-extern "C" {
+// ---- prepare: the device parameter block of a frame --------------------------------------------------------------------
+// prepare() fills RtDevParams, uploading tables as needed.  What goes INTO a table is arithmetic without a HIP call
+// (rt_tables.cpp); what is here is the stateful part: when a table must be rebuilt, when it may be overwritten, on which
+// stream.  Its stages, in order: copy_view, prepare_aa_table, prepare_cloud_table, prepare_receiver_flags,
+// copy_frame_shape, take_frame_slot, prepare_super_tiles, TableUpload::finish.
 
-// fills the device parameter block, uploading tables / sizing workspaces as needed
-static int prepare(rt_scene* s, const rt_params* p, uint32_t* argb_dev, const rt_aux* aux_dev, hipStream_t stream,
-                   RtDevParams* P) {
+// A table may only be overwritten once the frames that read the old one are done, and kernels on another stream may only
+// start once the upload has landed.
+struct TableUpload {
+  rt_scene* s;
+  hipStream_t stream;
+  bool uploaded = false;
+  // before a table (device copy or its host staging vector) is written
+  int begin() {
+    if (!s->tables_ev) HIP_TRY(hipEventCreateWithFlags(&s->tables_ev, hipEventDisableTiming));
+    // (also covers the host staging vectors: the previous asynchronous upload has read them by now)
+    if (s->tables_pending) HIP_TRY(hipStreamSynchronize(s->tables_stream));
+    for (int b = 0; b < RT_SLOTS; b++)  // every frame still in flight (on whatever stream) reads the old tables
+      if (s->frame_pending[b]) HIP_TRY(hipEventSynchronize(s->frame_ev[b]));
+    uploaded = true;
+    s->tables_version++;
+    return RT_OK;
+  }
+  // once per prepare(): marks this stream's uploads, or makes the stream wait for those of another
+  int finish() {
+    if (uploaded) {
+      HIP_TRY(hipEventRecord(s->tables_ev, stream));
+      s->tables_stream = stream;
+      s->tables_pending = true;
+    } else if (s->tables_pending && s->tables_stream != stream) {
+      HIP_TRY(hipStreamWaitEvent(stream, s->tables_ev, 0));
+    }
+    return RT_OK;
+  }
+};
+
+static void copy_view(const rt_params* p, RtDevParams* P) {
   memset(P, 0, sizeof(*P));
-  s->notes = 0;
   P->width = p->width;
   P->height = p->height;
   memcpy(P->focus, p->focus, sizeof(P->focus));
@@ -495,150 +239,108 @@ static int prepare(rt_scene* s, const rt_params* p, uint32_t* argb_dev, const rt
   P->flags = p->flags;
   const bool aa = (p->flags & RT_FLAG_ANTI_ALIASING) && p->aa_rays > 0;
   P->aa_rays = aa ? p->aa_rays : 0;
-  int rc;
-  bool uploaded = false;
-  // a table may only be overwritten once the frames that read the old one are done, and kernels on another stream
-  // may only start once the upload has landed
-  auto begin_upload = [&]() -> int {
-    if (!s->tables_ev) HIP_TRY(hipEventCreateWithFlags(&s->tables_ev, hipEventDisableTiming));
-    // (also covers the host staging vectors below: the previous asynchronous upload has read them by now)
-    if (s->tables_pending) HIP_TRY(hipStreamSynchronize(s->tables_stream));
-    for (int b = 0; b < RT_SLOTS; b++)  // every frame still in flight (on whatever stream) reads the old tables
-      if (s->frame_pending[b]) HIP_TRY(hipEventSynchronize(s->frame_ev[b]));
-    uploaded = true;
-    s->tables_version++;
-    return RT_OK;
-  };
   P->aa_unique = 1;
-  if (aa) {
-    const size_t n = p->aa_rays;
-    const bool dedup = !p->tuning.no_aa_dedup;
-    if (s->aa_host.size() != 2 * n || memcmp(s->aa_host.data(), p->aa_offsets, 2 * n * 4) != 0 || s->aa_dedup != dedup) {
-      // Distinct offsets in first-occurrence order.  Offsets are compared as VALUES: the origin is pixel + offset,
-      // and equal values (+0 / -0 included: the pixel coordinate is never -0) give bit-identical rays.
-      std::vector<float> uq;
-      std::vector<uint32_t> mult, src(n);
-      for (size_t k = 0; k < n; k++) {
-        const float x = p->aa_offsets[2 * k], y = p->aa_offsets[2 * k + 1];
-        size_t j = uq.size() / 2;
-        if (dedup)
-          for (j = 0; j < uq.size() / 2; j++)
-            if (uq[2 * j] == x && uq[2 * j + 1] == y) break;
-        if (j == uq.size() / 2) uq.push_back(x), uq.push_back(y), mult.push_back(0);
-        mult[j]++;
-        src[k] = (uint32_t)j;
-      }
-      const size_t U = mult.size();
-      if ((rc = begin_upload()) != RT_OK) return rc;
-      s->aa_table.resize(3 * U + n);
-      memcpy(s->aa_table.data(), uq.data(), 2 * U * 4);
-      memcpy(s->aa_table.data() + 2 * U, mult.data(), U * 4);
-      memcpy(s->aa_table.data() + 3 * U, src.data(), n * 4);
-      if ((rc = s->aa.ensure(s->aa_table.size() * 4)) != RT_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(s->aa.p, s->aa_table.data(), s->aa_table.size() * 4, hipMemcpyHostToDevice, stream));
-      s->aa_host.assign(p->aa_offsets, p->aa_offsets + 2 * n);
-      s->aa_unique = (uint32_t)U;
-      s->aa_dedup = dedup;
-    }
-    P->aa_unique = s->aa_unique;
-    P->weighted = s->aa_unique != p->aa_rays;
-    P->aa_offsets = (const float*)s->aa.p;
-    P->aa_mult = (const uint32_t*)s->aa.p + 2 * (size_t)s->aa_unique;
-    P->aa_src = (const uint32_t*)s->aa.p + 3 * (size_t)s->aa_unique;
+}
+
+// AA samples: bit-identical repeats of an offset are traced once (rt_build_aa_table)
+static int prepare_aa_table(rt_scene* s, const rt_params* p, TableUpload& up, RtDevParams* P) {
+  if (!P->aa_rays) return RT_OK;
+  const size_t n = p->aa_rays;
+  const bool dedup = !p->tuning.no_aa_dedup;
+  if (s->aa_host.size() != 2 * n || memcmp(s->aa_host.data(), p->aa_offsets, 2 * n * 4) != 0 || s->aa_dedup != dedup) {
+    std::vector<uint32_t> table;
+    const uint32_t U = rt_build_aa_table(p->aa_offsets, p->aa_rays, dedup, &table);
+    RC_TRY(up.begin());
+    s->aa_table.swap(table);
+    RC_TRY(s->aa.ensure(s->aa_table.size() * 4));
+    HIP_TRY(hipMemcpyAsync(s->aa.p, s->aa_table.data(), s->aa_table.size() * 4, hipMemcpyHostToDevice, up.stream));
+    s->aa_host.assign(p->aa_offsets, p->aa_offsets + 2 * n);
+    s->aa_unique = U;
+    s->aa_dedup = dedup;
   }
+  P->aa_unique = s->aa_unique;
+  P->weighted = s->aa_unique != p->aa_rays;
+  P->aa_offsets = (const float*)s->aa.p;
+  P->aa_mult = (const uint32_t*)s->aa.p + 2 * (size_t)s->aa_unique;
+  P->aa_src = (const uint32_t*)s->aa.p + 3 * (size_t)s->aa_unique;
+  return RT_OK;
+}
+
+// light clouds: the scaled table, its bounding ball (cached with the table) and the beam constants that follow from it
+static int prepare_cloud_table(rt_scene* s, const rt_params* p, TableUpload& up, RtDevParams* P) {
   P->light_mult = p->light_mult < 1 ? 1 : p->light_mult;
   P->cloud_seed = p->cloud_seed;
   P->n_cloud_sets = p->n_cloud_sets;
-  if (P->light_mult > 1) {
-    size_t n = (size_t)p->n_cloud_sets * P->light_mult * 3;
-    const bool new_table = s->cloud_host.size() != n || memcmp(s->cloud_host.data(), p->cloud_sets, n * 4) != 0;
-    const bool new_scale = s->cloud_ball_f[0] != p->fw || s->cloud_ball_f[1] != p->fh || s->cloud_ball_f[2] != p->fd;
-    if (new_table || new_scale) {
-      // The device table holds the offsets already multiplied by (fw, fh, fd) (light.rs:218: the same IEEE
-      // single multiply the kernel would do, done once here), one float4 per sample position.
-      if ((rc = begin_upload()) != RT_OK) return rc;
-      if ((rc = s->cloud.ensure(n / 3 * 16)) != RT_OK) return rc;
-      if (new_table) s->cloud_host.assign(p->cloud_sets, p->cloud_sets + n);
-      s->cloud_ball[3] = -1.f;  // recompute the bounding ball
-      s->cloud_ball_f[0] = p->fw, s->cloud_ball_f[1] = p->fh, s->cloud_ball_f[2] = p->fd;
-      const float f[3] = {p->fw, p->fh, p->fd};
-      s->cloud_scaled.assign(n / 3 * 4, 0.0f);
-      for (size_t i = 0; i < n; i++) s->cloud_scaled[i / 3 * 4 + i % 3] = s->cloud_host[i] * f[i % 3];
-      HIP_TRY(hipMemcpyAsync(s->cloud.p, s->cloud_scaled.data(), n / 3 * 16, hipMemcpyHostToDevice, stream));
-    }
-    P->cloud_sets = (const float4*)s->cloud.p;
-    // bounding ball of the offsets cs * (fw, fh, fd) over all sets (cached with the table)
-    if (s->cloud_ball[3] < 0.f || new_scale) {
-      float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-      const float f[3] = {p->fw, p->fh, p->fd};
-      for (size_t i = 0; i < n; i++) {
-        float v = s->cloud_host[i] * f[i % 3];
-        lo[i % 3] = std::fmin(lo[i % 3], v);
-        hi[i % 3] = std::fmax(hi[i % 3], v);
-      }
-      float r2 = 0.f;
-      for (int a = 0; a < 3; a++) {
-        s->cloud_ball[a] = 0.5f * (lo[a] + hi[a]);
-        float h = 0.5f * (hi[a] - lo[a]);
-        r2 += h * h;
-      }
-      s->cloud_ball[3] = std::sqrt(r2) * 1.001f + 1e-6f;
-    }
-    memcpy(P->cloud_centre, s->cloud_ball, 12);
-    P->cloud_delta = s->cloud_ball[3];
-    {
-      const float e = p->eps_distance;
-      P->beam_delta = P->cloud_delta + 2.0f * e;
-      P->beam_delta_e5 = P->beam_delta + 1e-5f;
-      P->beam_eps_push = 0.998f * e;
-      P->beam_eps_ulp = (1.3e-7f + 2.5e-6f) * e;
-      P->beam_eps_o = 1.01f * e + 2.0f * P->beam_eps_ulp;
-      P->beam_eps_198 = 1.98f * e;
-    }
-    const uint32_t cap = p->tuning.shadow_candidate_cap;
-    P->cand_cap = cap == RT_CAND_CAP_NONE ? 0u : (cap ? cap : 64u);
-    // receiver flags: cells no triangle / sphere can shadow for a light skip the candidate walk (rt_flags_kernel)
-    P->recv_flags = nullptr;
-    // (why the flags are off, when they are: rt_stats.notes)
-    if (p->tuning.no_receiver_flags || P->cand_cap == 0u) s->notes |= RT_NOTE_RECV_FLAGS_OFF_TUNING;
-    if (!s->n_cells || !(P->cloud_delta > 0.0f)) s->notes |= RT_NOTE_RECV_FLAGS_OFF_SCENE;
-    if (s->dev.n_lights > 8u) s->notes |= RT_NOTE_RECV_FLAGS_OFF_LIGHTS;
-    if (p->traversal != RT_TRAVERSAL_BVH) s->notes |= RT_NOTE_RECV_FLAGS_OFF_TRAVERSAL;
-    if (p->flags & RT_FLAG_BACKFACE_CULLING) s->notes |= RT_NOTE_RECV_FLAGS_OFF_CULLING;
-    if (!p->tuning.no_receiver_flags && P->cand_cap != 0u && s->n_cells && s->dev.n_lights <= 8u && p->traversal == RT_TRAVERSAL_BVH &&
-        !(p->flags & RT_FLAG_BACKFACE_CULLING) && P->cloud_delta > 0.0f) {
-      const float key[8] = {P->beam_delta, p->eps_distance, P->cloud_centre[0], P->cloud_centre[1], P->cloud_centre[2], 1.f, 0.f, 0.f};
-      if (memcmp(key, s->flags_key, sizeof(key)) != 0) {
-        if ((rc = begin_upload()) != RT_OK) return rc;  // (waits for kernels of an earlier frame that read the old flags)
-        RtDevParams B = *P;
-        B.flag_out = (uint16_t*)s->flags.p;
-        B.flag_geo = (const float4*)s->flag_geo.p;
-        B.n_cells = s->n_cells;
-        B.n_tri_cells = s->n_tri_cells;
-        // per-cell candidate lists, written by the same kernel: 16 bytes per cell and light (16-bit leaf slots), when the
-        // scene allows it and a quarter of the free memory holds them
-        s->cell_lists_built = false;
-        B.cell_list_out = nullptr;
-        const size_t list_bytes = (size_t)s->n_cells * s->dev.n_lights * 16u;
-        size_t free_b = 0, total_b = 0;
-        const size_t flag_bytes = s->flags.cap + s->flag_geo.cap;
-        if (s->dev.n_slots <= 65533u && flag_bytes + list_bytes <= s->budget && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
-            list_bytes <= (free_b + s->cell_lists.cap) / 4 && s->cell_lists.ensure(list_bytes + 64) == RT_OK) {
-          HIP_TRY(hipMemsetAsync(s->cell_lists.p, 0xFF, list_bytes, stream));
-          B.cell_list_out = (uint16_t*)s->cell_lists.p;
-          s->cell_lists_built = true;
-        }
-        if (!s->cell_lists_built) s->cell_lists.release();  // (a table built under an earlier, larger need)
-        hipError_t e = (hipError_t)rt_launch_flags(s->dev, B, stream);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_flags_kernel launch failed: %s", hipGetErrorString(e));
-        trace_point(stream, "rt_flags_kernel: cells, lights, lists", s->n_cells, s->dev.n_lights, s->cell_lists_built ? 1u : 0u);
-        memcpy(s->flags_key, key, sizeof(key));
-      }
-      P->recv_flags = (const uint16_t*)s->flags.p;
-      if (s->cell_lists_built && !p->tuning.no_cell_lists) P->cell_lists = (const uint4*)s->cell_lists.p;
-    }
-    if (!P->cell_lists) s->notes |= RT_NOTE_CELL_LISTS_OFF;
+  if (P->light_mult <= 1) return RT_OK;
+  const size_t n = (size_t)p->n_cloud_sets * P->light_mult * 3;
+  const bool new_table = s->cloud_host.size() != n || memcmp(s->cloud_host.data(), p->cloud_sets, n * 4) != 0;
+  const bool new_scale = s->cloud_ball_f[0] != p->fw || s->cloud_ball_f[1] != p->fh || s->cloud_ball_f[2] != p->fd;
+  if (new_table || new_scale) {
+    RC_TRY(up.begin());
+    RC_TRY(s->cloud.ensure(n / 3 * 16));
+    if (new_table) s->cloud_host.assign(p->cloud_sets, p->cloud_sets + n);
+    s->cloud_ball_f[0] = p->fw, s->cloud_ball_f[1] = p->fh, s->cloud_ball_f[2] = p->fd;
+    rt_scale_cloud(s->cloud_host.data(), n, s->cloud_ball_f, &s->cloud_scaled, s->cloud_ball);
+    HIP_TRY(hipMemcpyAsync(s->cloud.p, s->cloud_scaled.data(), n / 3 * 16, hipMemcpyHostToDevice, up.stream));
   }
+  P->cloud_sets = (const float4*)s->cloud.p;
+  memcpy(P->cloud_centre, s->cloud_ball, 12);
+  P->cloud_delta = s->cloud_ball[3];
+  rt_beam_constants(p->eps_distance, P);
+  const uint32_t cap = p->tuning.shadow_candidate_cap;
+  P->cand_cap = cap == RT_CAND_CAP_NONE ? 0u : (cap ? cap : 64u);
+  return RT_OK;
+}
+
+// receiver flags: cells no triangle / sphere can shadow for a light skip the candidate walk (rt_flags_kernel); the same
+// kernel writes the per-cell candidate lists.  Both are rebuilt when the beam constants change.
+static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& up, RtDevParams* P) {
+  hipStream_t stream = up.stream;
+  P->recv_flags = nullptr;
+  // (why the flags are off, when they are: rt_stats.notes)
+  if (p->tuning.no_receiver_flags || P->cand_cap == 0u) s->notes |= RT_NOTE_RECV_FLAGS_OFF_TUNING;
+  if (!s->n_cells || !(P->cloud_delta > 0.0f)) s->notes |= RT_NOTE_RECV_FLAGS_OFF_SCENE;
+  if (s->dev.n_lights > 8u) s->notes |= RT_NOTE_RECV_FLAGS_OFF_LIGHTS;
+  if (p->traversal != RT_TRAVERSAL_BVH) s->notes |= RT_NOTE_RECV_FLAGS_OFF_TRAVERSAL;
+  if (p->flags & RT_FLAG_BACKFACE_CULLING) s->notes |= RT_NOTE_RECV_FLAGS_OFF_CULLING;
+  if (!p->tuning.no_receiver_flags && P->cand_cap != 0u && s->n_cells && s->dev.n_lights <= 8u && p->traversal == RT_TRAVERSAL_BVH &&
+      !(p->flags & RT_FLAG_BACKFACE_CULLING) && P->cloud_delta > 0.0f) {
+    const float key[8] = {P->beam_delta, p->eps_distance, P->cloud_centre[0], P->cloud_centre[1], P->cloud_centre[2], 1.f, 0.f, 0.f};
+    if (memcmp(key, s->flags_key, sizeof(key)) != 0) {
+      RC_TRY(up.begin());  // (waits for kernels of an earlier frame that read the old flags)
+      RtDevParams B = *P;
+      B.flag_out = (uint16_t*)s->flags.p;
+      B.flag_geo = (const float4*)s->flag_geo.p;
+      B.n_cells = s->n_cells;
+      B.n_tri_cells = s->n_tri_cells;
+      // per-cell candidate lists, written by the same kernel: 16 bytes per cell and light (16-bit leaf slots), when the
+      // scene allows it and a quarter of the free memory holds them
+      s->cell_lists_built = false;
+      B.cell_list_out = nullptr;
+      const size_t list_bytes = (size_t)s->n_cells * s->dev.n_lights * 16u;
+      size_t free_b = 0, total_b = 0;
+      const size_t flag_bytes = s->flags.cap + s->flag_geo.cap;
+      if (s->dev.n_slots <= 65533u && flag_bytes + list_bytes <= s->budget && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
+          list_bytes <= (free_b + s->cell_lists.cap) / 4 && s->cell_lists.ensure(list_bytes + 64) == RT_OK) {
+        HIP_TRY(hipMemsetAsync(s->cell_lists.p, 0xFF, list_bytes, stream));
+        B.cell_list_out = (uint16_t*)s->cell_lists.p;
+        s->cell_lists_built = true;
+      }
+      if (!s->cell_lists_built) s->cell_lists.release();  // (a table built under an earlier, larger need)
+      hipError_t e = (hipError_t)rt_launch_flags(s->dev, B, stream);
+      if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_flags_kernel launch failed: %s", hipGetErrorString(e));
+      trace_point(stream, "rt_flags_kernel: cells, lights, lists", s->n_cells, s->dev.n_lights, s->cell_lists_built ? 1u : 0u);
+      memcpy(s->flags_key, key, sizeof(key));
+    }
+    P->recv_flags = (const uint16_t*)s->flags.p;
+    if (s->cell_lists_built && !p->tuning.no_cell_lists) P->cell_lists = (const uint4*)s->cell_lists.p;
+  }
+  if (!P->cell_lists) s->notes |= RT_NOTE_CELL_LISTS_OFF;
+  return RT_OK;
+}
+
+// recursion depths, the scheduler's wishes, window, tiling and outputs
+static void copy_frame_shape(rt_scene* s, const rt_params* p, uint32_t* argb_dev, const rt_aux* aux_dev, RtDevParams* P) {
   P->max_depth_reflection = p->max_depth_reflection;
   P->max_depth_refraction = p->max_depth_refraction;
   s->sort_bits_wanted = p->tuning.sort_bits;
@@ -662,39 +364,36 @@ static int prepare(rt_scene* s, const rt_params* p, uint32_t* argb_dev, const rt
     P->aux_hit_id = aux_dev->hit_id;
     P->aux_hit_t = aux_dev->hit_t;
   }
-  {
-    // this frame's slot (counter block + workspace set): one whose last frame has finished if there is one, else the one
-    // used longest ago -- whose frame this stream then waits for
-    // (a slot whose last frame ran on THIS stream is taken first: the stream orders the two frames anyway, and a host that
-    // runs far ahead of the GPU on two streams then holds two workspace sets, not one per slot)
-    int blk = -1, oldest = 0, same = -1;
-    for (int b = 0; b < RT_SLOTS; b++) {
-      if (!s->frame_ev[b]) HIP_TRY(hipEventCreateWithFlags(&s->frame_ev[b], hipEventDisableTiming));
-      if (s->frame_pending[b] && hipEventQuery(s->frame_ev[b]) == hipSuccess) s->frame_pending[b] = false;
-      if (blk < 0 && !s->frame_pending[b]) blk = b;
-      if (same < 0 && s->frame_seq[b] && s->frame_stream[b] == stream) same = b;
-      if (s->frame_seq[b] < s->frame_seq[oldest]) oldest = b;
-    }
-    if (same >= 0 && s->frame_pending[same]) blk = same;  // still running: queue up behind it on its stream
-    if (blk < 0) blk = oldest;
-    if (s->frame_pending[blk] && s->frame_stream[blk] != stream) HIP_TRY(hipStreamWaitEvent(stream, s->frame_ev[blk], 0));
-    s->frame_stream[blk] = stream;
-    s->frame_seq[blk] = ++s->frame_no;
-    s->cur_block = blk;
-    unsigned long long* blk_p = (unsigned long long*)s->counters.p + (size_t)blk * RT_COUNTER_REPLICAS * 16;
-    P->counters = p->tuning.no_counters ? nullptr : blk_p;
-    HIP_TRY(hipMemsetAsync(blk_p, 0, RT_COUNTER_REPLICAS * 16 * sizeof(unsigned long long), stream));
-  }
+}
 
-  const bool aa_on = P->aa_rays > 0;
-  if (aa_on && P->aa_rays > 256) return fail(RT_ERR_UNSUPPORTED, "aa_rays > 256");
-  for (int a = 0; a < 3; a++) {
-    const float ext = s->aabb_hi[a] - s->aabb_lo[a];
-    P->morton_lo[a] = s->aabb_lo[a] - 0.01f * ext;
-    P->morton_scale[a] = ext > 0.f ? 1024.0f / (1.02f * ext) : 0.f;
+// This frame's slot (counter block + workspace set): one whose last frame has finished if there is one, else the one
+// used longest ago -- whose frame this stream then waits for.
+// (a slot whose last frame ran on THIS stream is taken first: the stream orders the two frames anyway, and a host that
+// runs far ahead of the GPU on two streams then holds two workspace sets, not one per slot)
+static int take_frame_slot(rt_scene* s, const rt_params* p, hipStream_t stream, RtDevParams* P) {
+  int blk = -1, oldest = 0, same = -1;
+  for (int b = 0; b < RT_SLOTS; b++) {
+    if (!s->frame_ev[b]) HIP_TRY(hipEventCreateWithFlags(&s->frame_ev[b], hipEventDisableTiming));
+    if (s->frame_pending[b] && hipEventQuery(s->frame_ev[b]) == hipSuccess) s->frame_pending[b] = false;
+    if (blk < 0 && !s->frame_pending[b]) blk = b;
+    if (same < 0 && s->frame_seq[b] && s->frame_stream[b] == stream) same = b;
+    if (s->frame_seq[b] < s->frame_seq[oldest]) oldest = b;
   }
-  // The super-tiles (16x16 pixels) this launch renders, in launch order.  Multi-GPU: only those that hold pixels of this
-  // rank's tiles.  RT_TILE_ORDER_COST: heaviest first, by the cost map measured on a calibration frame of this shape.
+  if (same >= 0 && s->frame_pending[same]) blk = same;  // still running: queue up behind it on its stream
+  if (blk < 0) blk = oldest;
+  if (s->frame_pending[blk] && s->frame_stream[blk] != stream) HIP_TRY(hipStreamWaitEvent(stream, s->frame_ev[blk], 0));
+  s->frame_stream[blk] = stream;
+  s->frame_seq[blk] = ++s->frame_no;
+  s->cur_block = blk;
+  unsigned long long* blk_p = (unsigned long long*)s->counters.p + (size_t)blk * RT_COUNTER_REPLICAS * 16;
+  P->counters = p->tuning.no_counters ? nullptr : blk_p;
+  HIP_TRY(hipMemsetAsync(blk_p, 0, RT_COUNTER_REPLICAS * 16 * sizeof(unsigned long long), stream));
+  return RT_OK;
+}
+
+// The super-tiles (16x16 pixels) this launch renders, in launch order.  Multi-GPU: only those that hold pixels of this
+// rank's tiles.  RT_TILE_ORDER_COST: heaviest first, by the cost map measured on a calibration frame of this shape.
+static int prepare_super_tiles(rt_scene* s, const rt_params* p, TableUpload& up, RtDevParams* P) {
   P->sup_list = nullptr;
   P->n_sup = ((P->win_w + 15u) / 16u) * ((P->win_h + 15u) / 16u);
   uint32_t order = p->tuning.tile_order == RT_TILE_ORDER_COST ? RT_TILE_ORDER_COST : RT_TILE_ORDER_ROW_MAJOR;
@@ -707,45 +406,41 @@ static int prepare(rt_scene* s, const rt_params* p, uint32_t* argb_dev, const rt
     if (memcmp(ck, s->cost_key, sizeof(ck)) != 0) s->cost_valid = false, memcpy(s->cost_key, ck, sizeof(ck));
     s->cost_wanted = !s->cost_valid;  // the caller runs the calibration frame (calibrate_costs)
   }
-  if (P->n_ranks > 1 || (order == RT_TILE_ORDER_COST && s->cost_valid)) {
-    const uint32_t key[8] = {P->win_x0, P->win_y0, P->win_w, P->win_h, P->tile_size, P->n_ranks, P->rank,
-                             order == RT_TILE_ORDER_COST && s->cost_valid ? 2u : 1u};
-    if (memcmp(key, s->sup_key, sizeof(key)) != 0 || s->sup_host.empty()) {
-      if ((rc = begin_upload()) != RT_OK) return rc;
-      s->sup_host.clear();
-      const uint32_t st_x = (P->win_w + 15u) / 16u, st_y = (P->win_h + 15u) / 16u;
-      for (uint32_t sy = 0; sy < st_y; sy++)
-        for (uint32_t sx = 0; sx < st_x; sx++) {
-          // a 16x16 super-tile spans at most 2 tiles per axis (tile_size >= 16): its corners decide
-          uint32_t x0 = P->win_x0 + sx * 16u, y0 = P->win_y0 + sy * 16u;
-          uint32_t x1 = x0 + 15u < P->win_x0 + P->win_w - 1u ? x0 + 15u : P->win_x0 + P->win_w - 1u;
-          uint32_t y1 = y0 + 15u < P->win_y0 + P->win_h - 1u ? y0 + 15u : P->win_y0 + P->win_h - 1u;
-          bool own = P->n_ranks <= 1;
-          for (uint32_t yy : {y0, y1})
-            for (uint32_t xx : {x0, x1})
-              own = own || rt_tile_owner(xx / P->tile_size, yy / P->tile_size, P->n_ranks) == P->rank;
-          if (own) s->sup_host.push_back(sy * st_x + sx);
-        }
-      if (key[7] == 2u && s->cost_host.size() == (size_t)st_x * st_y)
-        std::stable_sort(s->sup_host.begin(), s->sup_host.end(), [&](uint32_t a, uint32_t b) { return s->cost_host[a] > s->cost_host[b]; });
-      memcpy(s->sup_key, key, sizeof(key));
-      if ((rc = s->suplist.ensure(s->sup_host.size() * 4 + 4)) != RT_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(s->suplist.p, s->sup_host.data(), s->sup_host.size() * 4, hipMemcpyHostToDevice, stream));
-    }
-    P->sup_list = (const uint32_t*)s->suplist.p;
-    P->n_sup = (uint32_t)s->sup_host.size();
+  if (P->n_ranks <= 1 && !(order == RT_TILE_ORDER_COST && s->cost_valid)) return RT_OK;  // all of the window, row-major
+  const uint32_t key[8] = {P->win_x0, P->win_y0, P->win_w, P->win_h, P->tile_size, P->n_ranks, P->rank,
+                           order == RT_TILE_ORDER_COST && s->cost_valid ? 2u : 1u};
+  if (memcmp(key, s->sup_key, sizeof(key)) != 0 || s->sup_host.empty()) {
+    RC_TRY(up.begin());
+    rt_super_tiles(key, P->tile_size, P->n_ranks, P->rank, key[7] == 2u ? &s->cost_host : nullptr, &s->sup_host);
+    memcpy(s->sup_key, key, sizeof(key));
+    RC_TRY(s->suplist.ensure(s->sup_host.size() * 4 + 4));
+    HIP_TRY(hipMemcpyAsync(s->suplist.p, s->sup_host.data(), s->sup_host.size() * 4, hipMemcpyHostToDevice, up.stream));
   }
-  if (uploaded) {
-    HIP_TRY(hipEventRecord(s->tables_ev, stream));
-    s->tables_stream = stream;
-    s->tables_pending = true;
-  } else if (s->tables_pending && s->tables_stream != stream) {
-    HIP_TRY(hipStreamWaitEvent(stream, s->tables_ev, 0));
-  }
+  P->sup_list = (const uint32_t*)s->suplist.p;
+  P->n_sup = (uint32_t)s->sup_host.size();
+  return RT_OK;
+}
+
+static int prepare(rt_scene* s, const rt_params* p, uint32_t* argb_dev, const rt_aux* aux_dev, hipStream_t stream, RtDevParams* P) {
+  TableUpload up{s, stream};
+  s->notes = 0;
+  copy_view(p, P);
+  RC_TRY(prepare_aa_table(s, p, up, P));
+  RC_TRY(prepare_cloud_table(s, p, up, P));
+  if (P->light_mult > 1) RC_TRY(prepare_receiver_flags(s, p, up, P));
+  copy_frame_shape(s, p, argb_dev, aux_dev, P);
+  RC_TRY(take_frame_slot(s, p, stream, P));
+  if (P->aa_rays > 256) return fail(RT_ERR_UNSUPPORTED, "aa_rays > 256");
+  rt_morton_frame(s->aabb_lo, s->aabb_hi, P->morton_lo, P->morton_scale);
+  RC_TRY(prepare_super_tiles(s, p, up, P));
+  RC_TRY(up.finish());
   s->last_stream = stream;
   s->rendered = true;
   return RT_OK;
 }
+
+extern "C" {
+
 
 // ---- frame scheduler -------------------------------------------------------------------------------
 // Without secondary rays a frame is ONE launch of the primary kernel.  With reflections / refractions every child ray
@@ -786,7 +481,6 @@ static int launched(int err, hipStream_t stream, const char* what, const char* l
   if (label) trace_point(stream, label, a, b, c);
   return RT_OK;
 }
-#define RC_TRY(expr) do { const int rc_ = (expr); if (rc_ != RT_OK) return rc_; } while (0)
 
 static uint32_t grid_for(uint64_t items, uint32_t per_wg, uint32_t cap_wgs) {
   uint64_t w = (items + items / 16u + per_wg - 1u) / per_wg + 8u;  // a little above the guess; the loop covers the rest

@@ -7,10 +7,8 @@
 #include <string>
 #include <vector>
 
-#include "rt_internal.h"
+#include "rt_scene_pack.h"  // (rt_internal.h; rt_fail; the device-free scene packer and table builders)
 
-// records the thread-local message of rt_last_error() and returns `code`
-int rt_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 #define fail rt_fail
 
 #define HIP_TRY(expr)                                                                          \

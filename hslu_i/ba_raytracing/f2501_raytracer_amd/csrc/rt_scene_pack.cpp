@@ -1,0 +1,373 @@
+// rt_scene_pack.cpp -- lays out every byte the kernels read from a scene (RtDevScene, rt_internal.h), on the host and
+// without a HIP call: rt_scene_create (rt_api.cpp) uploads what rt_pack_scene returns.  One function per section, in the
+// order of the blob.  Also rt_fail / rt_last_error, so that host-only code links without rt_api.cpp.
+#include <hip/hip_runtime_api.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+#include "rt_scene_pack.h"
+
+static thread_local std::string g_err;
+
+int rt_fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+extern "C" const char* rt_last_error(void) { return g_err.c_str(); }
+
+int rt_check_scene_desc(const rt_scene_desc* d) {
+  if (!d) return rt_fail(RT_ERR_INVALID_ARG, "null argument");
+  if (d->abi_version != RT_ABI_VERSION)
+    return rt_fail(RT_ERR_INVALID_ARG, "rt_scene_desc.abi_version %u != %u", d->abi_version, RT_ABI_VERSION);
+  if (d->n_spheres && (!d->sphere_center || !d->sphere_r_sq || !d->sphere_material))
+    return rt_fail(RT_ERR_INVALID_ARG, "sphere arrays missing");
+  if (d->n_triangles && (!d->tri_v1 || !d->tri_e1 || !d->tri_e2 || !d->tri_normal || !d->tri_material))
+    return rt_fail(RT_ERR_INVALID_ARG, "triangle arrays missing");
+  if ((d->n_spheres || d->n_triangles) && (!d->n_materials || !d->materials))
+    return rt_fail(RT_ERR_INVALID_ARG, "materials missing");
+  if (d->n_lights && !d->lights) return rt_fail(RT_ERR_INVALID_ARG, "lights missing");
+  for (uint32_t i = 0; i < d->n_spheres; i++)
+    if (d->sphere_material[i] >= d->n_materials) return rt_fail(RT_ERR_INVALID_ARG, "sphere %u: material out of range", i);
+  for (uint32_t i = 0; i < d->n_triangles; i++)
+    if (d->tri_material[i] >= d->n_materials) return rt_fail(RT_ERR_INVALID_ARG, "triangle %u: material out of range", i);
+  return RT_OK;
+}
+
+// All scene arrays live in ONE device allocation (`blob`): the kernels address them as base + 32-bit byte offset, which
+// the scalar loads take as an SGPR offset (2 scalar instructions per address instead of 4, and one base pointer instead
+// of nine in SGPRs).  Every section starts on a multiple of 256 bytes.
+static void put(std::vector<unsigned char>& blob, uint32_t* off, const void* src, size_t bytes) {
+  blob.resize((blob.size() + 255) / 256 * 256);
+  *off = (uint32_t)blob.size();
+  if (bytes) blob.insert(blob.end(), (const unsigned char*)src, (const unsigned char*)src + bytes);
+  blob.resize(blob.size() + 64);  // the widest scalar load may read past the last record
+}
+
+// {cx, cy, cz, r_sq} per sphere, then one float per sphere: an upper bound of the radius (candidate culling)
+static void pack_spheres(const rt_scene_desc* d, RtPackedScene* o) {
+  const uint32_t ns = d->n_spheres;
+  std::vector<float> sp(5 * (size_t)ns);
+  for (uint32_t i = 0; i < ns; i++) {
+    sp[4 * i + 0] = d->sphere_center[3 * i + 0];
+    sp[4 * i + 1] = d->sphere_center[3 * i + 1];
+    sp[4 * i + 2] = d->sphere_center[3 * i + 2];
+    sp[4 * i + 3] = d->sphere_r_sq[i];
+    sp[4 * (size_t)ns + i] = std::sqrt(std::fabs(d->sphere_r_sq[i])) * (1.0f + 4e-7f);
+  }
+  put(o->blob, &o->dev.off_spheres, sp.data(), 16 * (size_t)ns);
+  put(o->blob, &o->dev.off_sphere_rad, sp.data() + 4 * (size_t)ns, 4 * (size_t)ns);
+  put(o->blob, &o->dev.off_sphere_mat, d->sphere_material, (size_t)ns * 4);
+}
+
+// the tree; no_split[t] = triangle t is transmissive: it must be referenced exactly once (its shadow contributions add up)
+static void build_bvh(const rt_scene_desc* d, std::vector<uint8_t>* no_split, RtBvh* bvh) {
+  no_split->assign(d->n_triangles, 0);
+  for (uint32_t i = 0; i < d->n_triangles; i++) {
+    const float* r = d->materials + (size_t)d->tri_material[i] * RT_MATERIAL_STRIDE;
+    (*no_split)[i] = (r[RT_MAT_HAS_OPACITY] != 0.0f && !(std::fabs(r[RT_MAT_OPACITY]) <= 1.1920929e-7f)) ? 1 : 0;
+  }
+  rt_build_bvh(d->tri_v1, d->tri_e1, d->tri_e2, no_split->data(), d->n_triangles, d->bvh, bvh);
+}
+
+// bounds of everything a ray can hit (Morton keys of secondary hit points)
+static void scene_bounds(const rt_scene_desc* d, float aabb_lo[3], float aabb_hi[3]) {
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  auto grow = [&](float x, float y, float z) {
+    const float v[3] = {x, y, z};
+    for (int a = 0; a < 3; a++)
+      if (std::isfinite(v[a])) lo[a] = std::fmin(lo[a], v[a]), hi[a] = std::fmax(hi[a], v[a]);
+  };
+  for (uint32_t i = 0; i < d->n_spheres; i++) {
+    const float* c = d->sphere_center + 3 * (size_t)i;
+    const float r = std::sqrt(std::fabs(d->sphere_r_sq[i]));
+    grow(c[0] - r, c[1] - r, c[2] - r), grow(c[0] + r, c[1] + r, c[2] + r);
+  }
+  for (uint32_t i = 0; i < d->n_triangles; i++) {
+    const float *v = d->tri_v1 + 3 * (size_t)i, *a = d->tri_e1 + 3 * (size_t)i, *b = d->tri_e2 + 3 * (size_t)i;
+    grow(v[0], v[1], v[2]), grow(v[0] + a[0], v[1] + a[1], v[2] + a[2]), grow(v[0] + b[0], v[1] + b[1], v[2] + b[2]);
+  }
+  for (int a = 0; a < 3; a++) {
+    if (!(lo[a] <= hi[a])) lo[a] = 0.f, hi[a] = 1.f;
+    aabb_lo[a] = lo[a], aabb_hi[a] = hi[a];
+  }
+}
+
+// intersection records in leaf order: {v1, e1, e2, X} of the triangle each slot references
+static void pack_isect_records(const rt_scene_desc* d, const RtBvh& bvh, RtPackedScene* o) {
+  const uint32_t n_slots = (uint32_t)bvh.tri_order.size();
+  std::vector<float> isect(12 * (size_t)n_slots);
+  for (uint32_t slot = 0; slot < n_slots; slot++) {
+    uint32_t t = bvh.tri_order[slot] & ~RT_TRI_DUPLICATE;
+    const float* v1 = d->tri_v1 + 3 * (size_t)t;
+    const float* e1 = d->tri_e1 + 3 * (size_t)t;
+    const float* e2 = d->tri_e2 + 3 * (size_t)t;
+    // X = e1 x e2 in ultraviolet's cross form, bit-equal to cross(-e1, -e2) (triangle.rs:174-177).
+    // volatile keeps the host compiler from contracting mul+add into an fma.
+    volatile float a0 = e1[1] * e2[2], b0 = e1[2] * e2[1];
+    volatile float a1 = e1[2] * e2[0], b1 = e1[0] * e2[2];
+    volatile float a2 = e1[0] * e2[1], b2 = e1[1] * e2[0];
+    float X[3] = {a0 + (-b0), a1 + (-b1), a2 + (-b2)};
+    float* q = &isect[12 * (size_t)slot];
+    q[0] = v1[0], q[1] = v1[1], q[2] = v1[2], q[3] = e1[0];
+    q[4] = e1[1], q[5] = e1[2], q[6] = e2[0], q[7] = e2[1];
+    q[8] = e2[2], q[9] = X[0], q[10] = X[1], q[11] = X[2];
+  }
+  put(o->blob, &o->dev.off_tri_isect, isect.data(), isect.size() * 4);
+}
+
+// One pass of the receiver grid at a given cell size: the receiver record (`q`) and flags-kernel input (`g`) of every
+// triangle.  Returns the number of cells.
+static uint64_t triangle_cells(const rt_scene_desc* d, double cell, double pmax, std::vector<float>* recv, std::vector<float>* geo) {
+  uint64_t total = 0;
+  for (uint32_t t = 0; t < d->n_triangles; t++) {
+    const float *v1 = d->tri_v1 + 3 * (size_t)t, *e1 = d->tri_e1 + 3 * (size_t)t, *e2 = d->tri_e2 + 3 * (size_t)t;
+    const double n[3] = {(double)e1[1] * e2[2] - (double)e1[2] * e2[1], (double)e1[2] * e2[0] - (double)e1[0] * e2[2],
+                         (double)e1[0] * e2[1] - (double)e1[1] * e2[0]};
+    const double nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+    double l1 = 0, l2 = 0;
+    for (int a = 0; a < 3; a++) l1 += (double)e1[a] * e1[a], l2 += (double)e2[a] * e2[a];
+    uint32_t Rr = 0;
+    float* q = &(*recv)[12 * (size_t)t];
+    for (int k = 0; k < 12; k++) q[k] = 0.f;
+    if (nn > 0.0 && std::isfinite(nn) && cell > 0.0) {
+      Rr = (uint32_t)std::fmin(1024.0, std::fmax(1.0, std::ceil(std::sqrt(std::fmax(l1, l2)) / cell)));
+      // u = (p - v1) . (e2 x n) / n.n,  v = (p - v1) . (n x e1) / n.n
+      const double au[3] = {(e2[1] * n[2] - e2[2] * n[1]) / nn, (e2[2] * n[0] - e2[0] * n[2]) / nn, (e2[0] * n[1] - e2[1] * n[0]) / nn};
+      const double av[3] = {(n[1] * e1[2] - n[2] * e1[1]) / nn, (n[2] * e1[0] - n[0] * e1[2]) / nn, (n[0] * e1[1] - n[1] * e1[0]) / nn};
+      const double au0 = -(v1[0] * au[0] + v1[1] * au[1] + v1[2] * au[2]), av0 = -(v1[0] * av[0] + v1[1] * av[1] + v1[2] * av[2]);
+      q[0] = (float)au[0], q[1] = (float)au[1], q[2] = (float)au[2], q[3] = (float)au0;
+      q[4] = (float)av[0], q[5] = (float)av[1], q[6] = (float)av[2], q[7] = (float)av0;
+      for (int k = 0; k < 8; k++)
+        if (!std::isfinite(q[k])) Rr = 0;
+      // The kernel evaluates the maps in fp32: a sliver's are ill-conditioned.  The cells are computed 5 % larger
+      // than they are; keep the error of u * R, v * R below 4 % of a cell (R = 1 needs no coordinates at all).
+      const double err = 4e-7 * std::fmax((std::fabs(au[0]) + std::fabs(au[1]) + std::fabs(au[2])) * pmax + std::fabs(au0),
+                                          (std::fabs(av[0]) + std::fabs(av[1]) + std::fabs(av[2])) * pmax + std::fabs(av0));
+      if (Rr > 1u && err * Rr > 0.04) Rr = (uint32_t)std::fmax(1.0, std::floor(0.04 / err));
+    }
+    const uint32_t first = (uint32_t)total;
+    memcpy(&q[8], &Rr, 4), memcpy(&q[9], &first, 4);
+    float* g = &(*geo)[12 * (size_t)t];
+    g[0] = v1[0], g[1] = v1[1], g[2] = v1[2], memcpy(&g[3], &Rr, 4);
+    g[4] = e1[0], g[5] = e1[1], g[6] = e1[2], memcpy(&g[7], &first, 4);
+    g[8] = e2[0], g[9] = e2[1], g[10] = e2[2], g[11] = 0.f;
+    total += (uint64_t)Rr * Rr;
+  }
+  return total;
+}
+
+// Receiver cells: every triangle carries an R x R grid over its (u, v) coordinates, cells of about 1/1024 of the scene's
+// diagonal (R = 1 for the small triangles of a mesh, up to 1024 for a wall).  The flags themselves depend on the light
+// clouds and are computed by rt_flags_kernel when a frame first needs them (prepare()).
+// Returns the cell size used, or 0 when not even the coarsest flags fit the budget: no receiver cells at all
+// (rt_stats.notes: RT_NOTE_RECV_FLAGS_OFF_SCENE).
+static double pack_triangle_receivers(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {
+  const uint32_t nt = d->n_triangles;
+  double diag2 = 0.0, pmax = 0.0;
+  for (int a = 0; a < 3; a++) {
+    diag2 += (double)(o->aabb_hi[a] - o->aabb_lo[a]) * (o->aabb_hi[a] - o->aabb_lo[a]);
+    pmax = std::fmax(pmax, std::fmax(std::fabs((double)o->aabb_lo[a]), std::fabs((double)o->aabb_hi[a])));
+  }
+  std::vector<float> recv(12 * (size_t)nt);
+  std::vector<float>& geo = o->flag_geo;
+  geo.assign(12 * (size_t)nt, 0.f);
+  // the flags -- 2 bytes per cell, plus their kernel's input of 48 bytes per triangle -- must fit the scene's budget for
+  // optional tables, and stay below 2^26 cells = 128 MiB
+  auto fits = [&](uint64_t total) { return total <= (1ull << 26) && total * 2u + geo.size() * 4u <= budget; };
+  uint64_t total = 0;
+  // (a scene of many wall-sized triangles: coarser cells until the flags fit)
+  double cell = std::sqrt(diag2) / 1024.0;
+  for (;; cell *= 2.0) {
+    total = triangle_cells(d, cell, pmax, &recv, &geo);
+    if (fits(total)) break;
+    if (total <= nt) break;  // (one cell per triangle: coarser does not exist)
+  }
+  const bool cells_fit = fits(total);
+  put(o->blob, &o->dev.off_recv, recv.data(), recv.size() * 4);
+  o->n_tri_cells = cells_fit ? (uint32_t)total : 0u;
+  return cells_fit ? cell : 0.0;
+}
+
+// sphere receivers: a cube map of directions per sphere, cells of about the same size on its surface (`cell`; 0 = none)
+static void pack_sphere_receivers(const rt_scene_desc* d, uint64_t budget, double cell, RtPackedScene* o) {
+  const uint32_t ns = d->n_spheres;
+  const size_t geo_bytes = o->flag_geo.size() * 4u;
+  uint64_t total = o->n_tri_cells;
+  std::vector<uint32_t> srecv(2 * (size_t)ns + 2, 0u);
+  for (uint32_t i = 0; i < ns; i++) {
+    const double r = std::sqrt(std::fabs((double)d->sphere_r_sq[i]));
+    uint32_t Rs = 0;
+    if (std::isfinite(r) && r > 0.0 && cell > 0.0) Rs = (uint32_t)std::fmin(256.0, std::fmax(1.0, std::ceil(1.5708 * r / cell)));
+    if (total + 6ull * Rs * Rs > (1ull << 27) || (total + 6ull * Rs * Rs) * 2u + geo_bytes > budget) Rs = 0;
+    srecv[2 * i] = Rs, srecv[2 * i + 1] = (uint32_t)total;
+    total += 6ull * Rs * Rs;
+  }
+  put(o->blob, &o->dev.off_srecv, srecv.data(), srecv.size() * 4);
+  o->n_cells = (uint32_t)total;
+}
+
+// shading records {normal, bits(material row)}: [0, n_slots) leaf order, then canonical order
+static void pack_shade_records(const rt_scene_desc* d, const RtBvh& bvh, RtPackedScene* o) {
+  const uint32_t nt = d->n_triangles, n_slots = (uint32_t)bvh.tri_order.size();
+  std::vector<float> shade(4 * ((size_t)n_slots + nt));
+  auto put_shade = [&](size_t dst, uint32_t t) {
+    float* sh = &shade[4 * dst];
+    sh[0] = d->tri_normal[3 * (size_t)t + 0];
+    sh[1] = d->tri_normal[3 * (size_t)t + 1];
+    sh[2] = d->tri_normal[3 * (size_t)t + 2];
+    uint32_t m = d->tri_material[t];
+    memcpy(&sh[3], &m, 4);
+  };
+  for (uint32_t t = 0; t < nt; t++) put_shade((size_t)n_slots + t, t);
+  for (uint32_t slot = 0; slot < n_slots; slot++) put_shade(slot, bvh.tri_order[slot] & ~RT_TRI_DUPLICATE);
+  put(o->blob, &o->dev.off_tri_shade, shade.data(), shade.size() * 4);
+}
+
+// per-octant copies for the soft-shadow candidate walk: planes pre-selected (lo = entry, hi = exit), the child that is
+// entered first along the octant's diagonal stored first
+static void pack_octant_nodes(const RtBvh& bvh, RtPackedScene* o) {
+  const size_t nn = bvh.nodes.size();
+  std::vector<RtNode> oct(8 * nn);
+  for (uint32_t oc = 0; oc < 8; oc++)
+    for (size_t i = 0; i < nn; i++) {
+      const RtNode& src = bvh.nodes[i];
+      RtNode d0 = src;
+      float key[2] = {0.f, 0.f};
+      for (int a = 0; a < 3; a++) {
+        const bool neg = (oc >> a) & 1u;
+        if (src.c0 != RT_NODE_EMPTY) {
+          d0.lo0[a] = neg ? src.hi0[a] : src.lo0[a];
+          d0.hi0[a] = neg ? src.lo0[a] : src.hi0[a];
+          key[0] += neg ? -src.hi0[a] : src.lo0[a];
+        }
+        if (src.c1 != RT_NODE_EMPTY) {
+          d0.lo1[a] = neg ? src.hi1[a] : src.lo1[a];
+          d0.hi1[a] = neg ? src.lo1[a] : src.hi1[a];
+          key[1] += neg ? -src.hi1[a] : src.lo1[a];
+        }
+      }
+      if (src.c0 != RT_NODE_EMPTY && src.c1 != RT_NODE_EMPTY && key[1] < key[0]) {
+        RtNode sw = d0;
+        memcpy(sw.lo0, d0.lo1, 12), memcpy(sw.hi0, d0.hi1, 12), sw.c0 = d0.c1, sw.n0 = d0.n1;
+        memcpy(sw.lo1, d0.lo0, 12), memcpy(sw.hi1, d0.hi0, 12), sw.c1 = d0.c0, sw.n1 = d0.n0;
+        d0 = sw;
+      }
+      oct[oc * nn + i] = d0;
+    }
+  put(o->blob, &o->dev.off_nodes_oct, oct.data(), oct.size() * sizeof(RtNode));
+}
+
+// threaded copy (depth first, skip links) for the stackless per-lane walk of incoherent wavefronts
+static void pack_threaded_nodes(const RtBvh& bvh, RtPackedScene* o) {
+  std::vector<RtThrNode> thr;
+  struct Emit {
+    const std::vector<RtNode>& nodes;
+    std::vector<RtThrNode>& out;
+    void child(const float* lo, const float* hi, uint32_t c, uint32_t n) {
+      if (c == RT_NODE_EMPTY) return;
+      const size_t idx = out.size();
+      RtThrNode t;
+      memcpy(t.lo, lo, 12), memcpy(t.hi, hi, 12);
+      t.skip = 0;
+      t.leaf = n ? ((n << 24) | c) : 0u;
+      out.push_back(t);
+      if (!n) node(c);
+      out[idx].skip = (uint32_t)out.size();
+    }
+    void node(uint32_t i) {
+      const RtNode nd = nodes[i];
+      child(nd.lo0, nd.hi0, nd.c0, nd.n0);
+      child(nd.lo1, nd.hi1, nd.c1, nd.n1);
+    }
+  } emit{bvh.nodes, thr};
+  if (!bvh.nodes.empty()) emit.node(0);
+  o->dev.n_thr = (uint32_t)thr.size();
+  put(o->blob, &o->dev.off_nodes_thr, thr.data(), thr.size() * sizeof(RtThrNode));
+}
+
+// 3 x float4 per material: the description's row, then the constants of compute_fresnel
+static void pack_materials(const rt_scene_desc* d, RtPackedScene* o) {
+  std::vector<float> m(12 * (size_t)d->n_materials, 0.f);
+  for (uint32_t i = 0; i < d->n_materials; i++) {
+    const float* r = d->materials + (size_t)i * RT_MATERIAL_STRIDE;
+    float* q = &m[12 * (size_t)i];
+    q[0] = r[RT_MAT_R], q[1] = r[RT_MAT_G], q[2] = r[RT_MAT_B], q[3] = r[RT_MAT_METALLIC];
+    q[4] = r[RT_MAT_SHININESS], q[5] = r[RT_MAT_IOR], q[6] = r[RT_MAT_OPACITY], q[7] = r[RT_MAT_BOOST];
+    q[8] = r[RT_MAT_HAS_OPACITY];
+    // constants of compute_fresnel against other_ior = 1.0 (every shadow ray, raytracer.rs:64-66): the two IEEE
+    // divisions of a wave-uniform material would otherwise run on the vector ALU per occluder hit per sample.
+    // volatile: no host-side contraction; the same single-precision operations the kernel would execute.
+    volatile float ior = r[RT_MAT_IOR], one = 1.0f;
+    volatile float inv_ior = one / ior;
+    volatile float k = (one - ior) / (one + ior);
+    volatile float f0 = k * k;
+    q[9] = inv_ior, q[10] = f0;
+  }
+  put(o->blob, &o->dev.off_materials, m.data(), m.size() * 4);
+}
+
+// 2 x float4 per light: {x, y, z, intensity} {r, g, b, 0}
+static void pack_lights(const rt_scene_desc* d, RtPackedScene* o) {
+  std::vector<float> l(8 * (size_t)d->n_lights, 0.f);
+  for (uint32_t i = 0; i < d->n_lights; i++) {
+    const float* r = d->lights + (size_t)i * RT_LIGHT_STRIDE;
+    float* q = &l[8 * (size_t)i];
+    q[0] = r[0], q[1] = r[1], q[2] = r[2], q[3] = r[6];
+    q[4] = r[3], q[5] = r[4], q[6] = r[5];
+  }
+  put(o->blob, &o->dev.off_lights, l.data(), l.size() * 4);
+}
+
+int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {
+  *o = RtPackedScene();
+  const uint32_t nt = d->n_triangles;
+  pack_spheres(d, o);
+  RtBvh bvh;
+  std::vector<uint8_t> no_split;
+  build_bvh(d, &no_split, &bvh);
+  const uint32_t n_slots = (uint32_t)bvh.tri_order.size();
+  if (n_slots >= (1u << 24)) return rt_fail(RT_ERR_UNSUPPORTED, "more than 2^24 triangle references");
+  scene_bounds(d, o->aabb_lo, o->aabb_hi);
+  pack_isect_records(d, bvh, o);
+  const double cell = pack_triangle_receivers(d, budget, o);
+  pack_sphere_receivers(d, budget, cell, o);
+  if (!o->n_cells) o->flag_geo.clear();
+  pack_shade_records(d, bvh, o);
+  // leaf slot -> canonical triangle index, RT_TRI_DUPLICATE as built, RT_TRI_TRANSMISSIVE added here
+  std::vector<uint32_t> ids(bvh.tri_order);
+  for (uint32_t slot = 0; slot < n_slots; slot++)
+    if (no_split[ids[slot] & ~RT_TRI_DUPLICATE]) ids[slot] |= RT_TRI_TRANSMISSIVE;
+  put(o->blob, &o->dev.off_tri_id, ids.data(), (size_t)n_slots * 4);
+  put(o->blob, &o->dev.off_nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(RtNode));
+  pack_octant_nodes(bvh, o);
+  pack_threaded_nodes(bvh, o);
+  pack_materials(d, o);
+  pack_lights(d, o);
+  if (o->blob.size() >= (size_t)1 << 32) return rt_fail(RT_ERR_UNSUPPORTED, "scene data exceeds 4 GiB");
+  if (bvh.max_depth + 2 > 64) return rt_fail(RT_ERR_UNSUPPORTED, "BVH depth %u exceeds the traversal stack", bvh.max_depth);
+
+  o->bytes_bvh = bvh.nodes.size() * sizeof(RtNode) * 9u + (size_t)o->dev.n_thr * sizeof(RtThrNode);
+  o->dev.n_spheres = d->n_spheres;
+  o->dev.n_triangles = nt;
+  o->dev.n_slots = n_slots;
+  o->dev.n_lights = d->n_lights;
+  o->dev.n_nodes = (uint32_t)bvh.nodes.size();
+  o->info.n_nodes = (uint32_t)bvh.nodes.size();
+  o->info.n_leaves = bvh.n_leaves;
+  o->info.max_depth = bvh.max_depth;
+  o->info.max_leaf_size = bvh.max_leaf;
+  o->info.bytes_nodes = bvh.nodes.size() * sizeof(RtNode);
+  o->info.bytes_triangles = (size_t)n_slots * (48 + 16 + 4) + (size_t)nt * 16;
+  o->info.n_references = n_slots;
+  return RT_OK;
+}

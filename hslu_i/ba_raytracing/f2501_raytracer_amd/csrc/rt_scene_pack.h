@@ -1,0 +1,47 @@
+// rt_scene_pack.h -- the device-free half of the host side: what a scene looks like in device memory
+// (rt_scene_pack.cpp) and the arithmetic behind a frame's parameter tables (rt_tables.cpp).  Neither file makes a HIP
+// call, so both are compiled host-only and checked on the CPU (tests/test_scene_pack_host.py).
+// Not part of the public ABI.
+#pragma once
+
+#include <vector>
+
+#include "rt_internal.h"
+
+// records the thread-local message of rt_last_error() and returns `code` (rt_scene_pack.cpp)
+int rt_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// ---- scene packer ------------------------------------------------------------------------------------------------------
+// Everything rt_scene_create computes before it touches the device.
+struct RtPackedScene {
+  std::vector<unsigned char> blob;  // the one allocation the kernels address as base + offset (rt_scene::blob)
+  RtDevScene dev{};                 // offsets into `blob` and counts; `base` stays null
+  rt_bvh_info info{};
+  std::vector<float> flag_geo;      // input of rt_flags_kernel, 12 floats per triangle; empty when n_cells == 0
+  uint32_t n_cells = 0;             // receiver cells of triangles and spheres
+  uint32_t n_tri_cells = 0;         // ... of which the first n_tri_cells belong to triangles
+  size_t bytes_bvh = 0;             // of `blob`: nodes + octant copies + threaded copy
+  float aabb_lo[3] = {0.f, 0.f, 0.f}, aabb_hi[3] = {1.f, 1.f, 1.f};  // bounds of everything a ray can hit
+};
+
+// the checks of an rt_scene_desc that need no device: RT_OK or RT_ERR_INVALID_ARG
+int rt_check_scene_desc(const rt_scene_desc* d);
+// Lays out a checked description.  `budget` (bytes) bounds the receiver flags and their kernel input.
+// RT_OK, or RT_ERR_UNSUPPORTED (2^24 triangle references, 4 GiB of scene data, a BVH deeper than the traversal stack).
+int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* out);
+
+// ---- parameter tables of a frame -----------------------------------------------------------------------------------------
+// AA samples: the distinct offsets in first-occurrence order (compared as values; `dedup` off: every sample is distinct),
+// their multiplicities and the sample -> thread map, as the device image [2U offsets (float bits) | U | n].  Returns U.
+uint32_t rt_build_aa_table(const float* offsets, uint32_t n, bool dedup, std::vector<uint32_t>* table);
+// Light clouds: one float4 {dx * fw, dy * fh, dz * fd, 0} per sample position (`cloud`: n_floats = 3 per position), and
+// the bounding ball of those offsets: ball[0..2] = its centre, ball[3] = its radius.
+void rt_scale_cloud(const float* cloud, size_t n_floats, const float f[3], std::vector<float>* scaled, float ball[4]);
+// the beam_* constants of the soft-shadow beam tests from P->cloud_delta and eps_distance
+void rt_beam_constants(float eps_distance, RtDevParams* P);
+// the frame Morton keys of secondary hit points are taken in: the scene bounds, widened by 1 % on either side
+void rt_morton_frame(const float aabb_lo[3], const float aabb_hi[3], float morton_lo[3], float morton_scale[3]);
+// The 16x16 super-tiles (window-relative index, row-major) of window win = {x0, y0, w, h} that hold a pixel of a tile of
+// `rank`; all of them for n_ranks <= 1.  `cost` (one entry per super-tile of the window, or null): heaviest first.
+void rt_super_tiles(const uint32_t win[4], uint32_t tile_size, uint32_t n_ranks, uint32_t rank, const std::vector<uint32_t>* cost,
+                    std::vector<uint32_t>* out);
