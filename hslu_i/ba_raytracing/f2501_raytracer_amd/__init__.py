@@ -7,4 +7,5 @@ from .config import DEFAULT_FEATURES, RenderConfig, expand_features  # noqa: F40
 from .f32math import Isometry3, Rotor3, Similarity3, Vec3  # noqa: F401
 from .scene import (BoundedPlane, ColorType, FlatScene, Material, PointLight, Scene, SphereData,  # noqa: F401
                     TransmissionProperties, TriangleData, maximize_value)
-from .renderer import DeviceScene, IntersectionTest, RayHits  # noqa: F401
+from .camera import PinholeCamera, reference_rays  # noqa: F401
+from .renderer import DeviceScene, IntersectionTest, Radiance, RayHits  # noqa: F401

@@ -129,6 +129,10 @@ class rt_ray_occlusion(C.Structure):
                 ("color_filter", C.c_void_p)]
 
 
+class rt_ray_radiance(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("valid", C.c_void_p), ("id", C.c_void_p), ("t", C.c_void_p), ("argb", C.c_void_p)]
+
+
 def fptr(a: np.ndarray):
     assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(_fp)

@@ -80,7 +80,7 @@ void rt_scene_destroy(rt_scene* s) {
       for (DevBuf* b : {&l.queues, &l.qcount, &l.trace_ws, &l.hard, &l.hitrec, &l.sets}) b->release();
     }
   }
-  for (DevBuf* b : {&s->blob, &s->aa, &s->cloud, &s->counters, &s->suplist, &s->fb, &s->aux_rgb, &s->costmap, &s->aux_id, &s->aux_t, &s->flag_geo, &s->flags, &s->cell_lists, &s->progress_fb})
+  for (DevBuf* b : {&s->blob, &s->aa, &s->cloud, &s->counters, &s->suplist, &s->fb, &s->aux_rgb, &s->costmap, &s->aux_id, &s->aux_t, &s->flag_geo, &s->flags, &s->cell_lists, &s->progress_fb, &s->rays_argb})
     b->release();
   delete s;
 }
@@ -151,7 +151,7 @@ int rt_scene_memory_info(const rt_scene* s, rt_scene_info* out) {
     out->bytes_workspace += w.bytes();
     for (const auto& l : w.lane) out->bytes_workspace += l.qcount.cap;
   }
-  out->bytes_frames = s->fb.cap + s->aux_rgb.cap + s->aux_id.cap + s->aux_t.cap + s->progress_fb.cap;
+  out->bytes_frames = s->fb.cap + s->aux_rgb.cap + s->aux_id.cap + s->aux_t.cap + s->progress_fb.cap + s->rays_argb.cap;
   out->bytes_total = out->bytes_geometry + out->bytes_bvh + out->bytes_flags + out->bytes_cell_lists + out->bytes_tables + out->bytes_workspace +
                      out->bytes_frames;
   out->budget_bytes = s->budget;
@@ -506,6 +506,10 @@ struct Frame {
   hipStream_t stream;
   uint32_t forced;  // rt_tuning.chunk_log2: batch size under test (0: sized by need)
   bool blocking;
+  // A ray batch (rt_trace_rays*): a frame of n x 1 "pixels" whose camera rays are the caller's (rt_rays.h).  Its ray counts say
+  // nothing about the next batch, so it is always verified (blocking) and never marks its shape verified; it runs the chained
+  // schedule with fused phases -- the merged-level and phase kernels re-derive the camera ray from the work-item index.
+  const RtRayArgs* rays;
   // ---- plan (hard: soft-shadow sets of incoherent wavefronts deferred to rt_hard_kernel; merged: one append-only queue per chain)
   bool secondary, split, defer, hard = false, merged = false, pipelined = false;
   uint32_t total_wgs, levels = 0, levels_mode = RT_LEVELS_CHAINED, lanes = 1, n_cnt = 0;
@@ -520,15 +524,17 @@ struct Frame {
   float4* q[RT_LANES][2];
   uint32_t* counts[RT_LANES];
   bool forked = false, joined = false, shading = false;
-  Frame(rt_scene* s_, RtDevParams& P_, hipStream_t stream_, uint32_t forced_, bool blocking_)
-      : s(s_), P(P_), stream(stream_), forced(forced_), blocking(blocking_), secondary((P.flags & (RT_FLAG_REFLECTIONS | RT_FLAG_REFRACTIONS)) != 0) {
-    total_wgs = rt_primary_total_wgs(P);
+  Frame(rt_scene* s_, RtDevParams& P_, hipStream_t stream_, uint32_t forced_, bool blocking_, const RtRayArgs* rays_)
+      : s(s_), P(P_), stream(stream_), forced(forced_), blocking(blocking_ || rays_), rays(rays_),
+        secondary((P.flags & (RT_FLAG_REFLECTIONS | RT_FLAG_REFRACTIONS)) != 0) {
+    total_wgs = rays ? (rays->n + 255u) / 256u : rt_primary_total_wgs(P);
     // The phase-split pipeline (rt_phases.h; rt_tuning.phases): hit -> classify -> one kernel per class of (wavefront, light)
     // set -> resolve, instead of the fused kernels.  Frames without secondary rays then also sum through the accumulator.
     split = rt_use_phases(s->phases_wanted, P);
     // RT_PHASES_FUSED_DEFER: the fused kernels, but a frame without secondary rays also sums through the accumulator, so that its
     // incoherent (wavefront, light) sets can be deferred to rt_hard_kernel like those of a frame with secondary rays
     defer = !secondary && !split && !P.cost_map && s->phases_wanted == RT_PHASES_FUSED_DEFER && P.light_mult > 1;
+    if (rays) split = defer = false;
   }
   ~Frame() {
     for (uint32_t j = 1; j < lanes && forked && !joined; j++) (void)hipStreamSynchronize(w->lane[j].stream);
@@ -551,7 +557,7 @@ static int plan_schedule(Frame& f) {
            s->dev.n_triangles && P.cand_cap != 0;
   if (!f.hard && P.light_mult > 1) s->notes |= RT_NOTE_HARD_PAIRS_OFF;
   // merged levels (rt_tuning.levels): every level traced first (the trace kernel appends the children), then ONE sort and ONE shade launch
-  f.levels_mode = (f.secondary && !f.split) ? rt_levels_mode(s->levels_wanted) : RT_LEVELS_CHAINED;
+  f.levels_mode = (f.secondary && !f.split && !f.rays) ? rt_levels_mode(s->levels_wanted) : RT_LEVELS_CHAINED;
   if (f.levels_mode == RT_LEVELS_MERGED && s->levels_wanted == RT_LEVELS_DEFAULT) {
     // The merged queue holds every level of the tree at once (config 4: 5.0 GB against the 2.9 GB of two alternating queues).  Where a
     // third of the free memory (plus what this scene's workspaces already hold) does not take about four times the primary work items,
@@ -632,6 +638,7 @@ static void match_stream_key(Frame& f) {
   memcpy(key.f, P.focus, 12), key.f[3] = P.fw, key.f[4] = P.fh, key.f[5] = P.fd, key.f[6] = P.eps_distance, key.f[7] = P.air_ior;
   key.staged = P.stage_slot != nullptr, key.flags_on = P.recv_flags != nullptr, key.n_sup = P.n_sup, key.lanes = f.lanes, key.merged = f.levels_mode;
   key.split = (f.split ? 1u : 0u) | (f.defer ? 2u : 0u), key.sort_bits = s->sort_bits_wanted, key.lists_on = P.cell_lists != nullptr;
+  key.rays = f.rays ? 1u : 0u;  // (a camera frame behind a ray batch is a new shape: it does not trust sizes the batch left)
   if (memcmp(&key, &s->stream_key, sizeof(key)) != 0) {
     s->stream_key = key, s->key_gen++, s->stream_verified = false, s->est_valid = false;
     s->q_cap = s->hard_cap = s->batch_items = 0;
@@ -733,7 +740,7 @@ static int size_queues(Frame& f, int attempt, bool& oom) {
   f.n_batches = (uint32_t)((f.items + s->batch_items - 1) / s->batch_items);
   if (f.n_batches > f.lanes) s->notes |= RT_NOTE_FRAME_BATCHED;
   f.cap_wgs = (f.q_sort_cap + 255u) / 256u;
-  f.guess = s->est_valid && f.n_batches == f.lanes;
+  f.guess = s->est_valid && f.n_batches == f.lanes && !f.rays;  // (another batch, other counts: whole-capacity grids)
   const uint32_t ppw = 64u / (f.P.light_mult < 2u ? 2u : f.P.light_mult);
   f.pairs_per_wg = 4u * (ppw ? ppw : 1u), f.hard_cap_wgs = f.hard ? (s->hard_cap + f.pairs_per_wg - 1u) / f.pairs_per_wg : 1u;
   return RT_OK;
@@ -817,6 +824,8 @@ static int enqueue_primary(Frame& f, uint32_t j, hipStream_t st, uint32_t w0, ui
     RC_TRY(launched(rt_launch_classify(s->dev, Q, true, nw, st), st, "kernel launch", "rt_classify0_kernel: first workgroup, workgroups, set capacity", w0, nw, f.set_cap));
     return run_sets(f, j, st, 0, nw * 4u * s->dev.n_lights);
   }
+  if (f.rays)
+    return launched(rt_launch_rays(s->dev, Q, *f.rays, nw, st), st, "kernel launch", "rt_rays_stream_kernel: first workgroup, workgroups, queue capacity", w0, nw, s->q_cap);
   if (!f.merged)
     return launched(rt_launch_primary(s->dev, Q, nw, st), st, "kernel launch", "rt_primary_stream_kernel: first workgroup, workgroups, queue capacity", w0, nw, s->q_cap);
   // The camera rays' hits and children first (rt_hit_spawn_kernel: 44 VGPRs, no scratch), so that the levels below can be traced
@@ -988,6 +997,7 @@ static int finish_frame(Frame& f, int attempt, bool& again) {
     need_pairs = std::max(need_pairs, c[RT_CNT_HARD_STAT(levels) + 1u]);
   }
   if (!dropped && !dropped_pairs) {
+    if (f.rays) return RT_OK;  // (verified for THIS batch only: the next one is verified again)
     if (w.cnt_host_valid) memcpy(s->est, w.cnt_host, sizeof(s->est)), s->est_valid = true;
     s->stream_verified = true;
     // headroom for the frames that now run unverified: a quarter more pairs than this frame deferred (takes effect with the next
@@ -1014,13 +1024,14 @@ static int finish_frame(Frame& f, int attempt, bool& again) {
   return RT_OK;
 }
 
-static int render_frame_impl(rt_scene* s, RtDevParams& P, hipStream_t stream, uint32_t forced_chunk_log2, bool blocking) {
+static int render_frame_impl(rt_scene* s, RtDevParams& P, hipStream_t stream, uint32_t forced_chunk_log2, bool blocking, const RtRayArgs* rays) {
   s->queue_bytes = 0;
-  Frame f(s, P, stream, forced_chunk_log2, blocking);
+  Frame f(s, P, stream, forced_chunk_log2, blocking, rays);
   P.resolve_counts_written = f.split ? 1u : 0u;
   if (!f.secondary && !f.split && !f.defer) {  // one launch of the fused primary kernel
     P.acc = nullptr, P.q_out = nullptr;
     P.batch_first_wg = 0, P.batch_stride = 1, P.batch_group_log2 = 0;
+    if (rays) return launched(rt_launch_rays(s->dev, P, *rays, f.total_wgs, stream), stream, "kernel launch", "rt_rays_kernel: workgroups", f.total_wgs);
     char label[64];  // (names the kernel that runs: rt_primary_kernel or the one compiled for this configuration)
     snprintf(label, sizeof(label), "%s: workgroups", rt_primary_variant_name(rt_primary_variant_used(s->dev, P)));
     return launched(rt_launch_primary(s->dev, P, f.total_wgs, stream), stream, "kernel launch", label, f.total_wgs);
@@ -1042,8 +1053,9 @@ static int render_frame_impl(rt_scene* s, RtDevParams& P, hipStream_t stream, ui
 
 // A frame that fails half-way (HIP / launch error, out of memory) leaves partial sums in the pixel accumulator: mark
 // the accumulator dirty so that the next frame clears it.
-static int render_frame(rt_scene* s, RtDevParams& P, hipStream_t stream, uint32_t forced_chunk_log2, bool blocking = false) {
-  const int rc = render_frame_impl(s, P, stream, forced_chunk_log2, blocking);
+static int render_frame(rt_scene* s, RtDevParams& P, hipStream_t stream, uint32_t forced_chunk_log2, bool blocking = false,
+                        const RtRayArgs* rays = nullptr) {
+  const int rc = render_frame_impl(s, P, stream, forced_chunk_log2, blocking, rays);
   if (rc != RT_OK) s->ws[s->cur_ws].acc_pixels = 0;
   // marks the end of this frame's use of its counter block (prepare() of a later frame waits for it)
   if (hipEventRecord(s->frame_ev[s->cur_block], stream) == hipSuccess) s->frame_pending[s->cur_block] = true;
@@ -1201,6 +1213,37 @@ int rt_render(rt_scene* s, const rt_params* p, uint32_t* argb, const rt_aux* aux
 }
 
 }  // extern "C"
+
+// ---- ray batches (rt_trace_rays*, rt_rays.cpp): a frame of n x 1 "pixels" whose camera rays are the caller's ------------------
+// `p` is the caller's shading parameters with the camera members replaced (width n, height 1, no window, no ranks, no
+// anti-aliasing) and has been validated; `r` holds DEVICE pointers.  Uses the scene's tables, frame slots and workspaces as a
+// frame does.  Without secondary rays: one asynchronous launch.  With them: the chained schedule, resolved by
+// rt_resolve_kernel into r.rgb / r.argb (a plane of the library's when the caller has none), and verified at its end -- the
+// call waits for the batch's counters and runs it again with larger queues if a ray or a pair was dropped.
+int rt_trace_rays_enqueue(rt_scene* s, const rt_params* p, const RtRayArgs& r, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(s->device));
+  const bool secondary = (p->flags & (RT_FLAG_REFLECTIONS | RT_FLAG_REFRACTIONS)) != 0;
+  uint32_t* argb = r.argb;
+  if (secondary && !argb) {  // rt_resolve_kernel needs a target
+    RC_TRY(s->rays_argb.ensure((size_t)r.n * 4));
+    argb = (uint32_t*)s->rays_argb.p;
+  }
+  rt_aux aux{};
+  aux.rgb = r.rgb;
+  RtDevParams P;
+  RC_TRY(prepare(s, p, argb, &aux, stream, &P));
+  P.sup_list = nullptr, P.n_sup = (r.n + 255u) / 256u;  // (the work list: 256 rays per workgroup, in the caller's order)
+  // the resolve kernel only writes hits: a miss reads (0, 0, 0)
+  if (secondary && r.rgb) HIP_TRY(hipMemsetAsync(r.rgb, 0, (size_t)r.n * 12, stream));
+  return render_frame(s, P, stream, p->tuning.chunk_log2, false, &r);
+}
+
+void rt_scene_forget_stream(rt_scene* s, hipStream_t stream) {
+  if (s->tables_stream == stream) s->tables_stream = nullptr, s->tables_pending = false;
+  if (s->last_stream == stream) s->last_stream = nullptr;
+  for (int b = 0; b < RT_SLOTS; b++)
+    if (s->frame_stream[b] == stream) s->frame_stream[b] = nullptr, s->frame_pending[b] = false;
+}
 
 int rt_render_device_staged(rt_scene* s, const rt_params* p, uint32_t* out_dev, const uint32_t* stage_slot,
                             uint32_t tiles_x, hipStream_t stream) {

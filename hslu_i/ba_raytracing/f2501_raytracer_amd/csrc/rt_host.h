@@ -75,7 +75,8 @@ struct EventPair {  // destroyed on every return path
 // verified frame renders without a synchronisation
 struct StreamKey {
   uint32_t width, height, flags, aa_rays, aa_unique, light_mult, depth_refl, depth_refr, win[4], tile_size, n_ranks, rank, traversal,
-      cand_cap, cloud_seed, n_cloud_sets, forced, tables, staged, flags_on, n_sup, lanes, split, sort_bits, lists_on, merged;
+      cand_cap, cloud_seed, n_cloud_sets, forced, tables, staged, flags_on, n_sup, lanes, split, sort_bits, lists_on, merged,
+      rays;  // 1: a ray batch (rt_trace_rays*), 0: a camera frame
   float f[8];
 };
 
@@ -87,6 +88,7 @@ struct rt_scene {
   // per-render workspaces
   DevBuf aa, cloud, counters, fb, aux_rgb, aux_id, aux_t, suplist;
   DevBuf progress_fb;   // rt_render_begin: the device frame its bands are rendered into
+  DevBuf rays_argb;     // rt_trace_rays* with secondary rays and no argb plane of the caller's: rt_resolve_kernel's target
   bool progress_active = false;  // a progressive render (rt_render_begin .. rt_render_end) owns the scene
   uint64_t budget = 0;  // rt_scene_desc.device_budget_bytes as applied: bounds flags + per-cell lists
   size_t bytes_bvh = 0; // of `blob`: nodes + octant copies + threaded copy
@@ -188,6 +190,10 @@ struct rt_scene {
 int rt_render_device_staged(rt_scene* s, const rt_params* p, uint32_t* out_dev, const uint32_t* stage_slot,
                             uint32_t tiles_x, hipStream_t stream);
 int rt_validate_params(const rt_params* p);
+// a ray batch through the frame scheduler (rt_api.cpp; entry points and validation: rt_rays.cpp)
+int rt_trace_rays_enqueue(rt_scene* s, const rt_params* p, const RtRayArgs& r, hipStream_t stream);
+// `stream` has drained and is about to be destroyed: what the scene enqueued on it is done, and its handle must not be used again
+void rt_scene_forget_stream(rt_scene* s, hipStream_t stream);
 // the ray counters of the frame that used frame slot `slot` of the scene last (rt_scene::cur_block right after a frame
 // was enqueued); the caller has waited for that frame
 int rt_collect_stats_slot(rt_scene* s, int slot, rt_stats* st);

@@ -226,6 +226,22 @@ struct RtQueryArgs {
 int rt_launch_query_nearest(const RtDevScene& sc, const RtQueryArgs& q, void* stream);
 int rt_launch_query_any(const RtDevScene& sc, const RtQueryArgs& q, void* stream);
 
+// ---- radiance queries (rt_trace_rays*: csrc/rt_rays.h) ------------------------------------------------------------------
+// Third kernel argument of the two ray-source kernels, behind (RtDevScene, RtDevParams): the caller's rays and the output
+// planes (device pointers, nullptr = not written).  With secondary rays rgb and argb are written by rt_resolve_kernel
+// (RtDevParams::aux_rgb / argb) and are not read from here.
+struct RtRayArgs {
+  const float* origin;     // [n][3]
+  const float* direction;  // [n][3], any length
+  float* rgb;              // [n][3]
+  uint8_t* valid;          // [n]
+  int32_t* id;             // [n]
+  float* t;                // [n]
+  uint32_t* argb;          // [n], hits only
+  uint32_t n;
+};
+int rt_launch_rays(const RtDevScene& sc, const RtDevParams& p, const RtRayArgs& r, uint32_t n_wgs, void* stream);
+
 #define RT_QUEUE_QUADS 4u   // float4 per ray record
 #define RT_SORT_TILE 4096u  // buckets per workgroup of the offset scan
 #define RT_SORT_BITS_DEFAULT 22u

@@ -596,6 +596,7 @@ struct CfgGeneric {
   static constexpr int TABLES = CFG_TABLES_RUNTIME;  // FLAGS: recv_flags without cell_lists; LISTS: both; RUNTIME: as the pointers say
   static constexpr bool POW2_SETS = false;   // true: n_cloud_sets is a power of two
   static constexpr bool FEW_SPHERES = false; // true: n_spheres < 32
+  static constexpr bool FAR_ORIGINS = false; // true: rays may start far outside the scene (CfgRays)
 };
 template <uint32_t N_, int TABLES_>
 struct CfgSoft {
@@ -604,6 +605,16 @@ struct CfgSoft {
   static constexpr int TABLES = TABLES_;
   static constexpr bool POW2_SETS = true;
   static constexpr bool FEW_SPHERES = true;
+  static constexpr bool FAR_ORIGINS = false;
+};
+// Rays the CALLER supplies (rt_rays.h).  The receiver tables stand for hit points that lie ON their surface to within the
+// rounding of p = o + t d for a ray that starts in or near the scene (collect_light_candidates, COLLECT_FLAGS: 4e-7 |p|).  A
+// ray from far away carries the rounding of ITS magnitudes -- t = 167 puts p 1e-5 off a wall, as far as eps_distance pushes a
+// shadow ray -- and the reference then shadows the point by its own surface where the cell's flag says "clear".  So a lane
+// whose origin lies more than the scene's extent outside the scene's bounds takes no flag and no list: it collects its
+// candidates itself, which is exact for any p.
+struct CfgRays : CfgGeneric {
+  static constexpr bool FAR_ORIGINS = true;
 };
 // (The tests below are written where they stand as `C::X || run-time test` / `!C::X && run-time test` / `C::X ? constant : run-time
 // value`: the front end folds the constant side away, so CfgGeneric compiles to exactly what the run-time test alone compiles to.)
@@ -1621,7 +1632,13 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
   if (N > 1) {
     // receiver flags of the cell the hit point lies in (bit l: no triangle can shadow it for light l, bit 8 + l: no sphere)
     uint32_t rflags = 0u, cell = RT_NO_CELL;
-    if ((C::TABLES != CFG_TABLES_RUNTIME || P.recv_flags) && hit && h.id >= (int)sc.n_spheres) {
+    bool on_cell = hit;  // the hit point lies on its receiver cell as rt_flags_kernel assumed
+    if (C::FAR_ORIGINS) {
+      // (morton_lo / morton_scale: the scene's bounds as [0, 1024)^3; one extent more on every side)
+      const V3 q = (r.o - mk(P.morton_lo[0], P.morton_lo[1], P.morton_lo[2])) * mk(P.morton_scale[0], P.morton_scale[1], P.morton_scale[2]);
+      on_cell = hit && fminf(fminf(q.x, q.y), q.z) >= -1024.0f && fmaxf(fmaxf(q.x, q.y), q.z) <= 2048.0f;
+    }
+    if ((C::TABLES != CFG_TABLES_RUNTIME || P.recv_flags) && on_cell && h.id >= (int)sc.n_spheres) {
       const uint32_t ro = sc.off_recv + (uint32_t)(h.id - (int)sc.n_spheres) * 48u;
       const float4 ru = vload<float4>(sc, ro), rv = vload<float4>(sc, ro + 16u);
       const uint2 rr = vload<uint2>(sc, ro + 32u);  // {R, first cell}
@@ -1632,7 +1649,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       // (cells beyond the hypotenuse carry no flags; the cells are computed 5 % larger than they are, which covers the
       // rounding of u and v)
       if (rr.x != 0u && ci + cj < rr.x) cell = rr.y + ci + rr.x * cj, rflags = P.recv_flags[cell];
-    } else if ((C::TABLES != CFG_TABLES_RUNTIME || P.recv_flags) && hit && h.id >= 0) {
+    } else if ((C::TABLES != CFG_TABLES_RUNTIME || P.recv_flags) && on_cell && h.id >= 0) {
       // a sphere: the cell of the direction centre -> p in the sphere's cube map (face = largest component)
       const uint2 sr = vload<uint2>(sc, sc.off_srecv + (uint32_t)h.id * 8u);  // {Rs, first cell}
       const float4 sp = vload<float4>(sc, sc.off_spheres + (uint32_t)h.id * 16u);
@@ -3036,6 +3053,7 @@ __global__ __launch_bounds__(256) void rt_selftest_math_kernel(const float* in, 
 
 #include "rt_phases.h"
 #include "rt_query.h"
+#include "rt_rays.h"
 
 }  // namespace
 
@@ -3185,6 +3203,16 @@ int rt_launch_query_nearest(const RtDevScene& sc, const RtQueryArgs& q, void* st
 int rt_launch_query_any(const RtDevScene& sc, const RtQueryArgs& q, void* stream) {
   if (q.n == 0) return 0;
   hipLaunchKernelGGL(rt_query_any_kernel, dim3(query_wgs(q.n)), dim3(256), 0, (hipStream_t)stream, sc, q);
+  return (int)hipGetLastError();
+}
+
+// radiance queries (rt_rays.h): workgroup b of the launch holds rays 256 rt_batch_wg(p, b) .. + 255 of the batch
+int rt_launch_rays(const RtDevScene& sc, const RtDevParams& p, const RtRayArgs& r, uint32_t n_wgs, void* stream) {
+  if (n_wgs == 0) return 0;
+  if (p.acc)
+    hipLaunchKernelGGL(rt_rays_stream_kernel, dim3(n_wgs), dim3(256), 0, (hipStream_t)stream, sc, p, r);
+  else
+    hipLaunchKernelGGL(rt_rays_kernel, dim3(n_wgs), dim3(256), 0, (hipStream_t)stream, sc, p, r);
   return (int)hipGetLastError();
 }
 

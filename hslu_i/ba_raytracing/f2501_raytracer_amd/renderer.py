@@ -62,6 +62,15 @@ class IntersectionTest(NamedTuple):
     color_filter: Any
 
 
+class Radiance(NamedTuple):
+    """`single_raytrace` per ray (raytracer_renderer.rs:147-264): linear RGB ((0, 0, 0) on a miss), its valid mask, and the
+    primary hit's canonical object id (-1 = miss) and distance (+inf on a miss)."""
+    rgb: Any
+    valid: Any
+    id: Any
+    t: Any
+
+
 class DeviceScene:
     """Owns an `rt_scene*` (device copies + BVH)."""
 
@@ -74,6 +83,8 @@ class DeviceScene:
         self._h = h
         self.device = int(device)
         self.flat = keep
+        self.last_trace_stats: Optional[Dict] = None  # rt_stats of the last trace_rays call on host arrays
+        self._trace_params = None  # (key, rt_params, keepalive) of the last trace_rays call
 
     @property
     def handle(self) -> C.c_void_p:
@@ -142,7 +153,51 @@ class DeviceScene:
             _lib.check(lib.rt_any_intersection(self.handle, C.byref(b), C.byref(oc)))
         return out
 
-    # (bool arrays and tensors hold one byte per element, 0 or 1: the uint8 planes of rt_ray_occlusion)
+    def trace_rays(self, origins, directions, cfg: RenderConfig, tuning: Optional[Dict] = None, traversal: int = _abi.RT_TRAVERSAL_BVH,
+                   argb=None) -> "Radiance":
+        """`single_raytrace` (raytracer_renderer.rs:147-264) for a batch of rays: the colour the render gives a pixel whose
+        camera ray is that ray, shaded with `cfg` (soft shadows, reflections, refractions, backface culling, depths; its
+        camera and anti-aliasing are not used: the caller supplies its samples as rays).  Ray i takes the light-cloud set
+        of pixel i.  Same input kinds as cast_rays: numpy arrays (host entry point, numpy results, `last_trace_stats` is
+        filled) or torch tensors on this scene's device (the _device entry point on torch.cuda.current_stream(); tensor
+        results).  argb: optional uint32 array / int32 tensor of n packed pixels; hits are written, misses keep their
+        value.  One radiance or render call per scene at a time."""
+        torch_in, n, o, d, _ = self._batch(origins, directions, None)
+        if cfg.has("anti_aliasing"):
+            cfg = RenderConfig(**{**cfg.__dict__, "features": cfg.features - {"anti_aliasing"}})
+        # (the parameters of the last configuration are kept: building the light-cloud table is the expensive part of a call)
+        key = (cfg, int(traversal), tuple(sorted((tuning or {}).items())))
+        if self._trace_params is None or self._trace_params[0] != key:
+            self._trace_params = (key,) + _abi.make_params(cfg, traversal=traversal, tuning=tuning)
+        p = self._trace_params[1]
+        if torch_in:
+            import torch
+
+            dev = o.device
+            out = Radiance(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.bool, device=dev),
+                           torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+            if argb is not None and not (isinstance(argb, torch.Tensor) and argb.dtype == torch.int32 and argb.device == dev and
+                                         tuple(argb.shape) == (n,) and argb.is_contiguous()):
+                raise ValueError(f"argb must be a contiguous int32 tensor of shape ({n},) on {dev}")
+            ptr = lambda a: a.data_ptr()  # noqa: E731
+        else:
+            out = Radiance(np.empty((n, 3), np.float32), np.empty(n, np.bool_), np.empty(n, np.int32), np.empty(n, np.float32))
+            if argb is not None and not (isinstance(argb, np.ndarray) and argb.dtype == np.uint32 and argb.shape == (n,) and
+                                         argb.flags["C_CONTIGUOUS"]):
+                raise ValueError(f"argb must be a contiguous uint32 array of shape ({n},)")
+            ptr = lambda a: a.ctypes.data  # noqa: E731
+        b = self._batch_struct(n, o, d, None, False, ptr)
+        r = _abi.rt_ray_radiance(ptr(out.rgb), ptr(out.valid), ptr(out.id), ptr(out.t), ptr(argb) if argb is not None else None)
+        lib = _lib.load()
+        if torch_in:
+            _lib.check(lib.rt_trace_rays_device(self.handle, C.byref(p), C.byref(b), C.byref(r), self._stream_of(o)))
+        else:
+            st = _abi.rt_stats()
+            _lib.check(lib.rt_trace_rays(self.handle, C.byref(p), C.byref(b), C.byref(r), C.byref(st)))
+            self.last_trace_stats = st.as_dict()
+        return out
+
+    # (bool arrays and tensors hold one byte per element, 0 or 1: the uint8 planes of rt_ray_occlusion / rt_ray_radiance)
 
     def _batch(self, origins, directions, max_distance):
         """-> (torch?, n, origins, directions, max_distance) validated and contiguous."""
@@ -267,6 +322,19 @@ class RaytracerRenderer:
         _lib.check(lib.rt_render(ds.handle, C.byref(p), buffer.buffer.ctypes.data, C.byref(a) if aux else None, C.byref(st)))
         self.last_stats = st.as_dict()
         return planes
+
+    def render_camera(self, buffer: ImageBuffer, scene, camera, tuning: Optional[Dict] = None) -> Radiance:
+        """Renders `scene` as `camera` sees it (anything with width, height and rays() -> (origins, directions), row-major
+        with row 0 at the top: camera.PinholeCamera) into `buffer`: the rays go through DeviceScene.trace_rays with this
+        renderer's configuration, hit pixels are written, misses keep the buffer's fill.  One ray per pixel -- the
+        configuration's anti-aliasing belongs to the reference's own view and is not applied.  Returns the Radiance planes."""
+        if buffer.width != camera.width or buffer.height != camera.height:
+            raise ValueError(f"buffer is {buffer.width}x{buffer.height}, the camera renders {camera.width}x{camera.height}")
+        ds = self.device_scene(scene)
+        o, d = camera.rays()
+        out = ds.trace_rays(o, d, self.cfg, tuning=tuning, traversal=self.traversal, argb=buffer.buffer)
+        self.last_stats = ds.last_trace_stats
+        return out
 
     def render_progressive(self, buffer: ImageBuffer, scene, on_tiles=None, rows_per_step: Optional[int] = None, poll_s: float = 0.0002,
                            tuning: Optional[Dict] = None):

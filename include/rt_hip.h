@@ -29,6 +29,10 @@
  *   rt_any_intersection          <- Raytracer::has_any_intersection, raytracer.rs:24-106 (IntersectionTest,
  *                                   raytracer.rs:17-22), for a batch of HOST segments; blocks
  *   rt_any_intersection_device   <- same, DEVICE arrays, enqueued on the caller's stream
+ *   rt_trace_rays     <- RaytracerRenderer::single_raytrace, src/renderer/raytracer_renderer.rs:147-264 (the colour of
+ *                        a ray: nearest hit, the lights' shadow and transmittance rays, soft-shadow clouds, attenuation,
+ *                        reflection and refraction trees), for a batch of HOST rays; blocks
+ *   rt_trace_rays_device         <- same, DEVICE arrays, enqueued on the caller's stream
  *   rt_last_error     <- (reference panics: `unwrap()/expect()`); here: error codes + message
  *
  * All arithmetic on the path is fp32.  Hit ids are canonical object indices: spheres first
@@ -447,6 +451,58 @@ int rt_any_intersection(rt_scene* scene, const rt_ray_batch* batch, const rt_ray
  * nothing and returns once the work is enqueued. */
 int rt_cast_rays_device(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_hits* hits, void* hip_stream);
 int rt_any_intersection_device(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_occlusion* out, void* hip_stream);
+
+/* ---- radiance queries: Whitted shading of caller-supplied rays -------------------------------------------------------------
+ *
+ * The colour of each ray, as the render computes it for its camera rays:
+ *   single_raytrace(origin, direction, air_ior, objects, lights, depth None).0 -- raytracer_renderer.rs:147-264.
+ * Ray i plays the role of pixel i wherever the render uses the pixel index: its light-cloud set is
+ * rt_cloud_hash(cloud_seed, i, light) % n_cloud_sets.  Its weight is 1: the result is what a frame without anti-aliasing writes
+ * to rt_aux.rgb for a pixel whose camera ray is that ray.  Dead rays follow the query rule above (a miss; not counted).
+ *
+ * `batch`: rt_ray_batch as above; max_distance must be NULL and flags 0 (culling comes from shading->flags).
+ * `shading`: an rt_params of which fw, fh, fd, eps_distance, air_ior, ambient, flags, light_mult, cloud_seed, n_cloud_sets,
+ * cloud_sets, max_depth_*, traversal and tuning are read.  flags may carry REFLECTIONS, REFRACTIONS and BACKFACE_CULLING;
+ * RT_FLAG_ANTI_ALIASING is refused (the caller supplies its samples as rays).  The camera members (width, height, focus,
+ * aa_*, win_*, tile_size, n_ranks, rank) are ignored: a caller can pass the params it renders with, minus the AA bit.
+ * tuning.levels, tuning.phases, tuning.tile_order and tuning.no_aa_dedup are ignored too: a batch with secondary rays always
+ * runs the chained level schedule with fused phases (the other forms derive the camera ray from the work-item index).
+ *
+ * Order matters for speed, not for the result: the walks are wave-cooperative (64 consecutive rays share one), so
+ * neighbouring rays of a batch should be neighbours in space.  The library does not reorder the caller's rays.
+ *
+ * rt_stats (host form; device form: rt_render_collect_stats after synchronising): rays_primary = live rays,
+ * rays_reflection / rays_refraction / rays_shadow as the reference casts them, pixels_written = valid rays, rays_traced =
+ * the sum of the three ray kinds (nothing is deduplicated).
+ *
+ * Validation (RT_ERR_INVALID_ARG + rt_last_error, before any HIP call): NULL scene, shading, batch or output struct; wrong
+ * abi_version in either struct; max_distance or batch flags set; RT_FLAG_ANTI_ALIASING; NULL origin / direction with
+ * n_rays > 0; every output plane NULL; and what rt_render rejects in an rt_params (clouds, depths, tuning ranges, secondary
+ * flags with depth 0).  At most 2^31 - 1 rays.  n_rays == 0 is a valid no-op.
+ *
+ * A radiance call is a RENDER call: it uses the scene's parameter tables, frame slots and workspaces.  One such call per
+ * scene at a time, as for rt_render; refused while rt_render_begin owns the scene.
+ * Blocking: without REFLECTIONS / REFRACTIONS rt_trace_rays_device is ONE asynchronous kernel launch and allocates nothing
+ * (a changed light-cloud table is uploaded first, as by rt_render_device).  With them it enqueues the chained levels and
+ * then BLOCKS until the batch is through: ray counts do not repeat from batch to batch as they do from frame to frame, so
+ * every batch is verified -- its counters are read back, and if a ray or pair queue dropped anything the queues grow and
+ * the batch runs again (rt_stats.queue_bytes shows the growth).  It allocates the accumulator (32 bytes per ray), the
+ * queues, and an argb plane of its own when the caller gives none.  A camera frame that follows a batch verifies its queue
+ * sizes afresh. */
+typedef struct rt_ray_radiance {
+  float* rgb;     /* [n][3] un-quantised linear RGB; (0,0,0) on a miss */
+  uint8_t* valid; /* [n] 1 = the ray hit something (single_raytrace's valid mask) */
+  int32_t* id;    /* [n] canonical object index of the primary hit, -1 on a miss */
+  float* t;       /* [n] its distance, +inf on a miss (as rt_ray_hits.t) */
+  uint32_t* argb; /* [n] packed 0xFFRRGGBB (OutputColorEncoder::to_output); UNTOUCHED on a miss, as rt_render */
+} rt_ray_radiance; /* every member nullable, at least one non-NULL */
+
+/* HOST arrays: staged through one device allocation made for the call, on a stream of its own; returns when the results
+ * are in host memory.  stats may be NULL. */
+int rt_trace_rays(rt_scene* scene, const rt_params* shading, const rt_ray_batch* batch, const rt_ray_radiance* out, rt_stats* stats);
+/* DEVICE arrays on the scene's device, enqueued on `hip_stream` (a hipStream_t, NULL = default stream). */
+int rt_trace_rays_device(rt_scene* scene, const rt_params* shading, const rt_ray_batch* batch, const rt_ray_radiance* out,
+                         void* hip_stream);
 
 /* thread-local message for the last non-RT_OK return on this thread */
 const char* rt_last_error(void);

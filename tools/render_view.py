@@ -1,0 +1,49 @@
+#!/usr/bin/env python3
+"""Renders semesterbild on GPU 0 from a viewpoint of the caller's choosing (the reference has one, fixed at compile
+time) and writes a PNG: camera.PinholeCamera -> RaytracerRenderer.render_camera -> rt_trace_rays.
+
+    render_view.py OUT.png [--eye X,Y,Z] [--target X,Y,Z] [--fov DEG] [--size WxH] [--features f,g] [--model text|text_lowres]
+
+eye / target are in units of the scene's width, height and depth (the reference's own focus is 0.5,0.5,-1.9; image y points
+down, so the camera's up vector is (0, -1, 0))."""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from PIL import Image  # noqa: E402
+
+from hslu_i.ba_raytracing.f2501_raytracer_amd import RenderConfig, camera, scenes  # noqa: E402
+from hslu_i.ba_raytracing.f2501_raytracer_amd.renderer import ImageBuffer, RaytracerRenderer  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out")
+    ap.add_argument("--eye", default="-0.45,0.25,-1.1")
+    ap.add_argument("--target", default="0.5,0.5,0.6")
+    ap.add_argument("--fov", type=float, default=38.0)
+    ap.add_argument("--size", default="1280x960")
+    ap.add_argument("--features", default="soft_shadows,realistic")
+    ap.add_argument("--model", default="text")
+    ap.add_argument("--fill", default="0xFF101010")
+    args = ap.parse_args()
+    cfg = RenderConfig.from_features([f for f in args.features.split(",") if f])
+    scale = (float(cfg.scene_width), float(cfg.scene_height), float(cfg.scene_depth))
+    eye = [float(v) * s for v, s in zip(args.eye.split(","), scale)]
+    target = [float(v) * s for v, s in zip(args.target.split(","), scale)]
+    w, h = (int(v) for v in args.size.split("x"))
+    cam = camera.PinholeCamera(eye, target, (0.0, -1.0, 0.0), args.fov, w, h)
+    scene = scenes.semesterbild(cfg, args.model)
+    buf = ImageBuffer.new_with_color(w, h, int(args.fill, 0))
+    r = RaytracerRenderer(cfg)
+    t = time.time()
+    out = r.render_camera(buf, scene, cam)
+    print(f"semesterbild {w}x{h} from eye={eye} features={sorted(cfg.features)} valid={float(out.valid.mean()):.3f} "
+          f"wall={time.time() - t:.3f}s stats={r.last_stats}")
+    Image.fromarray(buf.as_rgb8()).save(args.out)
+
+
+if __name__ == "__main__":
+    main()
