@@ -133,6 +133,30 @@ class rt_ray_radiance(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("valid", C.c_void_p), ("id", C.c_void_p), ("t", C.c_void_p), ("argb", C.c_void_p)]
 
 
+class rt_scene_delta(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("sphere_center", C.c_void_p), ("sphere_r_sq", C.c_void_p), ("sphere_r_inv", C.c_void_p),
+        ("tri_first", C.c_uint32), ("tri_count", C.c_uint32),
+        ("tri_v1", C.c_void_p), ("tri_e1", C.c_void_p), ("tri_e2", C.c_void_p), ("tri_normal", C.c_void_p),
+        ("materials", C.c_void_p), ("lights", C.c_void_p),
+    ]
+
+
+RT_UPDATE_INVALIDATES_RECEIVER_TABLES, RT_UPDATE_INVALIDATES_TILE_COSTS, RT_UPDATE_INVALIDATES_QUEUE_SIZES = 1, 2, 4
+
+
+class rt_update_info(C.Structure):
+    _fields_ = [
+        ("device_ms", C.c_double), ("total_ms", C.c_double),
+        ("nodes_refitted", C.c_uint32), ("slots_rewritten", C.c_uint32), ("receivers_disabled", C.c_uint32),
+        ("tables_invalidated", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def fptr(a: np.ndarray):
     assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(_fp)
@@ -216,3 +240,66 @@ def make_params(cfg, aa_offsets=None, cloud=None, window=None, n_ranks=1, rank=0
     for k, v in (tuning or {}).items():
         setattr(p.tuning, k, int(v))
     return p, keep
+
+
+SPHERE_GROUP = ("sphere_center", "sphere_r_sq", "sphere_r_inv")
+TRIANGLE_GROUP = ("tri_v1", "tri_e1", "tri_e2", "tri_normal")
+
+
+def scene_delta_groups(old, new, full=False):
+    """What differs between two contiguous FlatScenes of the same shape, as the groups of an rt_scene_delta:
+    {"spheres": bool, "triangles": (first, count) or None, "materials": bool, "lights": bool}.  Arrays are compared as
+    bits (a NaN equals itself, -0 differs from +0).  full: every group the scene has objects for, changed or not.
+    Raises ValueError when a count or the object -> material assignment differs: an update cannot express that."""
+    for name in SPHERE_GROUP + TRIANGLE_GROUP + ("sphere_material", "tri_material", "materials", "lights"):
+        if getattr(old, name).shape != getattr(new, name).shape:
+            raise ValueError(f"{name}: shape {getattr(new, name).shape} differs from the scene's {getattr(old, name).shape}; "
+                             "an update keeps every count (create a new device scene)")
+    for name in ("sphere_material", "tri_material"):
+        if not np.array_equal(getattr(old, name), getattr(new, name)):
+            raise ValueError(f"{name} differs: an update keeps the object -> material assignment (create a new device scene)")
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)  # noqa: E731
+    differs = lambda name: not np.array_equal(bits(getattr(old, name)), bits(getattr(new, name)))  # noqa: E731
+    tri = None
+    if new.n_triangles:
+        rows = np.zeros(new.n_triangles, bool)
+        for name in TRIANGLE_GROUP:
+            rows |= (bits(getattr(old, name)) != bits(getattr(new, name))).reshape(new.n_triangles, -1).any(1)
+        if full:
+            tri = (0, new.n_triangles)
+        elif rows.any():
+            idx = np.flatnonzero(rows)
+            tri = (int(idx[0]), int(idx[-1]) - int(idx[0]) + 1)
+    return {"spheres": bool(new.n_spheres) and (full or any(differs(n) for n in SPHERE_GROUP)), "triangles": tri,
+            "materials": bool(new.materials.shape[0]) and (full or differs("materials")),
+            "lights": bool(new.lights.shape[0]) and (full or differs("lights"))}
+
+
+def make_scene_delta(new, groups, ptr=None):
+    """rt_scene_delta carrying `groups` (scene_delta_groups) of `new`: a contiguous FlatScene (host arrays; the triangle
+    range is cut out of its arrays), or any object with the same attributes whose arrays `ptr` turns into addresses (device
+    tensors; its triangle arrays ARE the range).  Returns (delta, keepalive)."""
+    if ptr is None:
+        ptr = lambda a: a.ctypes.data  # noqa: E731
+    d = rt_scene_delta()
+    d.abi_version = RT_ABI_VERSION
+    keep = []
+
+    def put(field, a):
+        keep.append(a)
+        setattr(d, field, ptr(a))
+
+    if groups["spheres"]:
+        for name in SPHERE_GROUP:
+            put(name, getattr(new, name))
+    if groups["triangles"]:
+        first, count = groups["triangles"]
+        d.tri_first, d.tri_count = first, count
+        for name in TRIANGLE_GROUP:
+            a = getattr(new, name)
+            put(name, np.ascontiguousarray(a[first:first + count]) if isinstance(a, np.ndarray) else a)
+    if groups["materials"]:
+        put("materials", new.materials)
+    if groups["lights"]:
+        put("lights", new.lights)
+    return d, keep

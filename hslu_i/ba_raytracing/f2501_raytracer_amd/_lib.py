@@ -5,8 +5,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_radiance, rt_scene_desc,
-                   rt_scene_info, rt_stats)
+from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_radiance, rt_scene_delta,
+                   rt_scene_desc, rt_scene_info, rt_stats, rt_update_info)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_HIP_LIB selects a diagnostic build of the same library (tools/, A/B timing); default: in-tree
@@ -17,7 +17,7 @@ EXPORTS = (
     "rt_gather_layout", "rt_render_multi", "rt_render_multi_begin", "rt_render_multi_end", "rt_multi_release", "rt_comm_unique_id", "rt_comm_create", "rt_comm_destroy",
     "rt_render_gather_device", "rt_comm_last_gather", "rt_render_begin", "rt_render_poll", "rt_render_end",
     "rt_cast_rays", "rt_cast_rays_device", "rt_any_intersection", "rt_any_intersection_device",
-    "rt_trace_rays", "rt_trace_rays_device",
+    "rt_trace_rays", "rt_trace_rays_device", "rt_scene_update", "rt_scene_update_device",
 )
 
 _lib = None
@@ -93,6 +93,10 @@ def load():
     lib.rt_trace_rays.argtypes = [C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_ray_batch), C.POINTER(rt_ray_radiance), C.POINTER(rt_stats)]
     lib.rt_trace_rays_device.restype = C.c_int
     lib.rt_trace_rays_device.argtypes = [C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_ray_batch), C.POINTER(rt_ray_radiance), C.c_void_p]
+    lib.rt_scene_update.restype = C.c_int
+    lib.rt_scene_update.argtypes = [C.c_void_p, C.POINTER(rt_scene_delta), C.POINTER(rt_update_info)]
+    lib.rt_scene_update_device.restype = C.c_int
+    lib.rt_scene_update_device.argtypes = [C.c_void_p, C.POINTER(rt_scene_delta), C.c_void_p, C.POINTER(rt_update_info)]
     _lib = lib
     return lib
 

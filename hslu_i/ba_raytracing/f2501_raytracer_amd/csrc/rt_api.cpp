@@ -82,6 +82,7 @@ void rt_scene_destroy(rt_scene* s) {
   }
   for (DevBuf* b : {&s->blob, &s->aa, &s->cloud, &s->counters, &s->suplist, &s->fb, &s->aux_rgb, &s->costmap, &s->aux_id, &s->aux_t, &s->flag_geo, &s->flags, &s->cell_lists, &s->progress_fb, &s->rays_argb})
     b->release();
+  rt_scene_release_update(s);
   delete s;
 }
 
@@ -117,6 +118,7 @@ int rt_scene_create(const rt_scene_desc* d, int device, rt_scene** out) {
   }
   if (rc == RT_OK) rc = s->counters.ensure(RT_SLOTS * RT_COUNTER_REPLICAS * 16 * sizeof(unsigned long long));
   if (rc == RT_OK) rc = upload(s->blob, pk.blob.data(), pk.blob.size());
+  if (rc == RT_OK) rc = rt_scene_upload_plan(s, pk);  // (in-place updates: rt_update.cpp)
   if (rc != RT_OK) {
     rt_scene_destroy(s);
     return rc;

@@ -181,8 +181,20 @@ struct rt_scene {
   // which fast paths the last frame did NOT take (rt_stats.notes)
   uint32_t notes = 0;
   size_t queue_bytes = 0;  // ray queues + hard-pair queue + sort workspace of the last frame with secondary rays
+  // in-place updates (rt_update.cpp): the refit plan and its device copy (parts at plan_off[]: height_nodes, thr_src,
+  // recv_cell, tri_slot, 8 words of results), the staging of a host delta (pinned, device) and the pinned read-back
+  RtRefitPlan plan;
+  DevBuf plan_dev, upd_dev;
+  size_t plan_off[5] = {0, 0, 0, 0, 0};
+  void* upd_stage = nullptr;
+  size_t upd_stage_cap = 0;
+  float* upd_back = nullptr;
 };
 
+
+// rt_update.cpp: the device copy of pk.plan (rt_scene_create) and the release of everything an update allocated (rt_scene_destroy)
+int rt_scene_upload_plan(rt_scene* s, const RtPackedScene& pk);
+void rt_scene_release_update(rt_scene* s);
 
 // rt_api.cpp internals used by the multi-GPU path
 // Multi-GPU staging: when `stage_slot` (device, [tiles_x * tiles_y]) is given, packed pixels are stored into the

@@ -242,6 +242,22 @@ struct RtRayArgs {
 };
 int rt_launch_rays(const RtDevScene& sc, const RtDevParams& p, const RtRayArgs& r, uint32_t n_wgs, void* stream);
 
+// ---- in-place scene updates (rt_scene_update*: csrc/rt_update.hip, arithmetic in rt_refit.h) --------------------------------
+// What the update kernels get besides RtDevScene and the delta's arrays: the writable blob and the device copy of the
+// refit plan (RtRefitPlan, rt_scene_pack.h).
+struct RtUpdateArgs {
+  char* base;                     // the scene's blob, writable
+  float* flag_geo;                // input of rt_flags_kernel (nullptr: the scene has no receiver cells)
+  const uint32_t* height_nodes;   // device: node indices by height
+  const uint32_t* thr_src;        // device: per threaded entry, node * 2 + child
+  const uint32_t* recv_cell;      // device: per triangle {R, first cell} of creation
+  const uint32_t* tri_slot;       // device: per triangle its first leaf slot
+  float* bounds;                  // device, 8 words: scene bounds lo, hi; bits(receivers disabled); 0
+  const uint32_t* height_offset;  // HOST: [n_heights + 1] offsets into height_nodes
+  uint32_t n_heights, n_materials;
+};
+int rt_launch_update(const RtDevScene& sc, const RtUpdateArgs& u, const rt_scene_delta& d, void* stream, uint32_t* n_launches);
+
 #define RT_QUEUE_QUADS 4u   // float4 per ray record
 #define RT_SORT_TILE 4096u  // buckets per workgroup of the offset scan
 #define RT_SORT_BITS_DEFAULT 22u

@@ -3,12 +3,14 @@
 // order of the blob.  Also rt_fail / rt_last_error, so that host-only code links without rt_api.cpp.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
 
+#include "rt_refit.h"
 #include "rt_scene_pack.h"
 
 static thread_local std::string g_err;
@@ -273,8 +275,10 @@ static void pack_threaded_nodes(const RtBvh& bvh, RtPackedScene* o) {
   struct Emit {
     const std::vector<RtNode>& nodes;
     std::vector<RtThrNode>& out;
-    void child(const float* lo, const float* hi, uint32_t c, uint32_t n) {
+    std::vector<uint32_t>& src;  // RtRefitPlan::thr_src
+    void child(uint32_t from, const float* lo, const float* hi, uint32_t c, uint32_t n) {
       if (c == RT_NODE_EMPTY) return;
+      src.push_back(from);
       const size_t idx = out.size();
       RtThrNode t;
       memcpy(t.lo, lo, 12), memcpy(t.hi, hi, 12);
@@ -286,10 +290,10 @@ static void pack_threaded_nodes(const RtBvh& bvh, RtPackedScene* o) {
     }
     void node(uint32_t i) {
       const RtNode nd = nodes[i];
-      child(nd.lo0, nd.hi0, nd.c0, nd.n0);
-      child(nd.lo1, nd.hi1, nd.c1, nd.n1);
+      child(2 * i, nd.lo0, nd.hi0, nd.c0, nd.n0);
+      child(2 * i + 1, nd.lo1, nd.hi1, nd.c1, nd.n1);
     }
-  } emit{bvh.nodes, thr};
+  } emit{bvh.nodes, thr, o->plan.thr_src};
   if (!bvh.nodes.empty()) emit.node(0);
   o->dev.n_thr = (uint32_t)thr.size();
   put(o->blob, &o->dev.off_nodes_thr, thr.data(), thr.size() * sizeof(RtThrNode));
@@ -328,6 +332,94 @@ static void pack_lights(const rt_scene_desc* d, RtPackedScene* o) {
   put(o->blob, &o->dev.off_lights, l.data(), l.size() * 4);
 }
 
+// what an update needs to know of the tree and of the decisions of creation (RtRefitPlan)
+static void make_refit_plan(const rt_scene_desc* d, const RtBvh& bvh, const std::vector<uint8_t>& no_split, RtPackedScene* o) {
+  RtRefitPlan& pl = o->plan;
+  const uint32_t nn = (uint32_t)bvh.nodes.size(), nt = d->n_triangles;
+  // heights: a child's index is larger than its parent's (the builder reserves a node before it recurses)
+  std::vector<uint32_t> height(nn, 0);
+  uint32_t top = 0;
+  for (uint32_t i = nn; i-- > 0;) {
+    const RtNode& nd = bvh.nodes[i];
+    if (nd.c0 != RT_NODE_EMPTY && !nd.n0) height[i] = std::max(height[i], height[nd.c0] + 1u);
+    if (nd.c1 != RT_NODE_EMPTY && !nd.n1) height[i] = std::max(height[i], height[nd.c1] + 1u);
+    top = std::max(top, height[i]);
+  }
+  pl.height_offset.assign(top + 2u, 0u);
+  for (uint32_t i = 0; i < nn; i++) pl.height_offset[height[i] + 1]++;
+  for (uint32_t h = 0; h <= top; h++) pl.height_offset[h + 1] += pl.height_offset[h];
+  pl.height_nodes.resize(nn);
+  std::vector<uint32_t> at(pl.height_offset.begin(), pl.height_offset.end() - 1);
+  for (uint32_t i = 0; i < nn; i++) pl.height_nodes[at[height[i]]++] = i;
+  const uint32_t* recv = (const uint32_t*)(o->blob.data() + o->dev.off_recv);
+  pl.recv_cell.resize(2 * (size_t)nt);
+  for (uint32_t t = 0; t < nt; t++) pl.recv_cell[2 * (size_t)t] = recv[12 * (size_t)t + 8], pl.recv_cell[2 * (size_t)t + 1] = recv[12 * (size_t)t + 9];
+  pl.tri_slot.assign(nt, 0u);
+  for (uint32_t slot = (uint32_t)bvh.tri_order.size(); slot-- > 0;) pl.tri_slot[bvh.tri_order[slot] & ~RT_TRI_DUPLICATE] = slot;
+  pl.mat_class.assign(d->n_materials, 0);
+  for (uint32_t t = 0; t < nt; t++) pl.mat_class[d->tri_material[t]] = (uint8_t)(2u | (no_split[t] ? 1u : 0u));
+}
+
+int rt_check_scene_delta(const RtDevScene& dev, const RtRefitPlan& plan, const rt_scene_delta* d, const float* materials_host) {
+  if (!d) return rt_fail(RT_ERR_INVALID_ARG, "null argument");
+  if (d->abi_version != RT_ABI_VERSION)
+    return rt_fail(RT_ERR_INVALID_ARG, "rt_scene_delta.abi_version %u != %u", d->abi_version, RT_ABI_VERSION);
+  const int n_sph = (d->sphere_center != nullptr) + (d->sphere_r_sq != nullptr) + (d->sphere_r_inv != nullptr);
+  if (n_sph != 0 && n_sph != 3)
+    return rt_fail(RT_ERR_INVALID_ARG, "rt_scene_delta: sphere_center, sphere_r_sq and sphere_r_inv are given together or not at all");
+  const int n_tri = (d->tri_v1 != nullptr) + (d->tri_e1 != nullptr) + (d->tri_e2 != nullptr) + (d->tri_normal != nullptr);
+  if ((n_tri != 0 && n_tri != 4) || (n_tri == 4) != (d->tri_count != 0))
+    return rt_fail(RT_ERR_INVALID_ARG, "rt_scene_delta: tri_v1, tri_e1, tri_e2, tri_normal and a tri_count > 0 are given together or not at all");
+  if ((uint64_t)d->tri_first + d->tri_count > dev.n_triangles)
+    return rt_fail(RT_ERR_INVALID_ARG, "rt_scene_delta: tri_first %u + tri_count %u > n_triangles %u", d->tri_first, d->tri_count, dev.n_triangles);
+  if (!n_sph && !n_tri && !d->materials && !d->lights) return rt_fail(RT_ERR_INVALID_ARG, "rt_scene_delta changes nothing: every group is NULL");
+  if (n_tri && dev.n_slots > dev.n_triangles)
+    return rt_fail(RT_ERR_UNSUPPORTED, "rt_scene_delta.tri_*: the tree was built with split clipping (%u references of %u triangles); "
+                   "clipped boxes cannot be refitted", dev.n_slots, dev.n_triangles);
+  if (d->materials && materials_host)
+    for (size_t m = 0; m < plan.mat_class.size(); m++)
+      if ((plan.mat_class[m] & 2u) && rt_material_transmissive(materials_host + m * RT_MATERIAL_STRIDE) != ((plan.mat_class[m] & 1u) != 0))
+        return rt_fail(RT_ERR_INVALID_ARG, "rt_scene_delta.materials: row %zu changes its transmissive class (has_opacity, opacity) "
+                       "while triangles use it", m);
+  return RT_OK;
+}
+
+int rt_refit_packed(RtPackedScene* pk, const rt_scene_delta* d) {
+  if (!pk) return rt_fail(RT_ERR_INVALID_ARG, "null argument");
+  const int rc = rt_check_scene_delta(pk->dev, pk->plan, d, d ? d->materials : nullptr);
+  if (rc != RT_OK) return rc;
+  const RtDevScene& sc = pk->dev;
+  const RtRefitPlan& pl = pk->plan;
+  char* base = (char*)pk->blob.data();
+  if (d->sphere_center)
+    for (uint32_t i = 0; i < sc.n_spheres; i++) rt_upd_sphere(sc, base, i, d->sphere_center, d->sphere_r_sq);
+  if (d->tri_count) {
+    const RtTriDelta td{d->tri_first, d->tri_count, d->tri_v1, d->tri_e1, d->tri_e2, d->tri_normal};
+    for (uint32_t slot = 0; slot < sc.n_slots; slot++) rt_upd_slot(sc, base, slot, td);
+    float* geo = pk->flag_geo.empty() ? nullptr : pk->flag_geo.data();
+    for (uint32_t k = 0; k < td.count; k++) rt_upd_tri(sc, base, geo, k, td);
+    for (uint32_t i : pl.height_nodes) rt_upd_node(sc, base, i);  // (by height: children before parents)
+    for (uint32_t oc = 0; oc < 8; oc++)
+      for (uint32_t i = 0; i < sc.n_nodes; i++) rt_upd_octant(sc, base, oc, i);
+    for (uint32_t i = 0; i < sc.n_thr; i++) rt_upd_thr(sc, base, pl.thr_src.data(), i);
+  }
+  if (d->sphere_center || d->tri_count) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, b[6];
+    for (uint32_t i = 0; i < sc.n_spheres; i++) rt_bounds_sphere(sc, base, i, lo, hi);
+    for (uint32_t s = 0; s < sc.n_slots; s++) rt_bounds_slot(sc, base, s, lo, hi);
+    rt_bounds_finish(lo, hi, b);
+    memcpy(pk->aabb_lo, b, 12), memcpy(pk->aabb_hi, b + 3, 12);
+    pk->plan.receivers_disabled = 0;
+    for (uint32_t t = 0; t < sc.n_triangles; t++)
+      pk->plan.receivers_disabled += rt_upd_recv(sc, base, pl.recv_cell.data(), pl.tri_slot.data(), b, t) ? 1u : 0u;
+  }
+  if (d->materials)
+    for (uint32_t i = 0; i < (uint32_t)pl.mat_class.size(); i++) rt_upd_material(sc, base, i, d->materials);
+  if (d->lights)
+    for (uint32_t i = 0; i < sc.n_lights; i++) rt_upd_light(sc, base, i, d->lights);
+  return RT_OK;
+}
+
 int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {
   *o = RtPackedScene();
   const uint32_t nt = d->n_triangles;
@@ -353,6 +445,7 @@ int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {
   pack_threaded_nodes(bvh, o);
   pack_materials(d, o);
   pack_lights(d, o);
+  make_refit_plan(d, bvh, no_split, o);
   if (o->blob.size() >= (size_t)1 << 32) return rt_fail(RT_ERR_UNSUPPORTED, "scene data exceeds 4 GiB");
   if (bvh.max_depth + 2 > 64) return rt_fail(RT_ERR_UNSUPPORTED, "BVH depth %u exceeds the traversal stack", bvh.max_depth);
 

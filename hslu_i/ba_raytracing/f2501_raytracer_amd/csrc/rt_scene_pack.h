@@ -12,6 +12,19 @@
 int rt_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // ---- scene packer ------------------------------------------------------------------------------------------------------
+// What an in-place update (rt_scene_update*, rt_refit_packed) needs beyond the blob: the tree's topology in the order a
+// refit walks it, and what was decided once at creation.  It lives outside the blob (device copies: rt_scene::plan_dev).
+struct RtRefitPlan {
+  // node indices grouped by height: first the nodes without an inner child, last the root; the nodes of height h are
+  // height_nodes[height_offset[h] .. height_offset[h + 1]), and every inner child of one of them has a smaller height
+  std::vector<uint32_t> height_nodes, height_offset;
+  std::vector<uint32_t> thr_src;    // per threaded entry: node * 2 + child, the child box it mirrors
+  std::vector<uint32_t> recv_cell;  // per canonical triangle: {R, first cell} as allocated at creation
+  std::vector<uint32_t> tri_slot;   // per canonical triangle: its first leaf slot
+  std::vector<uint8_t> mat_class;   // per material: bit 0 = transmissive at creation, bit 1 = a triangle uses it
+  uint32_t receivers_disabled = 0;  // triangles whose receiver record has R = 0 though cells were allocated (last update)
+};
+
 // Everything rt_scene_create computes before it touches the device.
 struct RtPackedScene {
   std::vector<unsigned char> blob;  // the one allocation the kernels address as base + offset (rt_scene::blob)
@@ -22,6 +35,7 @@ struct RtPackedScene {
   uint32_t n_tri_cells = 0;         // ... of which the first n_tri_cells belong to triangles
   size_t bytes_bvh = 0;             // of `blob`: nodes + octant copies + threaded copy
   float aabb_lo[3] = {0.f, 0.f, 0.f}, aabb_hi[3] = {1.f, 1.f, 1.f};  // bounds of everything a ray can hit
+  RtRefitPlan plan;
 };
 
 // the checks of an rt_scene_desc that need no device: RT_OK or RT_ERR_INVALID_ARG
@@ -29,6 +43,15 @@ int rt_check_scene_desc(const rt_scene_desc* d);
 // Lays out a checked description.  `budget` (bytes) bounds the receiver flags and their kernel input.
 // RT_OK, or RT_ERR_UNSUPPORTED (2^24 triangle references, 4 GiB of scene data, a BVH deeper than the traversal stack).
 int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* out);
+
+// ---- in-place updates ------------------------------------------------------------------------------------------------------
+// The checks of an rt_scene_delta that need no device, against the scene it is meant for: RT_OK, RT_ERR_INVALID_ARG (the
+// message names the field) or RT_ERR_UNSUPPORTED (a triangle group on a split-clipped tree).  `materials_host`: the delta's
+// material rows in host memory (null when the delta has none).
+int rt_check_scene_delta(const RtDevScene& dev, const RtRefitPlan& plan, const rt_scene_delta* d, const float* materials_host);
+// Applies a delta of HOST arrays to a packed scene with the arithmetic of the update kernels (rt_refit.h: the same
+// functions): the specification of rt_scene_update, checked on the CPU.  Same return codes as rt_check_scene_delta.
+int rt_refit_packed(RtPackedScene* pk, const rt_scene_delta* d);
 
 // ---- parameter tables of a frame -----------------------------------------------------------------------------------------
 // AA samples: the distinct offsets in first-occurrence order (compared as values; `dedup` off: every sample is distinct),

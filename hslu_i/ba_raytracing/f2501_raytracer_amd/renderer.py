@@ -102,6 +102,74 @@ class DeviceScene:
         _lib.check(_lib.load().rt_scene_memory_info(self.handle, C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in info._fields_}
 
+    def update(self, flat, info: bool = False, tri_first: int = 0):
+        """New values for the objects this scene already has, in place (`rt_scene_update`): the BVH is refitted on the
+        device, not rebuilt, and afterwards every render and query behaves as on a DeviceScene created from the new
+        description.  Blocks until the update is done.
+
+        flat: a FlatScene of numpy arrays -- it is compared with the description this scene holds, only the groups that
+        differ are sent (spheres, triangles, materials, lights), for triangles the smallest covering range; an equal
+        description is no call at all.  ValueError when a count or the object -> material assignment differs.
+        Or any object whose arrays are float32 torch tensors on this scene's device (`rt_scene_update_device` on
+        torch.cuda.current_stream()): every group it has is sent as given -- attributes that are missing or None are
+        unchanged, tri_v1 / tri_e1 / tri_e2 / tri_normal of shape (count, 3) replace triangles [tri_first, tri_first + count).
+        Returns None, or with info=True the rt_update_info of the call as a dict (None when nothing was sent)."""
+        lib = _lib.load()
+        inf = _abi.rt_update_info()
+        if isinstance(flat, FlatScene) and isinstance(flat.materials, np.ndarray):
+            new = flat.contiguous()
+            groups = _abi.scene_delta_groups(self.flat, new)
+            if not any(groups.values()):
+                return None
+            d, keep = _abi.make_scene_delta(new, groups)
+            _lib.check(lib.rt_scene_update(self.handle, C.byref(d), C.byref(inf)))
+            self.flat = new
+            return inf.as_dict() if info else None
+        import types
+
+        import torch
+
+        want = torch.device("cuda", self.device)
+        got = types.SimpleNamespace(**{k: getattr(flat, k, None) for k in _abi.SPHERE_GROUP + _abi.TRIANGLE_GROUP + ("materials", "lights")})
+        old = self.flat
+        shapes = {"sphere_center": (old.n_spheres, 3), "sphere_r_sq": (old.n_spheres,), "sphere_r_inv": (old.n_spheres,),
+                  "materials": tuple(old.materials.shape), "lights": tuple(old.lights.shape)}
+        count = None
+        for name, t in vars(got).items():
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != want:
+                raise ValueError(f"{name} must be a float32 tensor on {want} (the scene's device)")
+            if name in _abi.TRIANGLE_GROUP:
+                count = t.shape[0] if count is None else count
+                if t.dim() != 2 or tuple(t.shape) != (count, 3) or tri_first + count > old.n_triangles:
+                    raise ValueError(f"{name}: shape {tuple(t.shape)} does not replace triangles [{tri_first}, {tri_first} + count) of {old.n_triangles}")
+            elif tuple(t.shape) != shapes[name]:
+                raise ValueError(f"{name}: shape {tuple(t.shape)} differs from the scene's {shapes[name]}; an update keeps every count")
+            setattr(got, name, t.contiguous())
+        for group in (_abi.SPHERE_GROUP, _abi.TRIANGLE_GROUP):
+            given = [getattr(got, k) is not None for k in group]
+            if any(given) and not all(given):
+                raise ValueError(f"{', '.join(group)} are given together or not at all")
+        groups = {"spheres": got.sphere_center is not None and old.n_spheres > 0, "triangles": (int(tri_first), int(count)) if count else None,
+                  "materials": got.materials is not None and old.materials.shape[0] > 0, "lights": got.lights is not None and old.lights.shape[0] > 0}
+        if not any(groups.values()):
+            return None
+        d, keep = _abi.make_scene_delta(got, groups, ptr=lambda a: a.data_ptr())
+        stream = self._stream_of(next(t for t in vars(got).values() if t is not None))
+        _lib.check(lib.rt_scene_update_device(self.handle, C.byref(d), stream, C.byref(inf)))
+        # the description this scene holds follows (the call has synchronised its stream)
+        new = {k: np.array(getattr(old, k), copy=True) for k in FlatScene.__dataclass_fields__}
+        for name, t in vars(got).items():
+            if t is None:
+                continue
+            if name in _abi.TRIANGLE_GROUP:
+                new[name][tri_first:tri_first + count] = t.cpu().numpy()
+            else:
+                new[name] = t.cpu().numpy()
+        self.flat = FlatScene(**new).contiguous()
+        return inf.as_dict() if info else None
+
     def cast_rays(self, origins, directions, backface_culling: bool = False) -> "RayHits":
         """`Raytracer::cast_ray` (raytracer.rs:162-220) for a batch of rays: the nearest hit of each.  origins /
         directions: (n, 3) float32, numpy arrays (the host entry point; numpy results) or torch tensors on this scene's
@@ -268,9 +336,13 @@ class RaytracerRenderer:
     a `RenderConfig` and the renderer caches the device scene between calls.
     """
 
-    def __init__(self, cfg: RenderConfig, device: int = 0, traversal: int = _abi.RT_TRAVERSAL_BVH, scene_budget: int = 0):
+    def __init__(self, cfg: RenderConfig, device: int = 0, traversal: int = _abi.RT_TRAVERSAL_BVH, scene_budget: int = 0,
+                 update_in_place: bool = False):
         """scene_budget: rt_scene_desc.device_budget_bytes of the device scenes this renderer creates (0 = the library's
-        default, 128 MiB for the optional acceleration tables)."""
+        default, 128 MiB for the optional acceleration tables).
+        update_in_place: when a scene differs from the cached one only in values (same counts, same object -> material
+        assignment), update the cached device scene (DeviceScene.update: a BVH refit) instead of building a new one."""
+        self.update_in_place = bool(update_in_place)
         self.cfg = cfg
         self.device = int(device)
         self.traversal = int(traversal)
@@ -292,6 +364,16 @@ class RaytracerRenderer:
         key = flat.fingerprint()
         if self._cache is not None and self._cache[0] == key:
             return self._cache[1]
+        if self._cache is not None and self.update_in_place:
+            try:
+                self._cache[1].update(flat)
+                self._cache = (key, self._cache[1])
+                return self._cache[1]
+            except ValueError:
+                pass  # (counts or material assignment differ: a new device scene)
+            except _lib.RtError as e:
+                if e.code not in (_abi.RT_ERR_INVALID_ARG, _abi.RT_ERR_UNSUPPORTED):
+                    raise  # (refused: a transmissive class changed, or the tree was split-clipped -- a new device scene)
         if self._cache is not None:
             self._cache[1].close()
         ds = DeviceScene(flat, self.device, budget=self.scene_budget)

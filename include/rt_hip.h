@@ -411,8 +411,9 @@ int rt_render_end(rt_progress* progress, rt_stats* stats);
  * abi_version; a flag bit other than RT_FLAG_BACKFACE_CULLING; NULL origin / direction with n_rays > 0; every output
  * plane NULL.
  *
- * A query reads only the scene's immutable data: it may run on any stream while frames of the same scene render on others
- * (rt_render_begin's included), and it leaves every render state alone. */
+ * A query reads only the scene's data, which no render writes: it may run on any stream while frames of the same scene
+ * render on others (rt_render_begin's included), and it leaves every render state alone.  (rt_scene_update* is the one
+ * call that rewrites that data: a query still in flight must have finished before it.) */
 typedef struct rt_ray_batch {
   uint32_t abi_version;       /* RT_ABI_VERSION */
   uint32_t n_rays;            /* 0 is a valid no-op */
@@ -542,6 +543,64 @@ typedef struct rt_scene_info {
   uint32_t cell_lists_built;  /* 1 = the lists exist (they are built by the first frame with soft shadows) */
 } rt_scene_info;
 int rt_scene_memory_info(const rt_scene* scene, rt_scene_info* out);
+
+/* ---- in-place scene updates: new values for the objects of an existing handle, BVH refitted on the device ------------------
+ *
+ * No reference counterpart (its Scene is immutable during a render).  A delta carries new VALUES for objects the scene
+ * already has: counts and the object -> material assignment are those of rt_scene_create.  The tree keeps its topology;
+ * its boxes, the per-octant and threaded copies, the intersection / shading / receiver records and the scene bounds are
+ * recomputed by small kernels (csrc/rt_update.hip) with the arithmetic of the scene packer.
+ *
+ * After the call returns, every render, progressive render, multi-GPU render and query on this handle behaves exactly as
+ * on a handle freshly created from the updated description; the exceptions are speed (a refitted tree is looser than a
+ * rebuilt one, and the receiver-cell allocation is the one of creation) and rt_scene_bvh_info (the topology is kept).
+ *
+ * Both forms BLOCK: at entry they wait for every frame of this scene still in flight, at exit they synchronise their
+ * stream (the new scene bounds are read back there).  Ray queries the caller still has in flight on streams of its own are
+ * NOT waited for: finish them first.  Asynchronous updates are out of scope; so are adding or removing
+ * objects, a rebuild heuristic, and the refit of split-clipped trees.
+ *
+ * RT_ERR_INVALID_ARG (rt_last_error names the field): NULL scene or delta; wrong abi_version; a partial group;
+ * tri_first + tri_count > n_triangles; a delta that changes nothing; a progressive render owns the scene; a material row
+ * whose transmissive class -- has_opacity != 0 && !(fabs(opacity) <= 1.1920929e-7f) -- changes while a triangle uses it
+ * (the tree was built for that class).  All of these are found before any kernel runs; the device form reads the
+ * material rows back to check them.
+ * RT_ERR_UNSUPPORTED: a triangle group on a scene whose n_references > n_triangles (split clipping was on: clipped
+ * reference boxes cannot be refitted).  The default split_depth is 0.
+ * Multi-GPU: the caller updates each per_gpu[i]. */
+typedef struct rt_scene_delta {
+  uint32_t abi_version;          /* RT_ABI_VERSION */
+  /* every group: NULL = unchanged */
+  const float* sphere_center;    /* [n_spheres][3]  | the three sphere arrays are given together or not at all */
+  const float* sphere_r_sq;      /* [n_spheres]     | */
+  const float* sphere_r_inv;     /* [n_spheres]     | (not read by the library, as in rt_scene_desc) */
+  uint32_t tri_first, tri_count; /* canonical triangles [tri_first, tri_first + tri_count) are replaced; 0 = none */
+  const float* tri_v1;           /* [tri_count][3]  | all four together */
+  const float* tri_e1;
+  const float* tri_e2;
+  const float* tri_normal;
+  const float* materials;        /* [n_materials][RT_MATERIAL_STRIDE] */
+  const float* lights;           /* [n_lights][RT_LIGHT_STRIDE] */
+} rt_scene_delta;
+
+#define RT_UPDATE_INVALIDATES_RECEIVER_TABLES 1u /* receiver flags / cell lists: rebuilt by the next soft-shadow frame */
+#define RT_UPDATE_INVALIDATES_TILE_COSTS 2u      /* RT_TILE_ORDER_COST: the next such frame calibrates again */
+#define RT_UPDATE_INVALIDATES_QUEUE_SIZES 4u     /* the next frame with secondary rays verifies its queue sizes as a first frame does */
+
+typedef struct rt_update_info {
+  double device_ms;             /* device time of the update's kernels and copies */
+  double total_ms;              /* wall time of the call */
+  uint32_t nodes_refitted;      /* BVH nodes whose boxes were recomputed (0: no geometry in the delta) */
+  uint32_t slots_rewritten;     /* leaf slots whose intersection / shading records were rewritten */
+  uint32_t receivers_disabled;  /* triangles whose receiver grid is off (R = 0: their hit points walk the tree for soft shadows)
+                                   because the new maps are not finite or too ill-conditioned for the R of creation */
+  uint32_t tables_invalidated;  /* RT_UPDATE_INVALIDATES_* */
+} rt_update_info;
+
+/* host arrays (staged through one pinned buffer); `info` may be NULL */
+int rt_scene_update(rt_scene* scene, const rt_scene_delta* delta, rt_update_info* info);
+/* device arrays on the scene's device; the kernels run on `hip_stream` */
+int rt_scene_update_device(rt_scene* scene, const rt_scene_delta* delta, void* hip_stream, rt_update_info* info);
 
 /* ---- multi-GPU: tile-partitioned frame + ONE gather of the packed pixels to rank 0 (RCCL over xGMI) ---------
  *
