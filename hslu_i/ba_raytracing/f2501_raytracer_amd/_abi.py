@@ -143,6 +143,20 @@ class rt_scene_delta(C.Structure):
     ]
 
 
+class rt_ray_order_desc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("capacity", C.c_uint32), ("origin_bits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class rt_ray_order_info(C.Structure):
+    _fields_ = [
+        ("n_rays", C.c_uint32), ("n_live", C.c_uint32), ("origin_bits", C.c_uint32), ("direction_bits", C.c_uint32),
+        ("n_origin_axes", C.c_uint32), ("n_direction_axes", C.c_uint32), ("bytes", C.c_uint64), ("device_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 RT_UPDATE_INVALIDATES_RECEIVER_TABLES, RT_UPDATE_INVALIDATES_TILE_COSTS, RT_UPDATE_INVALIDATES_QUEUE_SIZES = 1, 2, 4
 
 

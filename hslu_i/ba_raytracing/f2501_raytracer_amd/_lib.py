@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_radiance, rt_scene_delta,
+from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
                    rt_scene_desc, rt_scene_info, rt_stats, rt_update_info)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,6 +18,8 @@ EXPORTS = (
     "rt_render_gather_device", "rt_comm_last_gather", "rt_render_begin", "rt_render_poll", "rt_render_end",
     "rt_cast_rays", "rt_cast_rays_device", "rt_any_intersection", "rt_any_intersection_device",
     "rt_trace_rays", "rt_trace_rays_device", "rt_scene_update", "rt_scene_update_device",
+    "rt_ray_order_create", "rt_ray_order_destroy", "rt_ray_order_build", "rt_ray_order_build_device", "rt_ray_order_set", "rt_ray_order_read",
+    "rt_trace_rays_ordered", "rt_trace_rays_ordered_device",
 )
 
 _lib = None
@@ -97,6 +99,24 @@ def load():
     lib.rt_scene_update.argtypes = [C.c_void_p, C.POINTER(rt_scene_delta), C.POINTER(rt_update_info)]
     lib.rt_scene_update_device.restype = C.c_int
     lib.rt_scene_update_device.argtypes = [C.c_void_p, C.POINTER(rt_scene_delta), C.c_void_p, C.POINTER(rt_update_info)]
+    lib.rt_ray_order_create.restype = C.c_int
+    lib.rt_ray_order_create.argtypes = [C.POINTER(rt_ray_order_desc), C.c_int, C.POINTER(C.c_void_p)]
+    lib.rt_ray_order_destroy.restype = None
+    lib.rt_ray_order_destroy.argtypes = [C.c_void_p]
+    lib.rt_ray_order_build.restype = C.c_int
+    lib.rt_ray_order_build.argtypes = [C.c_void_p, C.POINTER(rt_ray_batch)]
+    lib.rt_ray_order_build_device.restype = C.c_int
+    lib.rt_ray_order_build_device.argtypes = [C.c_void_p, C.POINTER(rt_ray_batch), C.c_void_p]
+    lib.rt_ray_order_set.restype = C.c_int
+    lib.rt_ray_order_set.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.rt_ray_order_read.restype = C.c_int
+    lib.rt_ray_order_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rt_ray_order_info)]
+    lib.rt_trace_rays_ordered.restype = C.c_int
+    lib.rt_trace_rays_ordered.argtypes = [C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_ray_batch), C.c_void_p, C.POINTER(rt_ray_radiance),
+                                          C.POINTER(rt_stats)]
+    lib.rt_trace_rays_ordered_device.restype = C.c_int
+    lib.rt_trace_rays_ordered_device.argtypes = [C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_ray_batch), C.c_void_p, C.POINTER(rt_ray_radiance),
+                                                 C.c_void_p]
     _lib = lib
     return lib
 

@@ -229,7 +229,8 @@ int rt_launch_query_any(const RtDevScene& sc, const RtQueryArgs& q, void* stream
 // ---- radiance queries (rt_trace_rays*: csrc/rt_rays.h) ------------------------------------------------------------------
 // Third kernel argument of the two ray-source kernels, behind (RtDevScene, RtDevParams): the caller's rays and the output
 // planes (device pointers, nullptr = not written).  With secondary rays rgb and argb are written by rt_resolve_kernel
-// (RtDevParams::aux_rgb / argb) and are not read from here.
+// (RtDevParams::aux_rgb / argb) and are not read from here.  Every array is indexed by the RAY, whatever `order` is: the
+// order only decides which 64 rays share a wavefront.
 struct RtRayArgs {
   const float* origin;     // [n][3]
   const float* direction;  // [n][3], any length
@@ -239,6 +240,7 @@ struct RtRayArgs {
   float* t;                // [n]
   uint32_t* argb;          // [n], hits only
   uint32_t n;
+  const uint32_t* order;   // [n] a permutation of the rays (rt_ray_order): position in the work list -> ray; nullptr = the identity
 };
 int rt_launch_rays(const RtDevScene& sc, const RtDevParams& p, const RtRayArgs& r, uint32_t n_wgs, void* stream);
 

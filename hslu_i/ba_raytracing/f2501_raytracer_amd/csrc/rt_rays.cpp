@@ -4,14 +4,77 @@
 // Unlike the queries of rt_query.cpp a radiance call IS a render call: it goes through the frame scheduler of rt_api.cpp
 // (rt_trace_rays_enqueue) as a frame of n x 1 pixels and uses the scene's parameter tables, frame slots and workspaces.
 // What is here: validation (before any HIP call), the parameters of that frame, and the host form's staging.
+//
+// Also the ray orders (rt_ray_order*, rt_trace_rays_ordered*): the handle, its workspace and its checks.  What an order IS
+// is in rt_ray_key.h (the key; host model: rt_ray_order.cpp) and rt_order.hip (the kernels); a trace reads it as
+// RtRayArgs::order.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cstring>
 
 #include "rt_host.h"
+#include "rt_ray_key.h"
+
+// A permutation of one batch's rays on one device and the workspace that builds it (one allocation: RtOrderWs).
+struct rt_ray_order {
+  int device = 0;
+  uint32_t capacity = 0, origin_bits = 0;
+  uint32_t n = 0;         // rays of the batch the order was built or set for
+  bool ready = false;     // built or set at least once
+  bool has_keys = false;  // built (rt_ray_order_set leaves no keys)
+  DevBuf buf;
+  RtOrderWs ws{};
+  hipEvent_t built_ev = nullptr;  // recorded behind the kernels of the last build
+  bool build_pending = false;
+  double device_ms = 0.0;
+};
 
 namespace {
+
+size_t pad256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
+
+int check_order_batch(const rt_ray_order* o, const rt_ray_batch* b, const char* fn) {
+  if (!o) return fail(RT_ERR_INVALID_ARG, "%s: null ray order", fn);
+  if (!b) return fail(RT_ERR_INVALID_ARG, "%s: null ray batch", fn);
+  if (b->abi_version != RT_ABI_VERSION)
+    return fail(RT_ERR_INVALID_ARG, "%s: rt_ray_batch.abi_version %u != %u", fn, b->abi_version, RT_ABI_VERSION);
+  if (b->n_rays > o->capacity) return fail(RT_ERR_INVALID_ARG, "%s: %u rays exceed the order's capacity of %u", fn, b->n_rays, o->capacity);
+  if (b->n_rays && (!b->origin || !b->direction)) return fail(RT_ERR_INVALID_ARG, "%s: origin / direction missing", fn);
+  return RT_OK;
+}
+
+// an order a trace of `b` may read: built or set, for as many rays (before any HIP call, before the scene is looked at)
+int check_order_use(const rt_ray_order* o, const rt_ray_batch* b, const char* fn) {
+  if (!o->ready) return fail(RT_ERR_INVALID_ARG, "%s: the ray order has never been built or set", fn);
+  if (o->n != b->n_rays) return fail(RT_ERR_INVALID_ARG, "%s: the ray order holds %u rays, the batch %u", fn, o->n, b->n_rays);
+  return RT_OK;
+}
+
+int check_order_device(const rt_ray_order* o, const rt_scene* s, const char* fn) {
+  if (o->device != s->device) return fail(RT_ERR_INVALID_ARG, "%s: the ray order lives on device %d, the scene on device %d", fn, o->device, s->device);
+  return RT_OK;
+}
+
+// the kernels of a build on `stream` (DEVICE arrays); n = 0 builds the empty order
+int order_enqueue(rt_ray_order* o, const float* origin, const float* direction, uint32_t n, hipStream_t stream) {
+  if (n) {
+    const hipError_t e = (hipError_t)rt_launch_order_build(o->ws, origin, direction, n, o->origin_bits, stream);
+    if (e != hipSuccess) return fail(RT_ERR_HIP, "ray order launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(o->built_ev, stream));
+    o->build_pending = true;
+  }
+  o->n = n, o->ready = true, o->has_keys = true, o->device_ms = 0.0;
+  return RT_OK;
+}
+
+int order_wait(rt_ray_order* o) {
+  if (o->build_pending) {
+    HIP_TRY(hipEventSynchronize(o->built_ev));
+    o->build_pending = false;
+  }
+  return RT_OK;
+}
 
 bool any_plane(const rt_ray_radiance* o) { return o && (o->rgb || o->valid || o->id || o->t || o->argb); }
 
@@ -46,10 +109,11 @@ int check_call(const rt_scene* s, const rt_params* p, const rt_ray_batch* b, con
   return RT_OK;
 }
 
-RtRayArgs args_of(const rt_ray_batch* b, const rt_ray_radiance* o) {
+RtRayArgs args_of(const rt_ray_batch* b, const rt_ray_radiance* o, const rt_ray_order* order) {
   RtRayArgs r;
   memset(&r, 0, sizeof(r));
   r.origin = b->origin, r.direction = b->direction, r.n = b->n_rays;
+  r.order = order ? order->ws.idx_b : nullptr;
   r.rgb = o->rgb, r.valid = o->valid, r.id = o->id, r.t = o->t, r.argb = o->argb;
   return r;
 }
@@ -73,30 +137,60 @@ struct Plane {  // a host output plane and its device twin
   bool upload;  // argb: a miss leaves the caller's value, so the caller's plane goes up first
 };
 
-}  // namespace
-
-extern "C" {
-
-int rt_trace_rays_device(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, void* hip_stream) {
-  rt_params q;
-  int rc = check_call(s, p, b, out, "rt_trace_rays_device", &q);
+// the device memory of an order for `capacity` rays on the current device
+int order_alloc(rt_ray_order* o) {
+  const size_t per = pad256((size_t)o->capacity * 4);
+  const size_t n_tiles = ((size_t)o->capacity + RT_ORDER_TILE - 1u) / RT_ORDER_TILE;
+  const size_t sums = pad256(RT_ORDER_SCAN_BLOCKS * 4);
+  const size_t hist = pad256(256u * n_tiles * 4), partial = pad256(RT_ORDER_BOUNDS_WGS * sizeof(RtKeyBounds)), frame = pad256(sizeof(RtKeyFrame));
+  int rc = o->buf.ensure(5 * per + hist + sums + partial + frame);
   if (rc != RT_OK) return rc;
-  if (b->n_rays == 0) return RT_OK;
-  if (s->progress_active) return fail(RT_ERR_INVALID_ARG, "a progressive render owns this scene until rt_render_end");
-  return rt_trace_rays_enqueue(s, &q, args_of(b, out), (hipStream_t)hip_stream);
+  char* p = (char*)o->buf.p;
+  o->ws.keys = (uint32_t*)p, o->ws.key_a = (uint32_t*)(p + per), o->ws.key_b = (uint32_t*)(p + 2 * per);
+  o->ws.idx_a = (uint32_t*)(p + 3 * per), o->ws.idx_b = (uint32_t*)(p + 4 * per);
+  o->ws.hist = (uint32_t*)(p + 5 * per);
+  o->ws.sums = (uint32_t*)(p + 5 * per + hist);
+  o->ws.partial = (RtKeyBounds*)(p + 5 * per + hist + sums);
+  o->ws.frame = (RtKeyFrame*)(p + 5 * per + hist + sums + partial);
+  HIP_TRY(hipEventCreate(&o->built_ev));
+  return RT_OK;
 }
 
-int rt_trace_rays(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, rt_stats* stats) {
+void order_free(rt_ray_order* o) {
+  if (!o) return;
+  (void)hipSetDevice(o->device);
+  if (o->build_pending) (void)hipEventSynchronize(o->built_ev);
+  if (o->built_ev) (void)hipEventDestroy(o->built_ev);
+  o->buf.release();
+  delete o;
+}
+
+// rt_trace_rays and rt_trace_rays_ordered: HOST arrays.  `order`: the order the kernels read the batch through (nullptr:
+// none); build_one: no order was given, one is built for this call behind the upload of the rays and freed at its end.
+int trace_host(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_order* order, bool build_one, const rt_ray_radiance* out,
+               rt_stats* stats, const char* fn) {
   rt_params q;
-  int rc = check_call(s, p, b, out, "rt_trace_rays", &q);
+  int rc = check_call(s, p, b, out, fn, &q);
   if (rc != RT_OK) return rc;
+  if (order && (rc = check_order_use(order, b, fn)) != RT_OK) return rc;
   if (stats) memset(stats, 0, sizeof(*stats));
   if (b->n_rays == 0) return RT_OK;
   if (s->progress_active) return fail(RT_ERR_INVALID_ARG, "a progressive render owns this scene until rt_render_end");
+  if (order && (rc = check_order_device(order, s, fn)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const auto t_begin = std::chrono::steady_clock::now();
   const size_t n = b->n_rays;
-  RtRayArgs r = args_of(b, out);
+  struct OrderGuard {  // the order of this call alone
+    rt_ray_order* o = nullptr;
+    ~OrderGuard() { order_free(o); }
+  } own;
+  if (build_one) {
+    own.o = new rt_ray_order();
+    own.o->device = s->device, own.o->capacity = b->n_rays;
+    if ((rc = order_alloc(own.o)) != RT_OK) return rc;
+    order = own.o;
+  }
+  RtRayArgs r = args_of(b, out, order);
   Plane planes[5];
   int np = 0;
   if (out->rgb) planes[np++] = {out->rgb, (void**)&r.rgb, n * 12, false};
@@ -119,7 +213,7 @@ int rt_trace_rays(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const 
     rt_scene* scene;
     hipStream_t s;
     ~StreamGuard() { (void)hipStreamSynchronize(s), rt_scene_forget_stream(scene, s), (void)hipStreamDestroy(s); }
-  } guard{s, stream};
+  } guard{s, stream};  // (declared behind `own`: the stream drains before the call's order is freed)
   EventPair ev;
   HIP_TRY(hipEventCreate(&ev.e0));
   HIP_TRY(hipEventCreate(&ev.e1));
@@ -127,7 +221,10 @@ int rt_trace_rays(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const 
   HIP_TRY(hipMemcpyAsync(d_d, b->direction, n * 12, hipMemcpyHostToDevice, stream));
   for (int k = 0; k < np; k++)
     if (planes[k].upload) HIP_TRY(hipMemcpyAsync(*planes[k].dev, planes[k].host, planes[k].bytes, hipMemcpyHostToDevice, stream));
+  // an order another stream is still building: this stream waits for it
+  if (order && !build_one && order->build_pending) HIP_TRY(hipStreamWaitEvent(stream, order->built_ev, 0));
   HIP_TRY(hipEventRecord(ev.e0, stream));
+  if (build_one && (rc = order_enqueue(own.o, d_o, d_d, b->n_rays, stream)) != RT_OK) return rc;
   if ((rc = rt_trace_rays_enqueue(s, &q, r, stream)) != RT_OK) return rc;
   HIP_TRY(hipEventRecord(ev.e1, stream));
   for (int k = 0; k < np; k++) HIP_TRY(hipMemcpyAsync(planes[k].host, *planes[k].dev, planes[k].bytes, hipMemcpyDeviceToHost, stream));
@@ -136,8 +233,145 @@ int rt_trace_rays(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const 
     if ((rc = rt_render_collect_stats(s, stats)) != RT_OK) return rc;
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    stats->kernel_ms = ms;  // (with secondary rays: every attempt of the batch, and the waits for its counters)
+    stats->kernel_ms = ms;  // (with secondary rays: every attempt of the batch, and the waits for its counters; the build of an order of this call)
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_trace_rays_device(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, void* hip_stream) {
+  rt_params q;
+  int rc = check_call(s, p, b, out, "rt_trace_rays_device", &q);
+  if (rc != RT_OK) return rc;
+  if (b->n_rays == 0) return RT_OK;
+  if (s->progress_active) return fail(RT_ERR_INVALID_ARG, "a progressive render owns this scene until rt_render_end");
+  return rt_trace_rays_enqueue(s, &q, args_of(b, out, nullptr), (hipStream_t)hip_stream);
+}
+
+int rt_trace_rays_ordered_device(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_order* order, const rt_ray_radiance* out,
+                                 void* hip_stream) {
+  const char* fn = "rt_trace_rays_ordered_device";
+  rt_params q;
+  int rc = check_call(s, p, b, out, fn, &q);
+  if (rc != RT_OK) return rc;
+  if (!order) return fail(RT_ERR_INVALID_ARG, "%s: null ray order (the device form allocates nothing: build one with rt_ray_order_build_device)", fn);
+  if ((rc = check_order_use(order, b, fn)) != RT_OK) return rc;
+  if (b->n_rays == 0) return RT_OK;
+  if (s->progress_active) return fail(RT_ERR_INVALID_ARG, "a progressive render owns this scene until rt_render_end");
+  if ((rc = check_order_device(order, s, fn)) != RT_OK) return rc;
+  return rt_trace_rays_enqueue(s, &q, args_of(b, out, order), (hipStream_t)hip_stream);
+}
+
+int rt_trace_rays(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, rt_stats* stats) {
+  return trace_host(s, p, b, nullptr, false, out, stats, "rt_trace_rays");
+}
+
+int rt_trace_rays_ordered(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_order* order, const rt_ray_radiance* out,
+                          rt_stats* stats) {
+  return trace_host(s, p, b, order, order == nullptr, out, stats, "rt_trace_rays_ordered");
+}
+
+// ---- ray orders ---------------------------------------------------------------------------------------------------------------
+int rt_ray_order_create(const rt_ray_order_desc* d, int device, rt_ray_order** out) {
+  if (!d || !out) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_create: null argument");
+  *out = nullptr;
+  if (d->abi_version != RT_ABI_VERSION)
+    return fail(RT_ERR_INVALID_ARG, "rt_ray_order_create: rt_ray_order_desc.abi_version %u != %u", d->abi_version, RT_ABI_VERSION);
+  if (d->capacity == 0) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_create: capacity 0");
+  if (d->capacity > RT_ORDER_MAX_RAYS) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_create: capacity %u exceeds the %u rays an order sorts", d->capacity, RT_ORDER_MAX_RAYS);
+  if (d->origin_bits > RT_KEY_AXIS_BITS) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_create: origin_bits %u > %u", d->origin_bits, RT_KEY_AXIS_BITS);
+  if (d->reserved) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_create: rt_ray_order_desc.reserved must be 0");
+  const int ndev = rt_device_count();
+  if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
+  if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+  rt_ray_order* o = new rt_ray_order();
+  o->device = device, o->capacity = d->capacity, o->origin_bits = d->origin_bits;
+  const int rc = order_alloc(o);
+  if (rc != RT_OK) {
+    order_free(o);
+    return rc;
+  }
+  *out = o;
+  return RT_OK;
+}
+
+void rt_ray_order_destroy(rt_ray_order* o) { order_free(o); }
+
+int rt_ray_order_build_device(rt_ray_order* o, const rt_ray_batch* b, void* hip_stream) {
+  const int rc = check_order_batch(o, b, "rt_ray_order_build_device");
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(o->device));
+  return order_enqueue(o, b->origin, b->direction, b->n_rays, (hipStream_t)hip_stream);
+}
+
+int rt_ray_order_build(rt_ray_order* o, const rt_ray_batch* b) {
+  int rc = check_order_batch(o, b, "rt_ray_order_build");
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(o->device));
+  if ((rc = order_wait(o)) != RT_OK) return rc;
+  const size_t n = b->n_rays;
+  if (n == 0) return order_enqueue(o, nullptr, nullptr, 0, nullptr);
+  Staging st;
+  if ((rc = st.buf.ensure(2 * Staging::pad(n * 12))) != RT_OK) return rc;
+  float* d_o = (float*)st.take(n * 12);
+  float* d_d = (float*)st.take(n * 12);
+  hipStream_t stream = nullptr;
+  HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  struct StreamGuard {
+    hipStream_t s;
+    ~StreamGuard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
+  } guard{stream};
+  EventPair ev;
+  HIP_TRY(hipEventCreate(&ev.e0));
+  HIP_TRY(hipEventCreate(&ev.e1));
+  HIP_TRY(hipMemcpyAsync(d_o, b->origin, n * 12, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_d, b->direction, n * 12, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(ev.e0, stream));
+  if ((rc = order_enqueue(o, d_o, d_d, b->n_rays, stream)) != RT_OK) return rc;
+  HIP_TRY(hipEventRecord(ev.e1, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  o->build_pending = false;
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  o->device_ms = ms;
+  return RT_OK;
+}
+
+int rt_ray_order_set(rt_ray_order* o, const uint32_t* perm, uint32_t n) {
+  if (!o) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_set: null ray order");
+  if (n > o->capacity) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_set: %u rays exceed the order's capacity of %u", n, o->capacity);
+  int rc = rt_check_permutation(perm, n);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(o->device));
+  if ((rc = order_wait(o)) != RT_OK) return rc;
+  if (n) HIP_TRY(hipMemcpy(o->ws.idx_b, perm, (size_t)n * 4, hipMemcpyHostToDevice));
+  o->n = n, o->ready = true, o->has_keys = false, o->device_ms = 0.0;
+  return RT_OK;
+}
+
+int rt_ray_order_read(rt_ray_order* o, uint32_t* perm, uint32_t* keys, rt_ray_order_info* info) {
+  if (!o) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_read: null ray order");
+  if (!o->ready) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_read: the ray order has never been built or set");
+  if (keys && !o->has_keys) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_read: an order given by rt_ray_order_set has no keys");
+  HIP_TRY(hipSetDevice(o->device));
+  const int rc = order_wait(o);
+  if (rc != RT_OK) return rc;
+  if (perm && o->n) HIP_TRY(hipMemcpy(perm, o->ws.idx_b, (size_t)o->n * 4, hipMemcpyDeviceToHost));
+  if (keys && o->n) HIP_TRY(hipMemcpy(keys, o->ws.keys, (size_t)o->n * 4, hipMemcpyDeviceToHost));
+  if (info) {
+    *info = rt_ray_order_info{};
+    info->n_rays = o->n, info->bytes = o->buf.cap, info->device_ms = o->device_ms;
+    if (o->has_keys && o->n) {
+      RtKeyFrame f;
+      HIP_TRY(hipMemcpy(&f, o->ws.frame, sizeof(f), hipMemcpyDeviceToHost));
+      info->n_live = f.n_live, info->origin_bits = f.origin_bits, info->direction_bits = f.direction_bits;
+      info->n_origin_axes = f.n_origin_axes, info->n_direction_axes = f.n_direction_axes;
+    }
   }
   return RT_OK;
 }

@@ -8,9 +8,10 @@
 //
 // One ray per lane, ray i = "pixel" i of a frame of n x 1 pixels: the light-cloud set of ray i is the one pixel i would
 // take, its children carry i as their pixel, and (STREAM) its sums meet in accumulator entry i.  The mapping is linear
-// (workgroup w of the frame's list holds rays 256 w .. 256 w + 255), not the super-tile order of a frame: the caller's
-// order is the only order there is, and neighbouring rays of a batch should be neighbours in space -- the walks inside
-// process_ray are wave-cooperative, so a wavefront of unrelated rays is correct but visits the union of their nodes.
+// (workgroup w of the frame's list holds positions 256 w .. 256 w + 255), not the super-tile order of a frame.  Position k
+// holds ray k, or ray order[k] when the call came with a ray order (rt_trace_rays_ordered*; built by rt_order.hip): the
+// walks inside process_ray are wave-cooperative, so a wavefront of unrelated rays is correct but visits the union of their
+// nodes, and an order packs neighbours in space into one wavefront.  The results do not depend on the packing.
 //
 // Kernel arguments: process_ray and its callees read sc and P again from the kernarg segment at offsets 0 and 88
 // (kernarg_scene / kernarg_params), so the kernels take (RtDevScene, RtDevParams) first and the batch as a THIRD argument,
@@ -22,8 +23,12 @@
 #define RT_KERNARG_OFF_R ((RT_KERNARG_OFF_P + sizeof(RtDevParams) + alignof(RtRayArgs) - 1) / alignof(RtRayArgs) * alignof(RtRayArgs))
 __device__ __forceinline__ const RtRayArgs& kernarg_rays() { return *(const RtRayArgs*)((const char*)kernarg_fresh() + RT_KERNARG_OFF_R); }
 
-// the ray of this thread in the frame's work list (the chains of a batch with secondary rays interleave: rt_batch_wg)
-__device__ __forceinline__ uint32_t ray_index(const RtDevParams& P, uint32_t tid) { return rt_batch_wg(P, blockIdx.x) * 256u + tid; }
+// the position of this thread in the frame's work list (the chains of a batch with secondary rays interleave: rt_batch_wg)
+__device__ __forceinline__ uint32_t ray_slot(const RtDevParams& P, uint32_t tid) { return rt_batch_wg(P, blockIdx.x) * 256u + tid; }
+// ... and the ray at that position: the caller's order, or through a ray order (rt_ray_order: a permutation of [0, n)).  Past
+// the end of the list: the position itself (>= n, never a ray).  Ray i stays ray i whatever its position: its cloud set,
+// its accumulator entry and its outputs are indexed by i.
+__device__ __forceinline__ uint32_t ray_index(const RtRayArgs& R, uint32_t slot) { return R.order && slot < R.n ? R.order[slot] : slot; }
 
 // STREAM: children are queued and the ray's own terms are added to accumulator entry i (rt_resolve_kernel then writes rgb
 // and argb); otherwise the colour is complete here and every plane is written directly.
@@ -33,7 +38,7 @@ __device__ __forceinline__ void rays_body(const RtDevScene& sc, const RtDevParam
   Wave wv;
   wave_init(wv);
   wave_flush_init(P, lds_cnt);
-  const uint32_t i = ray_index(P, threadIdx.x);
+  const uint32_t i = ray_index(R, ray_slot(P, threadIdx.x));
   const bool have = i < R.n;
   RayIn r;
   r.o = mk(0.0f, 0.0f, 0.0f);
@@ -59,7 +64,7 @@ __device__ __forceinline__ void rays_body(const RtDevScene& sc, const RtDevParam
   const RtRayArgs& R1 = kernarg_rays();
   uint32_t tid2 = threadIdx.x;
   RT_OPAQUE(tid2);  // keeps hipcc from carrying the first index through process_ray
-  const uint32_t i2 = ray_index(P1, tid2);
+  const uint32_t i2 = ray_index(R1, ray_slot(P1, tid2));
   const bool on = i2 < R1.n, hit = on && out.hit;
   if (on) {
     if (R1.valid) R1.valid[i2] = hit ? 1u : 0u;

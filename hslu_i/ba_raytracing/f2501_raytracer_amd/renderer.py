@@ -71,6 +71,87 @@ class Radiance(NamedTuple):
     t: Any
 
 
+class RayOrder:
+    """Owns an `rt_ray_order*`: a permutation of one batch's rays on one device, which `DeviceScene.trace_rays(order=...)`
+    reads the batch through so that rays which are neighbours in space share a wavefront.  The results are those of the
+    unordered call, bit for bit.  An order belongs to a batch, not to a scene: it survives `DeviceScene.update`, works with
+    any scene on its device and may be reused for any batch of the same number of rays."""
+
+    def __init__(self, device: int, capacity: int, origin_bits: int = 0):
+        lib = _lib.load()
+        desc = _abi.rt_ray_order_desc(_abi.RT_ABI_VERSION, int(capacity), int(origin_bits), 0)
+        h = C.c_void_p()
+        _lib.check(lib.rt_ray_order_create(C.byref(desc), int(device), C.byref(h)))
+        self._h = h
+        self.device = int(device)
+        self.capacity = int(capacity)
+
+    @staticmethod
+    def from_permutation(device: int, perm) -> "RayOrder":
+        """The caller's own order (its tiles, say): perm[k] = the ray at position k, a permutation of range(n)."""
+        perm = np.ascontiguousarray(perm, np.uint32)
+        if perm.ndim != 1 or perm.size == 0:
+            raise ValueError("perm must be a non-empty 1-d array")
+        order = RayOrder(device, perm.size)
+        _lib.check(_lib.load().rt_ray_order_set(order.handle, perm.ctypes.data, perm.size))
+        return order
+
+    @property
+    def handle(self) -> C.c_void_p:
+        if self._h is None:
+            raise RuntimeError("ray order destroyed")
+        return self._h
+
+    def build(self, batch: "_abi.rt_ray_batch", stream=None) -> "RayOrder":
+        """Sorts the rays of `batch`: host arrays (stream None; blocks) or device arrays enqueued on `stream`."""
+        lib = _lib.load()
+        if stream is None:
+            _lib.check(lib.rt_ray_order_build(self.handle, C.byref(batch)))
+        else:
+            _lib.check(lib.rt_ray_order_build_device(self.handle, C.byref(batch), stream))
+        return self
+
+    def _read(self, perm: bool, keys: bool):
+        lib = _lib.load()
+        info = _abi.rt_ray_order_info()
+        _lib.check(lib.rt_ray_order_read(self.handle, None, None, C.byref(info)))  # (the handle knows how many rays it holds)
+        if not (perm or keys):
+            return None, None, info.as_dict()
+        p = np.empty(info.n_rays, np.uint32) if perm else None
+        k = np.empty(info.n_rays, np.uint32) if keys else None
+        _lib.check(lib.rt_ray_order_read(self.handle, p.ctypes.data if perm else None, k.ctypes.data if keys else None, None))
+        return p, k, info.as_dict()
+
+    @property
+    def n_rays(self) -> int:
+        """rays of the batch the order was last built or set for"""
+        return self.info["n_rays"]
+
+    def permutation(self) -> np.ndarray:
+        """perm[k] = the ray at position k (blocks until the last build is done)."""
+        return self._read(True, False)[0]
+
+    def keys(self) -> np.ndarray:
+        """The sort key of every ray, by ray (a built order only)."""
+        return self._read(False, True)[1]
+
+    @property
+    def info(self) -> Dict:
+        """rt_ray_order_info: rays, live rays, the bit split of the key, device bytes, the device time of a blocking build."""
+        return self._read(False, False)[2]
+
+    def close(self):
+        if self._h is not None:
+            _lib.load().rt_ray_order_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceScene:
     """Owns an `rt_scene*` (device copies + BVH)."""
 
@@ -85,6 +166,7 @@ class DeviceScene:
         self.flat = keep
         self.last_trace_stats: Optional[Dict] = None  # rt_stats of the last trace_rays call on host arrays
         self._trace_params = None  # (key, rt_params, keepalive) of the last trace_rays call
+        self._call_order: Optional[RayOrder] = None  # trace_rays(tensors, order=True): the order of the last such call
 
     @property
     def handle(self) -> C.c_void_p:
@@ -221,16 +303,34 @@ class DeviceScene:
             _lib.check(lib.rt_any_intersection(self.handle, C.byref(b), C.byref(oc)))
         return out
 
+    def ray_order(self, origins, directions, origin_bits: int = 0) -> RayOrder:
+        """A RayOrder for these rays on this scene's device, sorted on the device by the Morton code of origin and
+        direction (origin_bits: bits per origin axis, 0 = default).  Same input kinds as cast_rays: numpy arrays (blocks)
+        or torch tensors (enqueued on torch.cuda.current_stream(), no synchronisation)."""
+        torch_in, n, o, d, _ = self._batch(origins, directions, None)
+        if n == 0:
+            raise ValueError("a ray order needs at least one ray")
+        order = RayOrder(self.device, n, origin_bits)
+        ptr = (lambda a: a.data_ptr()) if torch_in else (lambda a: a.ctypes.data)
+        return order.build(self._batch_struct(n, o, d, None, False, ptr), self._stream_of(o) if torch_in else None)
+
     def trace_rays(self, origins, directions, cfg: RenderConfig, tuning: Optional[Dict] = None, traversal: int = _abi.RT_TRAVERSAL_BVH,
-                   argb=None) -> "Radiance":
+                   argb=None, order=None) -> "Radiance":
         """`single_raytrace` (raytracer_renderer.rs:147-264) for a batch of rays: the colour the render gives a pixel whose
         camera ray is that ray, shaded with `cfg` (soft shadows, reflections, refractions, backface culling, depths; its
         camera and anti-aliasing are not used: the caller supplies its samples as rays).  Ray i takes the light-cloud set
         of pixel i.  Same input kinds as cast_rays: numpy arrays (host entry point, numpy results, `last_trace_stats` is
         filled) or torch tensors on this scene's device (the _device entry point on torch.cuda.current_stream(); tensor
         results).  argb: optional uint32 array / int32 tensor of n packed pixels; hits are written, misses keep their
-        value.  One radiance or render call per scene at a time."""
+        value.  One radiance or render call per scene at a time.
+        order: None = the rays share wavefronts in the order given; True = an order is built on the device for this call;
+        a RayOrder (ray_order(), RayOrder.from_permutation) is reused.  The results are the same bits either way.
+        With tensors and order=True the order of the call lives in this scene and every such call rebuilds it on its
+        stream: the rule above -- one radiance call per scene at a time -- holds across streams too (a second call on
+        another stream must be ordered behind the first, as its frame slots and workspaces must)."""
         torch_in, n, o, d, _ = self._batch(origins, directions, None)
+        if order is not None and order is not True and not isinstance(order, RayOrder):
+            raise ValueError("order must be None, True or a RayOrder")
         if cfg.has("anti_aliasing"):
             cfg = RenderConfig(**{**cfg.__dict__, "features": cfg.features - {"anti_aliasing"}})
         # (the parameters of the last configuration are kept: building the light-cloud table is the expensive part of a call)
@@ -258,10 +358,29 @@ class DeviceScene:
         r = _abi.rt_ray_radiance(ptr(out.rgb), ptr(out.valid), ptr(out.id), ptr(out.t), ptr(argb) if argb is not None else None)
         lib = _lib.load()
         if torch_in:
-            _lib.check(lib.rt_trace_rays_device(self.handle, C.byref(p), C.byref(b), C.byref(r), self._stream_of(o)))
+            stream = self._stream_of(o)
+            if order is True and n:
+                # the order of this call stays alive in the scene while the stream reads it; a larger batch replaces it once
+                # the device has drained (rare: the capacity only grows)
+                if self._call_order is None or self._call_order.capacity < n:
+                    if self._call_order is not None:
+                        import torch
+
+                        torch.cuda.synchronize(o.device)
+                        self._call_order.close()
+                    self._call_order = RayOrder(self.device, n)
+                order = self._call_order.build(b, stream)
+            if order is None or order is True:
+                _lib.check(lib.rt_trace_rays_device(self.handle, C.byref(p), C.byref(b), C.byref(r), stream))
+            else:
+                _lib.check(lib.rt_trace_rays_ordered_device(self.handle, C.byref(p), C.byref(b), order.handle, C.byref(r), stream))
         else:
             st = _abi.rt_stats()
-            _lib.check(lib.rt_trace_rays(self.handle, C.byref(p), C.byref(b), C.byref(r), C.byref(st)))
+            if order is None:
+                _lib.check(lib.rt_trace_rays(self.handle, C.byref(p), C.byref(b), C.byref(r), C.byref(st)))
+            else:
+                _lib.check(lib.rt_trace_rays_ordered(self.handle, C.byref(p), C.byref(b), None if order is True else order.handle, C.byref(r),
+                                                     C.byref(st)))
             self.last_trace_stats = st.as_dict()
         return out
 
@@ -319,8 +438,11 @@ class DeviceScene:
 
     def close(self):
         if self._h is not None:
-            _lib.load().rt_scene_destroy(self._h)
+            _lib.load().rt_scene_destroy(self._h)  # (waits for the scene's frames and batches)
             self._h = None
+        if self._call_order is not None:
+            self._call_order.close()
+            self._call_order = None
 
     def __del__(self):
         try:
@@ -405,16 +527,18 @@ class RaytracerRenderer:
         self.last_stats = st.as_dict()
         return planes
 
-    def render_camera(self, buffer: ImageBuffer, scene, camera, tuning: Optional[Dict] = None) -> Radiance:
+    def render_camera(self, buffer: ImageBuffer, scene, camera, tuning: Optional[Dict] = None, order=False) -> Radiance:
         """Renders `scene` as `camera` sees it (anything with width, height and rays() -> (origins, directions), row-major
         with row 0 at the top: camera.PinholeCamera) into `buffer`: the rays go through DeviceScene.trace_rays with this
         renderer's configuration, hit pixels are written, misses keep the buffer's fill.  One ray per pixel -- the
-        configuration's anti-aliasing belongs to the reference's own view and is not applied.  Returns the Radiance planes."""
+        configuration's anti-aliasing belongs to the reference's own view and is not applied.  Returns the Radiance planes.
+        order: False = the camera's row-major order; True = a ray order is built on the device for this call; a RayOrder
+        (of a camera that does not move relative to its rays' pattern) is reused.  The image is the same."""
         if buffer.width != camera.width or buffer.height != camera.height:
             raise ValueError(f"buffer is {buffer.width}x{buffer.height}, the camera renders {camera.width}x{camera.height}")
         ds = self.device_scene(scene)
         o, d = camera.rays()
-        out = ds.trace_rays(o, d, self.cfg, tuning=tuning, traversal=self.traversal, argb=buffer.buffer)
+        out = ds.trace_rays(o, d, self.cfg, tuning=tuning, traversal=self.traversal, argb=buffer.buffer, order=order or None)
         self.last_stats = ds.last_trace_stats
         return out
 

@@ -33,6 +33,8 @@
  *                        a ray: nearest hit, the lights' shadow and transmittance rays, soft-shadow clouds, attenuation,
  *                        reflection and refraction trees), for a batch of HOST rays; blocks
  *   rt_trace_rays_device         <- same, DEVICE arrays, enqueued on the caller's stream
+ *   rt_ray_order_*, rt_trace_rays_ordered[_device]  <- none (the reference recurses per ray): the same colours, the
+ *                        rays packed into wavefronts by a permutation sorted on the device
  *   rt_last_error     <- (reference panics: `unwrap()/expect()`); here: error codes + message
  *
  * All arithmetic on the path is fp32.  Hit ids are canonical object indices: spheres first
@@ -470,7 +472,8 @@ int rt_any_intersection_device(rt_scene* scene, const rt_ray_batch* batch, const
  * runs the chained level schedule with fused phases (the other forms derive the camera ray from the work-item index).
  *
  * Order matters for speed, not for the result: the walks are wave-cooperative (64 consecutive rays share one), so
- * neighbouring rays of a batch should be neighbours in space.  The library does not reorder the caller's rays.
+ * neighbouring rays of a batch should be neighbours in space.  These two calls do not reorder the caller's rays;
+ * rt_trace_rays_ordered* (below) read the batch through a permutation built on the device, with the same results.
  *
  * rt_stats (host form; device form: rt_render_collect_stats after synchronising): rays_primary = live rays,
  * rays_reflection / rays_refraction / rays_shadow as the reference casts them, pixels_written = valid rays, rays_traced =
@@ -504,6 +507,79 @@ int rt_trace_rays(rt_scene* scene, const rt_params* shading, const rt_ray_batch*
 /* DEVICE arrays on the scene's device, enqueued on `hip_stream` (a hipStream_t, NULL = default stream). */
 int rt_trace_rays_device(rt_scene* scene, const rt_params* shading, const rt_ray_batch* batch, const rt_ray_radiance* out,
                          void* hip_stream);
+
+/* ---- ray orders: coherent wavefronts for radiance queries, sorted on the device ----------------------------------------------
+ *
+ * An rt_ray_order is a permutation of one batch's rays (and the workspace that builds it) on one device.  The ordered
+ * radiance calls read the batch THROUGH it: wavefront w works on rays perm[64 w .. 64 w + 63] instead of rays 64 w ..
+ * 64 w + 63, so that rays which are neighbours in space share the wave-cooperative walks.
+ *
+ * Results: an ordered call returns exactly what rt_trace_rays[_device] returns for the same batch, whatever the order is
+ * -- every plane bit for bit, argb untouched on a miss, every rt_stats counter, the same validation and blocking rules.
+ * Ray identity: ray i remains ray i.  Its light-cloud set (keyed by i), its accumulator entry and its output index do not
+ * move; only which 64 rays share a wavefront changes.  (A caller who permutes its own arrays instead changes the cloud
+ * set of every ray, and with it the soft-shadow result.)
+ *
+ * rt_ray_order_build* sorts the rays by a key made of the batch alone: the Morton code of origin and normalised
+ * direction, quantised inside the bounds of the batch's live rays, origins first.  Each origin axis on which the rays
+ * differ gets `origin_bits` bits (0 = default: min(10, 30 / number of such axes), but 5 when all three origin axes and
+ * some direction axis differ -- unrelated rays in a volume, where 5 + 5 measured fastest), each such direction axis
+ * min(10, (30 - origin bits in all) / number of such axes); dead rays (the query rule) get key 0xFFFFFFFF and come last.
+ * The major part of the key (the origins; the directions of a batch with one origin) is not a Morton code all the way up:
+ * its cells form blocks of about 4096 rays that follow one another row-major, with the Morton code inside a block -- a
+ * camera batch walked in nested squares traced slower than in rows of blocks.
+ * Rays of equal key follow one another in an unspecified order.  The key is specified by a host model compiled from the
+ * same source as the kernels (csrc/rt_ray_key.h); rt_ray_order_read returns the device's keys.
+ *
+ * Not tied to a scene: the key uses only the batch, so an order stays valid across rt_scene_update*, may be used with any
+ * scene on its device, and may be reused for any batch of the same n_rays -- it is as good as the rays are similar to
+ * the ones it was built from.
+ *
+ * Refused with RT_ERR_INVALID_ARG (+ rt_last_error) before any HIP call: a NULL pointer or wrong abi_version; capacity 0 or above
+ * 2^27 = 134 217 728 rays; origin_bits > 10; n > capacity; an order whose n_rays differs from batch->n_rays, that lives on another device than the
+ * scene, or that has never been built or set; an rt_ray_order_set array that is not a permutation of [0, n).
+ *
+ * Stream ordering is the caller's: rt_ray_order_build_device and a trace that reads the order run on the same stream, or
+ * are ordered with events.  rt_ray_order_destroy waits for the last build; traces still in flight that read the order are
+ * the caller's to finish first (the queries' rule).
+ *
+ * rt_cast_rays* and rt_any_intersection* take no order: their kernels walk per lane, so wavefront packing matters less.
+ * A caller who wants it can apply rt_ray_order_read's permutation to its own arrays (the queries have no per-index state). */
+typedef struct rt_ray_order rt_ray_order;
+typedef struct rt_ray_order_desc {
+  uint32_t abi_version; /* RT_ABI_VERSION */
+  uint32_t capacity;    /* most rays a batch of this order may have, 1 .. 2^27 */
+  uint32_t origin_bits; /* bits per active origin axis, 0 = default, at most 10 */
+  uint32_t reserved;    /* 0 */
+} rt_ray_order_desc;
+typedef struct rt_ray_order_info {
+  uint32_t n_rays, n_live;                    /* rays of the batch; of them not dead (0 after rt_ray_order_set) */
+  uint32_t origin_bits, direction_bits;       /* bits per active axis as applied */
+  uint32_t n_origin_axes, n_direction_axes;   /* axes on which the live rays differ */
+  uint64_t bytes;                             /* device memory the order holds */
+  double device_ms;                           /* rt_ray_order_build: the kernels of the last build (0 otherwise) */
+} rt_ray_order_info;
+
+/* allocates the permutation, the keys and the sort workspace for `capacity` rays on `device` (20 bytes per ray + tables) */
+int rt_ray_order_create(const rt_ray_order_desc* desc, int device, rt_ray_order** out);
+void rt_ray_order_destroy(rt_ray_order* order);
+/* HOST arrays (origin, direction; max_distance and flags are not read): staged through device memory of the call; returns
+ * when the order is built */
+int rt_ray_order_build(rt_ray_order* order, const rt_ray_batch* host_batch);
+/* DEVICE arrays on the order's device: enqueues the bounds, key and sort kernels on `hip_stream`; allocates nothing, reads
+ * nothing back and never synchronises */
+int rt_ray_order_build_device(rt_ray_order* order, const rt_ray_batch* batch, void* hip_stream);
+/* the caller's own order (its tiles, say): perm_host[k] = the ray at position k; checked on the host; blocks */
+int rt_ray_order_set(rt_ray_order* order, const uint32_t* perm_host, uint32_t n);
+/* blocks until the last build is done; every output nullable: perm_host [n_rays], keys_host [n_rays] (the key of ray i;
+ * refused after rt_ray_order_set, which has none) */
+int rt_ray_order_read(rt_ray_order* order, uint32_t* perm_host, uint32_t* keys_host, rt_ray_order_info* info);
+/* rt_trace_rays through `order`; order NULL: one is built for this call (and freed), rt_stats.kernel_ms includes it */
+int rt_trace_rays_ordered(rt_scene* scene, const rt_params* shading, const rt_ray_batch* batch, const rt_ray_order* order,
+                          const rt_ray_radiance* out, rt_stats* stats);
+/* rt_trace_rays_device through `order` (not NULL: the device form allocates nothing) */
+int rt_trace_rays_ordered_device(rt_scene* scene, const rt_params* shading, const rt_ray_batch* batch, const rt_ray_order* order,
+                                 const rt_ray_radiance* out, void* hip_stream);
 
 /* thread-local message for the last non-RT_OK return on this thread */
 const char* rt_last_error(void);

@@ -2,7 +2,7 @@
 """Renders semesterbild on GPU 0 from a viewpoint of the caller's choosing (the reference has one, fixed at compile
 time) and writes a PNG: camera.PinholeCamera -> RaytracerRenderer.render_camera -> rt_trace_rays.
 
-    render_view.py OUT.png [--eye X,Y,Z] [--target X,Y,Z] [--fov DEG] [--size WxH] [--features f,g] [--model text|text_lowres]
+    render_view.py OUT.png [--eye X,Y,Z] [--target X,Y,Z] [--fov DEG] [--size WxH] [--features f,g] [--model text|text_lowres] [--order]
 
 eye / target are in units of the scene's width, height and depth (the reference's own focus is 0.5,0.5,-1.9; image y points
 down, so the camera's up vector is (0, -1, 0))."""
@@ -28,6 +28,7 @@ def main():
     ap.add_argument("--features", default="soft_shadows,realistic")
     ap.add_argument("--model", default="text")
     ap.add_argument("--fill", default="0xFF101010")
+    ap.add_argument("--order", action="store_true", help="pack the camera's rays into coherent wavefronts (a ray order built on the device)")
     args = ap.parse_args()
     cfg = RenderConfig.from_features([f for f in args.features.split(",") if f])
     scale = (float(cfg.scene_width), float(cfg.scene_height), float(cfg.scene_depth))
@@ -39,8 +40,8 @@ def main():
     buf = ImageBuffer.new_with_color(w, h, int(args.fill, 0))
     r = RaytracerRenderer(cfg)
     t = time.time()
-    out = r.render_camera(buf, scene, cam)
-    print(f"semesterbild {w}x{h} from eye={eye} features={sorted(cfg.features)} valid={float(out.valid.mean()):.3f} "
+    out = r.render_camera(buf, scene, cam, order=args.order)
+    print(f"semesterbild {w}x{h} from eye={eye} features={sorted(cfg.features)} order={args.order} valid={float(out.valid.mean()):.3f} "
           f"wall={time.time() - t:.3f}s stats={r.last_stats}")
     Image.fromarray(buf.as_rgb8()).save(args.out)
 
