@@ -71,6 +71,67 @@ struct EventPair {  // destroyed on every return path
   }
 };
 
+// the alignment of every array inside a device allocation that holds several
+inline size_t rt_pad256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
+
+// The device side of an entry point that takes HOST arrays (rt_cast_rays, rt_any_intersection, rt_trace_rays*,
+// rt_ray_order_build): one device allocation for the call, every array 256-byte aligned in it, and a private stream, so
+// that the call neither waits for nor delays work the caller has on the null stream.  in() / out() list the arrays: *slot
+// is the host array (NULL: not staged) and becomes its device twin in begin(), which allocates, creates the stream and
+// enqueues the uploads; the caller enqueues its work on `stream`; finish() enqueues the downloads and waits.  The stream
+// drains and is destroyed on every return path, then the memory is freed.
+struct HostCall {
+  struct Array {
+    void* host;
+    void** dev;
+    size_t bytes;
+    bool up, down;
+  };
+  std::vector<Array> arrays;
+  DevBuf buf;
+  hipStream_t stream = nullptr;
+  template <class T>
+  void in(const T** slot, size_t bytes) {
+    if (*slot) arrays.push_back({(void*)*slot, (void**)slot, bytes, true, false});
+  }
+  // upload_first: a plane the kernels write only in part (argb: a miss leaves the caller's value)
+  template <class T>
+  void out(T** slot, size_t bytes, bool upload_first = false) {
+    if (*slot) arrays.push_back({*slot, (void**)slot, bytes, upload_first, true});
+  }
+  int begin() {
+    size_t total = 0;
+    for (const Array& a : arrays) total += rt_pad256(a.bytes);
+    const int rc = buf.ensure(total);
+    if (rc != RT_OK) return rc;
+    size_t used = 0;
+    for (const Array& a : arrays) *a.dev = (char*)buf.p + used, used += rt_pad256(a.bytes);
+    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    for (const Array& a : arrays)
+      if (a.up) HIP_TRY(hipMemcpyAsync(*a.dev, a.host, a.bytes, hipMemcpyHostToDevice, stream));
+    return RT_OK;
+  }
+  int finish() {
+    for (const Array& a : arrays)
+      if (a.down) HIP_TRY(hipMemcpyAsync(a.host, *a.dev, a.bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return RT_OK;
+  }
+  ~HostCall() {
+    if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+    buf.release();
+  }
+};
+
+// the checks of a rt_ray_batch every entry point that takes one makes; before any HIP call
+inline int rt_check_ray_batch(const rt_ray_batch* b, const char* fn) {
+  if (!b) return fail(RT_ERR_INVALID_ARG, "%s: null ray batch", fn);
+  if (b->abi_version != RT_ABI_VERSION)
+    return fail(RT_ERR_INVALID_ARG, "%s: rt_ray_batch.abi_version %u != %u", fn, b->abi_version, RT_ABI_VERSION);
+  if (b->n_rays && (!b->origin || !b->direction)) return fail(RT_ERR_INVALID_ARG, "%s: origin / direction missing", fn);
+  return RT_OK;
+}
+
 // what the ray counts of a frame with secondary rays depend on (besides the scene): a frame with the key of the last
 // verified frame renders without a synchronisation
 struct StreamKey {

@@ -556,9 +556,10 @@ __device__ __forceinline__ void shadow_accumulate(Shadow& S, const Mat& m, V3 n,
   S.fb = on ? S.fb + abl : S.fb;
 }
 
-// same for an occluder whose material differs from lane to lane (per-lane walk, rt_hard_kernel)
+// same for an occluder whose material differs from lane to lane (per-lane walk: rt_hard_kernel, the any-hit query); -> the
+// lanes of `h` that count
 template <bool CULL>
-__device__ __forceinline__ void shadow_accumulate_lane(Shadow& S, const Mat& m, V3 n, V3 d, lanemask h) {
+__device__ __forceinline__ lanemask shadow_accumulate_lane(Shadow& S, const Mat& m, V3 n, V3 d, lanemask h) {
   if (CULL) h &= wave_ballot(m.transmissive || dot(d, n) < 0.75f);  // sphere.rs:137-151, triangle.rs:154-168
   S.occ |= h & wave_ballot(!m.transmissive);
   const float io = m.transmissive ? m.opacity * (1.0f - fresnel_reflectance_air_red(m, n, -d)) : 0.0f;
@@ -570,6 +571,7 @@ __device__ __forceinline__ void shadow_accumulate_lane(Shadow& S, const Mat& m, 
   S.fr = on ? S.fr + (uint32_t)__float2uint_rn(ab.x * RT_FILT_SCALE) : S.fr;
   S.fg = on ? S.fg + (uint32_t)__float2uint_rn(ab.y * RT_FILT_SCALE) : S.fg;
   S.fb = on ? S.fb + (uint32_t)__float2uint_rn(ab.z * RT_FILT_SCALE) : S.fb;
+  return h;
 }
 
 struct WaveCtx {
@@ -2785,45 +2787,63 @@ __global__ __launch_bounds__(256, RT_MIN_WAVES) void rt_shade_kernel(RtDevScene 
 // 64 unrelated rays visits thousands.  The samples' contributions are summed over the N lanes in a fixed order and
 // added to the pixel accumulator (linear in the light's share of `direct` and `specular`, :206-209,:251-257).
 // ------------------------------------------------------------------------------------------------
-template <bool CULL>
-__device__ __forceinline__ void shadow_tris_lane(const RtDevScene& sc, lanemask grp, V3 o, V3 d, float tmax, Shadow& S) {
+// The per-lane walk itself, shared with the ray queries (rt_query.h).  The caller supplies what differs between them, as
+// lambdas that are inlined: limit() -> the lane's t limit (a box entered beyond it, slab slack included, is skipped, and
+// tri_hit prunes with it), done() -> the lanes that need nothing more, visit(slot, t, h) with the lanes `h` whose ray hits
+// the triangle in their leaf slot `slot` at `t`.  PAD: every box is widened by `pad` on every side (far_pad, rt_query.h);
+// a compile-time switch, because x + 0.0f does not fold.  The box padding of rt_bvh.cpp and the slab slack here are what
+// make the walk reach every triangle a linear scan would accept.
+template <bool PAD, class Limit, class Done, class Visit>
+__device__ __forceinline__ void walk_tris_lane(const RtDevScene& sc, lanemask grp, V3 o, V3 d, float pad, Limit limit, Done done,
+                                               Visit visit) {
   const BoxRay br = box_ray(o, d);
-  const float tl = t_limit_slack(tmax);
   uint32_t n_exact = 0;
   // entry `node` of the threaded tree: a missed box jumps to its skip link, a hit box steps to the next entry (its
   // first child or -- after a leaf -- the same as its skip link)
   uint32_t node = 0;
   for (;;) {
-    const lanemask live = grp & ~S.occ & wave_ballot(node < sc.n_thr);
+    const lanemask live = grp & ~done() & wave_ballot(node < sc.n_thr);
     if (!live) break;
     const bool on = lane_of(live);
     const uint32_t at = sc.off_nodes_thr + (on ? node : 0u) * 32u;
     const float4 b0 = vload<float4>(sc, at), b1 = vload<float4>(sc, at + 16u);
-    const float lo[3] = {b0.x, b0.y, b0.z}, hi[3] = {b1.x, b1.y, b1.z};
+    float lo[3] = {b0.x, b0.y, b0.z}, hi[3] = {b1.x, b1.y, b1.z};
+    if (PAD)
+      for (int a = 0; a < 3; a++) lo[a] -= pad, hi[a] += pad;
     float tn, tm;
     box_one(lo, hi, br, tn, tm);
     const float slack = __builtin_fmaf(fabsf(tm), 4e-6f, tm + 1e-5f);
-    const lanemask hitbox = live & wave_ballot(tn <= fminf(slack, tl)) & wave_ballot(slack >= 0.0f);
+    const lanemask hitbox = live & wave_ballot(tn <= fminf(slack, t_limit_slack(limit()))) & wave_ballot(slack >= 0.0f);
     const uint32_t leaf = __float_as_uint(b1.w);
     lanemask todo = hitbox & wave_ballot((leaf >> 24) != 0u);
     for (uint32_t k = 0; todo; k++) {  // the triangles of the lanes' leaves, one per lane per round
-      todo &= wave_ballot(k < (leaf >> 24)) & ~S.occ;
+      todo &= wave_ballot(k < (leaf >> 24)) & ~done();
       if (!todo) break;
       const uint32_t slot = lane_of(todo) ? (leaf & 0xFFFFFFu) + k : 0u;
       const float4 q0 = vload<float4>(sc, sc.off_tri_isect + slot * 48u);
       const float4 q1 = vload<float4>(sc, sc.off_tri_isect + slot * 48u + 16u);
       const float4 q2 = vload<float4>(sc, sc.off_tri_isect + slot * 48u + 32u);
       float t;
-      lanemask h = tri_hit(q0, q1, q2, o, d, todo, tmax, t, n_exact);
-      h &= wave_ballot(t <= tmax);
-      if (h) {
-        const float4 sh = vload<float4>(sc, sc.off_tri_shade + slot * 16u);
-        const Mat m = load_mat(sc, lane_of(h) ? __float_as_uint(sh.w) : 0u);
-        shadow_accumulate_lane<CULL>(S, m, mk(sh.x, sh.y, sh.z), d, h);
-      }
+      const lanemask h = tri_hit(q0, q1, q2, o, d, todo, limit(), t, n_exact);
+      visit(slot, t, h);
     }
     node = on ? (lane_of(hitbox) ? node + 1u : __float_as_uint(b0.w)) : node;
   }
+}
+
+// every hit at t <= tmax into S, until the lane is completely occluded; `any` |= the lanes with some hit
+template <bool CULL, bool PAD>
+__device__ __forceinline__ void shadow_tris_lane(const RtDevScene& sc, lanemask grp, V3 o, V3 d, float tmax, float pad, Shadow& S,
+                                                 lanemask& any) {
+  walk_tris_lane<PAD>(
+      sc, grp, o, d, pad, [&]() __attribute__((always_inline)) { return tmax; }, [&]() __attribute__((always_inline)) { return S.occ; },
+      [&](uint32_t slot, float t, lanemask h) __attribute__((always_inline)) {
+        h &= wave_ballot(t <= tmax);
+        if (!h) return;
+        const float4 sh = vload<float4>(sc, sc.off_tri_shade + slot * 16u);
+        const Mat m = load_mat(sc, lane_of(h) ? __float_as_uint(sh.w) : 0u);
+        any |= shadow_accumulate_lane<CULL>(S, m, mk(sh.x, sh.y, sh.z), d, h);
+      });
 }
 
 template <bool CULL>
@@ -2872,7 +2892,8 @@ __device__ __forceinline__ void hard_body(const RtDevScene& sc, const RtDevParam
       shadow_accumulate(S, sm, sn, d, h);
     }
   }
-  shadow_tris_lane<CULL>(sc, grp, so, d, tmax, S);
+  lanemask any = 0ull;  // (the lanes with some hit: only the any-hit query reports them)
+  shadow_tris_lane<CULL, false>(sc, grp, so, d, tmax, 0.0f, S, any);
   // the sample's colour terms: the function the render kernels call (light_sample_terms), then the pair's chain over its
   // N samples in sample order -- run by every lane of the pair on values fetched from the sample lanes, so that the sum
   // is the same bits as the inline loop's

@@ -10,8 +10,8 @@
 // One lane per ray.  A query batch can be arbitrary (picking rays, probes, segments between unrelated points), and the
 // render's wave-cooperative walk (nearest_hit) visits the union of the wavefront's nodes -- thousands for 64 unrelated
 // rays, against ~50 for one lane alone (rt_hard_kernel).  So every lane walks the threaded copy of the tree (RtThrNode:
-// depth first, skip links, no stack) for its own ray with per-lane vector loads, as shadow_tris_lane does; spheres are
-// few and are tested by the whole wavefront one after the other (a loop that is uniform across the wavefront).
+// depth first, skip links, no stack) for its own ray with per-lane vector loads -- walk_tris_lane, the walk rt_hard_kernel
+// runs; spheres are few and are tested by the whole wavefront one after the other (a loop that is uniform across the wavefront).
 //
 // Far origins.  The BVH boxes are padded for the rounding of rays that start in or near the scene (rt_bvh.cpp): 2e-5 +
 // 1e-4 of the triangle's extent + 4 ulp of its coordinates.  The literal triangle test's own rounding reaches past the
@@ -25,31 +25,31 @@
 // inf components) or a non-finite origin makes a dead ray -- a miss, and for the any-hit query "no intersection,
 // opacity 1, filter 1".  The reference's triangle arithmetic would accept NaN / inf "hits" for such rays.
 
-// the ray of lane `i`: origin and the direction as Ray::new_with_mask normalises it (ray.rs:52-57)
-__device__ __forceinline__ bool query_ray(const RtQueryArgs& q, uint32_t i, bool have, V3& o, V3& d) {
+// ray `i` of a caller's batch as it lies in memory (zeros in a lane without one: 12 bytes per lane and array, contiguous
+// across the wavefront), and the test of its origin: a non-finite origin makes a dead ray
+__device__ __forceinline__ void load_ray(const float* origin, const float* direction, uint32_t i, bool have, V3& o, V3& d_raw) {
   o = mk(0.0f, 0.0f, 0.0f);
-  V3 dr = mk(0.0f, 0.0f, 0.0f);
+  d_raw = mk(0.0f, 0.0f, 0.0f);
   if (have) {
     const size_t k = 3u * (size_t)i;
-    o = mk(q.origin[k], q.origin[k + 1], q.origin[k + 2]);
-    dr = mk(q.direction[k], q.direction[k + 1], q.direction[k + 2]);
+    o = mk(origin[k], origin[k + 1], origin[k + 2]);
+    d_raw = mk(direction[k], direction[k + 1], direction[k + 2]);
   }
+}
+__device__ __forceinline__ bool finite_origin(V3 o) {
+  return fabsf(o.x) <= 3.4028235e38f && fabsf(o.y) <= 3.4028235e38f && fabsf(o.z) <= 3.4028235e38f;
+}
+
+// the ray of lane `i`: origin and the direction as Ray::new_with_mask normalises it (ray.rs:52-57)
+__device__ __forceinline__ bool query_ray(const RtQueryArgs& q, uint32_t i, bool have, V3& o, V3& d) {
+  V3 dr;
+  load_ray(q.origin, q.direction, i, have, o, dr);
   d = normalize(dr);
-  const bool finite_o = fabsf(o.x) <= 3.4028235e38f && fabsf(o.y) <= 3.4028235e38f && fabsf(o.z) <= 3.4028235e38f;
+  const bool finite_o = finite_origin(o);
   return have && finite_o && !has_nan(d);
 }
 
 __device__ __forceinline__ float far_pad(V3 o) { return 8e-6f * ((fabsf(o.x) + fabsf(o.y)) + fabsf(o.z)); }
-
-// entry `node` of the threaded tree against the lane's ray, its box widened by `pad`: hit if the box is entered before
-// min(its exit, tl) (both with the slab test's slack)
-__device__ __forceinline__ bool query_box(const float4 b0, const float4 b1, const BoxRay& br, float pad, float tl) {
-  const float lo[3] = {b0.x - pad, b0.y - pad, b0.z - pad}, hi[3] = {b1.x + pad, b1.y + pad, b1.z + pad};
-  float tn, tm;
-  box_one(lo, hi, br, tn, tm);
-  const float slack = __builtin_fmaf(fabsf(tm), 4e-6f, tm + 1e-5f);
-  return tn <= fminf(slack, tl) && slack >= 0.0f;
-}
 
 // ---- nearest hit (cast_ray) --------------------------------------------------------------------------------------
 // The triangles of the lane's own walk.  A box whose entry lies beyond the lane's best t (plus the slab slack) is
@@ -58,43 +58,23 @@ __device__ __forceinline__ bool query_box(const float4 b0, const float4 b1, cons
 // triangle into the leaves: each gives the same t and id, and the tie rule keeps the first.
 template <bool CULL>
 __device__ __forceinline__ void nearest_tris_lane(const RtDevScene& sc, lanemask grp, V3 o, V3 d, float pad, Hit& best) {
-  const BoxRay br = box_ray(o, d);
   const int tri_base = (int)sc.n_spheres;
-  uint32_t n_exact = 0;
-  uint32_t node = 0;
-  for (;;) {
-    const lanemask live = grp & wave_ballot(node < sc.n_thr);
-    if (!live) break;
-    const bool on = lane_of(live);
-    const uint32_t at = sc.off_nodes_thr + (on ? node : 0u) * 32u;
-    const float4 b0 = vload<float4>(sc, at), b1 = vload<float4>(sc, at + 16u);
-    const lanemask hitbox = live & wave_ballot(query_box(b0, b1, br, pad, t_limit_slack(best.t)));
-    const uint32_t leaf = __float_as_uint(b1.w);
-    lanemask todo = hitbox & wave_ballot((leaf >> 24) != 0u);
-    for (uint32_t k = 0; todo; k++) {  // the triangles of the lanes' leaves, one per lane per round
-      todo &= wave_ballot(k < (leaf >> 24));
-      if (!todo) break;
-      const uint32_t slot = lane_of(todo) ? (leaf & 0xFFFFFFu) + k : 0u;
-      const float4 q0 = vload<float4>(sc, sc.off_tri_isect + slot * 48u);
-      const float4 q1 = vload<float4>(sc, sc.off_tri_isect + slot * 48u + 16u);
-      const float4 q2 = vload<float4>(sc, sc.off_tri_isect + slot * 48u + 32u);
-      float t;
-      lanemask h = tri_hit(q0, q1, q2, o, d, todo, best.t, t, n_exact);
-      if (CULL && h) {  // triangle.rs:154-168
-        const float4 sh = vload<float4>(sc, sc.off_tri_shade + slot * 16u);
-        const Mat m = load_mat(sc, lane_of(h) ? __float_as_uint(sh.w) : 0u);
-        h &= wave_ballot(m.transmissive || dot(d, mk(sh.x, sh.y, sh.z)) < 0.75f);
-      }
-      if (h) {
+  walk_tris_lane<true>(
+      sc, grp, o, d, pad, [&]() __attribute__((always_inline)) { return best.t; }, []() __attribute__((always_inline)) { return (lanemask)0; },
+      [&](uint32_t slot, float t, lanemask h) __attribute__((always_inline)) {
+        if (!h) return;
+        if (CULL) {  // triangle.rs:154-168
+          const float4 sh = vload<float4>(sc, sc.off_tri_shade + slot * 16u);
+          const Mat m = load_mat(sc, lane_of(h) ? __float_as_uint(sh.w) : 0u);
+          h &= wave_ballot(m.transmissive || dot(d, mk(sh.x, sh.y, sh.z)) < 0.75f);
+        }
+        if (!h) return;
         const int id = tri_base + (int)(vload<uint32_t>(sc, sc.off_tri_id + slot * 4u) & RT_TRI_INDEX_MASK);
         if (lane_of(h) && (t < best.t || (t == best.t && id > best.id))) {
           best.t = t;
           best.id = id;
         }
-      }
-    }
-    node = on ? (lane_of(hitbox) ? node + 1u : __float_as_uint(b0.w)) : node;
-  }
+      });
 }
 
 template <bool CULL>
@@ -145,45 +125,6 @@ __device__ __forceinline__ void query_nearest_body(const RtDevScene& sc, const R
 // unspecified from then on (the reference stops at its first opaque hit in object order).  Split clipping duplicates
 // only opaque triangles (rt_api.cpp: transmissive ones are never split), and an opaque hit is idempotent here.
 template <bool CULL>
-__device__ __forceinline__ void any_tris_lane(const RtDevScene& sc, lanemask grp, V3 o, V3 d, float tmax, float pad, Shadow& S,
-                                              lanemask& any) {
-  const BoxRay br = box_ray(o, d);
-  const float tl = t_limit_slack(tmax);
-  uint32_t n_exact = 0;
-  uint32_t node = 0;
-  for (;;) {
-    const lanemask live = grp & ~S.occ & wave_ballot(node < sc.n_thr);
-    if (!live) break;
-    const bool on = lane_of(live);
-    const uint32_t at = sc.off_nodes_thr + (on ? node : 0u) * 32u;
-    const float4 b0 = vload<float4>(sc, at), b1 = vload<float4>(sc, at + 16u);
-    const lanemask hitbox = live & wave_ballot(query_box(b0, b1, br, pad, tl));
-    const uint32_t leaf = __float_as_uint(b1.w);
-    lanemask todo = hitbox & wave_ballot((leaf >> 24) != 0u);
-    for (uint32_t k = 0; todo; k++) {
-      todo &= wave_ballot(k < (leaf >> 24)) & ~S.occ;
-      if (!todo) break;
-      const uint32_t slot = lane_of(todo) ? (leaf & 0xFFFFFFu) + k : 0u;
-      const float4 q0 = vload<float4>(sc, sc.off_tri_isect + slot * 48u);
-      const float4 q1 = vload<float4>(sc, sc.off_tri_isect + slot * 48u + 16u);
-      const float4 q2 = vload<float4>(sc, sc.off_tri_isect + slot * 48u + 32u);
-      float t;
-      lanemask h = tri_hit(q0, q1, q2, o, d, todo, tmax, t, n_exact);
-      h &= wave_ballot(t <= tmax);
-      if (h) {
-        const float4 sh = vload<float4>(sc, sc.off_tri_shade + slot * 16u);
-        const Mat m = load_mat(sc, lane_of(h) ? __float_as_uint(sh.w) : 0u);
-        const V3 n = mk(sh.x, sh.y, sh.z);
-        if (CULL) h &= wave_ballot(m.transmissive || dot(d, n) < 0.75f);  // triangle.rs:154-168
-        any |= h;
-        shadow_accumulate_lane<false>(S, m, n, d, h);
-      }
-    }
-    node = on ? (lane_of(hitbox) ? node + 1u : __float_as_uint(b0.w)) : node;
-  }
-}
-
-template <bool CULL>
 __device__ __forceinline__ void query_any_body(const RtDevScene& sc, const RtQueryArgs& q, uint32_t i, bool have) {
   V3 o, d;
   bool alive = query_ray(q, i, have, o, d);
@@ -208,7 +149,7 @@ __device__ __forceinline__ void query_any_body(const RtDevScene& sc, const RtQue
         shadow_accumulate(S, m, n, d, h);
       }
     }
-    if (sc.n_triangles) any_tris_lane<CULL>(sc, grp, o, d, tmax, far_pad(o), S, any);
+    if (sc.n_triangles) shadow_tris_lane<CULL, true>(sc, grp, o, d, tmax, far_pad(o), S, any);
   }
   if (!have) return;
   const bool occ = lane_of(S.occ);

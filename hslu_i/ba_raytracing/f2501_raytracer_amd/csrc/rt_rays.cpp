@@ -32,15 +32,11 @@ struct rt_ray_order {
 
 namespace {
 
-size_t pad256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
-
 int check_order_batch(const rt_ray_order* o, const rt_ray_batch* b, const char* fn) {
   if (!o) return fail(RT_ERR_INVALID_ARG, "%s: null ray order", fn);
-  if (!b) return fail(RT_ERR_INVALID_ARG, "%s: null ray batch", fn);
-  if (b->abi_version != RT_ABI_VERSION)
-    return fail(RT_ERR_INVALID_ARG, "%s: rt_ray_batch.abi_version %u != %u", fn, b->abi_version, RT_ABI_VERSION);
+  const int rc = rt_check_ray_batch(b, fn);
+  if (rc != RT_OK) return rc;
   if (b->n_rays > o->capacity) return fail(RT_ERR_INVALID_ARG, "%s: %u rays exceed the order's capacity of %u", fn, b->n_rays, o->capacity);
-  if (b->n_rays && (!b->origin || !b->direction)) return fail(RT_ERR_INVALID_ARG, "%s: origin / direction missing", fn);
   return RT_OK;
 }
 
@@ -83,17 +79,16 @@ bool any_plane(const rt_ray_radiance* o) { return o && (o->rgb || o->valid || o-
 int check_call(const rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, const char* fn, rt_params* q) {
   if (!s) return fail(RT_ERR_INVALID_ARG, "%s: null scene", fn);
   if (!p) return fail(RT_ERR_INVALID_ARG, "%s: null shading parameters", fn);
-  if (!b) return fail(RT_ERR_INVALID_ARG, "%s: null ray batch", fn);
-  if (!out) return fail(RT_ERR_INVALID_ARG, "%s: null output struct", fn);
-  if (p->abi_version != RT_ABI_VERSION)
+  // (b &&: a null batch is reported before these, by rt_check_ray_batch)
+  if (b && !out) return fail(RT_ERR_INVALID_ARG, "%s: null output struct", fn);
+  if (b && p->abi_version != RT_ABI_VERSION)
     return fail(RT_ERR_INVALID_ARG, "%s: rt_params.abi_version %u != %u", fn, p->abi_version, RT_ABI_VERSION);
-  if (b->abi_version != RT_ABI_VERSION)
-    return fail(RT_ERR_INVALID_ARG, "%s: rt_ray_batch.abi_version %u != %u", fn, b->abi_version, RT_ABI_VERSION);
+  int rc = rt_check_ray_batch(b, fn);
+  if (rc != RT_OK) return rc;
   if (b->max_distance) return fail(RT_ERR_INVALID_ARG, "%s: rt_ray_batch.max_distance must be NULL (a radiance ray has no length limit)", fn);
   if (b->flags) return fail(RT_ERR_INVALID_ARG, "%s: rt_ray_batch.flags must be 0 (backface culling comes from the shading flags)", fn);
   if (p->flags & RT_FLAG_ANTI_ALIASING)
     return fail(RT_ERR_INVALID_ARG, "%s: RT_FLAG_ANTI_ALIASING in the shading flags (the caller supplies its samples as rays)", fn);
-  if (b->n_rays && (!b->origin || !b->direction)) return fail(RT_ERR_INVALID_ARG, "%s: origin / direction missing", fn);
   if (!any_plane(out)) return fail(RT_ERR_INVALID_ARG, "%s: every output plane is NULL", fn);
   *q = *p;
   q->width = b->n_rays ? b->n_rays : 1u, q->height = 1u;
@@ -102,7 +97,7 @@ int check_call(const rt_scene* s, const rt_params* p, const rt_ray_batch* b, con
   q->tile_size = 0, q->n_ranks = 0, q->rank = 0;
   // ignored for ray batches: the merged-level and phase kernels and the tile order belong to the camera
   q->tuning.levels = RT_LEVELS_CHAINED, q->tuning.phases = RT_PHASES_FUSED, q->tuning.tile_order = RT_TILE_ORDER_DEFAULT, q->tuning.no_aa_dedup = 0;
-  const int rc = rt_validate_params(q);  // clouds, depths, tuning ranges; "frame too large" = more than 2^31 - 1 rays
+  rc = rt_validate_params(q);  // clouds, depths, tuning ranges; "frame too large" = more than 2^31 - 1 rays
   if (rc != RT_OK) return rc;
   if ((q->flags & (RT_FLAG_REFLECTIONS | RT_FLAG_REFRACTIONS)) && q->max_depth_reflection == 0 && q->max_depth_refraction == 0)
     return fail(RT_ERR_INVALID_ARG, "%s: secondary rays enabled with depth 0", fn);
@@ -118,31 +113,12 @@ RtRayArgs args_of(const rt_ray_batch* b, const rt_ray_radiance* o, const rt_ray_
   return r;
 }
 
-struct Staging {  // one device allocation for a host call: inputs, then every requested plane (256-byte aligned each)
-  DevBuf buf;
-  size_t used = 0;
-  static size_t pad(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
-  char* take(size_t bytes) {
-    char* p = (char*)buf.p + used;
-    used += pad(bytes);
-    return p;
-  }
-  ~Staging() { buf.release(); }
-};
-
-struct Plane {  // a host output plane and its device twin
-  void* host;
-  void** dev;
-  size_t bytes;
-  bool upload;  // argb: a miss leaves the caller's value, so the caller's plane goes up first
-};
-
 // the device memory of an order for `capacity` rays on the current device
 int order_alloc(rt_ray_order* o) {
-  const size_t per = pad256((size_t)o->capacity * 4);
+  const size_t per = rt_pad256((size_t)o->capacity * 4);
   const size_t n_tiles = ((size_t)o->capacity + RT_ORDER_TILE - 1u) / RT_ORDER_TILE;
-  const size_t sums = pad256(RT_ORDER_SCAN_BLOCKS * 4);
-  const size_t hist = pad256(256u * n_tiles * 4), partial = pad256(RT_ORDER_BOUNDS_WGS * sizeof(RtKeyBounds)), frame = pad256(sizeof(RtKeyFrame));
+  const size_t sums = rt_pad256(RT_ORDER_SCAN_BLOCKS * 4);
+  const size_t hist = rt_pad256(256u * n_tiles * 4), partial = rt_pad256(RT_ORDER_BOUNDS_WGS * sizeof(RtKeyBounds)), frame = rt_pad256(sizeof(RtKeyFrame));
   int rc = o->buf.ensure(5 * per + hist + sums + partial + frame);
   if (rc != RT_OK) return rc;
   char* p = (char*)o->buf.p;
@@ -191,44 +167,27 @@ int trace_host(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_
     order = own.o;
   }
   RtRayArgs r = args_of(b, out, order);
-  Plane planes[5];
-  int np = 0;
-  if (out->rgb) planes[np++] = {out->rgb, (void**)&r.rgb, n * 12, false};
-  if (out->valid) planes[np++] = {out->valid, (void**)&r.valid, n, false};
-  if (out->id) planes[np++] = {out->id, (void**)&r.id, n * 4, false};
-  if (out->t) planes[np++] = {out->t, (void**)&r.t, n * 4, false};
-  if (out->argb) planes[np++] = {out->argb, (void**)&r.argb, n * 4, true};
-  size_t total = 2 * Staging::pad(n * 12);
-  for (int k = 0; k < np; k++) total += Staging::pad(planes[k].bytes);
-  Staging st;
-  if ((rc = st.buf.ensure(total)) != RT_OK) return rc;
-  float* d_o = (float*)st.take(n * 12);
-  float* d_d = (float*)st.take(n * 12);
-  for (int k = 0; k < np; k++) *planes[k].dev = st.take(planes[k].bytes);
-  r.origin = d_o, r.direction = d_d;
-  // a private stream: the call neither waits for nor delays work the caller has on the null stream
-  hipStream_t stream = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  struct StreamGuard {  // (the scene remembers streams -- of table uploads, of its frame slots: not this one, once it is gone)
+  HostCall c;  // (declared behind `own`: the stream drains before the call's order is freed)
+  c.in(&r.origin, n * 12), c.in(&r.direction, n * 12);
+  c.out(&r.rgb, n * 12), c.out(&r.valid, n), c.out(&r.id, n * 4), c.out(&r.t, n * 4), c.out(&r.argb, n * 4, true);
+  struct Forget {  // the scene remembers streams -- of table uploads, of its frame slots: not this one, once it is gone
     rt_scene* scene;
-    hipStream_t s;
-    ~StreamGuard() { (void)hipStreamSynchronize(s), rt_scene_forget_stream(scene, s), (void)hipStreamDestroy(s); }
-  } guard{s, stream};  // (declared behind `own`: the stream drains before the call's order is freed)
+    HostCall& c;
+    ~Forget() {
+      if (c.stream) (void)hipStreamSynchronize(c.stream), rt_scene_forget_stream(scene, c.stream);
+    }
+  } forget{s, c};
   EventPair ev;
   HIP_TRY(hipEventCreate(&ev.e0));
   HIP_TRY(hipEventCreate(&ev.e1));
-  HIP_TRY(hipMemcpyAsync(d_o, b->origin, n * 12, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_d, b->direction, n * 12, hipMemcpyHostToDevice, stream));
-  for (int k = 0; k < np; k++)
-    if (planes[k].upload) HIP_TRY(hipMemcpyAsync(*planes[k].dev, planes[k].host, planes[k].bytes, hipMemcpyHostToDevice, stream));
+  if ((rc = c.begin()) != RT_OK) return rc;
   // an order another stream is still building: this stream waits for it
-  if (order && !build_one && order->build_pending) HIP_TRY(hipStreamWaitEvent(stream, order->built_ev, 0));
-  HIP_TRY(hipEventRecord(ev.e0, stream));
-  if (build_one && (rc = order_enqueue(own.o, d_o, d_d, b->n_rays, stream)) != RT_OK) return rc;
-  if ((rc = rt_trace_rays_enqueue(s, &q, r, stream)) != RT_OK) return rc;
-  HIP_TRY(hipEventRecord(ev.e1, stream));
-  for (int k = 0; k < np; k++) HIP_TRY(hipMemcpyAsync(planes[k].host, *planes[k].dev, planes[k].bytes, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+  if (order && !build_one && order->build_pending) HIP_TRY(hipStreamWaitEvent(c.stream, order->built_ev, 0));
+  HIP_TRY(hipEventRecord(ev.e0, c.stream));
+  if (build_one && (rc = order_enqueue(own.o, r.origin, r.direction, b->n_rays, c.stream)) != RT_OK) return rc;
+  if ((rc = rt_trace_rays_enqueue(s, &q, r, c.stream)) != RT_OK) return rc;
+  HIP_TRY(hipEventRecord(ev.e1, c.stream));
+  if ((rc = c.finish()) != RT_OK) return rc;
   if (stats) {
     if ((rc = rt_render_collect_stats(s, stats)) != RT_OK) return rc;
     float ms = 0.f;
@@ -316,25 +275,17 @@ int rt_ray_order_build(rt_ray_order* o, const rt_ray_batch* b) {
   if ((rc = order_wait(o)) != RT_OK) return rc;
   const size_t n = b->n_rays;
   if (n == 0) return order_enqueue(o, nullptr, nullptr, 0, nullptr);
-  Staging st;
-  if ((rc = st.buf.ensure(2 * Staging::pad(n * 12))) != RT_OK) return rc;
-  float* d_o = (float*)st.take(n * 12);
-  float* d_d = (float*)st.take(n * 12);
-  hipStream_t stream = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  struct StreamGuard {
-    hipStream_t s;
-    ~StreamGuard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
-  } guard{stream};
+  const float *d_o = b->origin, *d_d = b->direction;
+  HostCall c;
+  c.in(&d_o, n * 12), c.in(&d_d, n * 12);
   EventPair ev;
   HIP_TRY(hipEventCreate(&ev.e0));
   HIP_TRY(hipEventCreate(&ev.e1));
-  HIP_TRY(hipMemcpyAsync(d_o, b->origin, n * 12, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_d, b->direction, n * 12, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipEventRecord(ev.e0, stream));
-  if ((rc = order_enqueue(o, d_o, d_d, b->n_rays, stream)) != RT_OK) return rc;
-  HIP_TRY(hipEventRecord(ev.e1, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+  if ((rc = c.begin()) != RT_OK) return rc;
+  HIP_TRY(hipEventRecord(ev.e0, c.stream));
+  if ((rc = order_enqueue(o, d_o, d_d, b->n_rays, c.stream)) != RT_OK) return rc;
+  HIP_TRY(hipEventRecord(ev.e1, c.stream));
+  if ((rc = c.finish()) != RT_OK) return rc;
   o->build_pending = false;
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));

@@ -41,14 +41,8 @@ __device__ __forceinline__ void rays_body(const RtDevScene& sc, const RtDevParam
   const uint32_t i = ray_index(R, ray_slot(P, threadIdx.x));
   const bool have = i < R.n;
   RayIn r;
-  r.o = mk(0.0f, 0.0f, 0.0f);
-  r.d_raw = mk(0.0f, 0.0f, 0.0f);
-  if (have) {  // 12 bytes per lane and array, contiguous across the wavefront
-    const size_t k = 3u * (size_t)i;
-    r.o = mk(R.origin[k], R.origin[k + 1], R.origin[k + 2]);
-    r.d_raw = mk(R.direction[k], R.direction[k + 1], R.direction[k + 2]);
-  }
-  const bool finite_o = fabsf(r.o.x) <= 3.4028235e38f && fabsf(r.o.y) <= 3.4028235e38f && fabsf(r.o.z) <= 3.4028235e38f;
+  load_ray(R.origin, R.direction, i, have, r.o, r.d_raw);
+  const bool finite_o = finite_origin(r.o);
   r.n_start = P.air_ior;
   r.Wt = mk(1.0f, 1.0f, 1.0f);
   r.depth = -1;

@@ -257,24 +257,14 @@ class DeviceScene:
         directions: (n, 3) float32, numpy arrays (the host entry point; numpy results) or torch tensors on this scene's
         device (the _device entry point on torch.cuda.current_stream(); tensor results, no synchronisation)."""
         torch_in, n, o, d, _ = self._batch(origins, directions, None)
-        if torch_in:
-            import torch
-
-            dev = o.device
-            out = RayHits(torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
-                          torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev),
-                          torch.empty(n, dtype=torch.int32, device=dev))
-            ptr = lambda a: a.data_ptr()  # noqa: E731
-        else:
-            out = RayHits(np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32),
-                          np.empty(n, np.uint32))
-            ptr = lambda a: a.ctypes.data  # noqa: E731
+        # (the material rows travel as int32 in a tensor: torch has no uint32 arithmetic; a miss is -1 = 0xFFFFFFFF)
+        out, ptr = self._planes(RayHits, o, n, ("id", "int32", 1), ("t", "float32", 1), ("point", "float32", 3), ("normal", "float32", 3),
+                                ("material", "int32" if torch_in else "uint32", 1))
         b = self._batch_struct(n, o, d, None, backface_culling, ptr)
         h = _abi.rt_ray_hits(ptr(out.id), ptr(out.t), ptr(out.point), ptr(out.normal), ptr(out.material))
         lib = _lib.load()
         if torch_in:
             _lib.check(lib.rt_cast_rays_device(self.handle, C.byref(b), C.byref(h), self._stream_of(o)))
-            # (the material rows travel as int32 in a tensor: torch has no uint32 arithmetic; a miss is -1 = 0xFFFFFFFF)
         else:
             _lib.check(lib.rt_cast_rays(self.handle, C.byref(b), C.byref(h)))
         return out
@@ -283,16 +273,8 @@ class DeviceScene:
         """`Raytracer::has_any_intersection` (raytracer.rs:24-106) for a batch of segments: every hit at t <= max_distance
         (None = +inf) counts.  Same input kinds as cast_rays."""
         torch_in, n, o, d, m = self._batch(origins, directions, max_distance)
-        if torch_in:
-            import torch
-
-            dev = o.device
-            out = IntersectionTest(torch.empty(n, dtype=torch.bool, device=dev), torch.empty(n, dtype=torch.bool, device=dev),
-                                   torch.empty(n, dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev))
-            ptr = lambda a: a.data_ptr()  # noqa: E731
-        else:
-            out = IntersectionTest(np.empty(n, np.bool_), np.empty(n, np.bool_), np.empty(n, np.float32), np.empty((n, 3), np.float32))
-            ptr = lambda a: a.ctypes.data  # noqa: E731
+        out, ptr = self._planes(IntersectionTest, o, n, ("has_intersection", "bool", 1), ("completely_occluded", "bool", 1),
+                                ("combined_opacity", "float32", 1), ("color_filter", "float32", 3))
         b = self._batch_struct(n, o, d, m, backface_culling, ptr)
         oc = _abi.rt_ray_occlusion(ptr(out.has_intersection), ptr(out.completely_occluded), ptr(out.combined_opacity),
                                    ptr(out.color_filter))
@@ -338,22 +320,16 @@ class DeviceScene:
         if self._trace_params is None or self._trace_params[0] != key:
             self._trace_params = (key,) + _abi.make_params(cfg, traversal=traversal, tuning=tuning)
         p = self._trace_params[1]
+        out, ptr = self._planes(Radiance, o, n, ("rgb", "float32", 3), ("valid", "bool", 1), ("id", "int32", 1), ("t", "float32", 1))
         if torch_in:
             import torch
 
-            dev = o.device
-            out = Radiance(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.bool, device=dev),
-                           torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
-            if argb is not None and not (isinstance(argb, torch.Tensor) and argb.dtype == torch.int32 and argb.device == dev and
+            if argb is not None and not (isinstance(argb, torch.Tensor) and argb.dtype == torch.int32 and argb.device == o.device and
                                          tuple(argb.shape) == (n,) and argb.is_contiguous()):
-                raise ValueError(f"argb must be a contiguous int32 tensor of shape ({n},) on {dev}")
-            ptr = lambda a: a.data_ptr()  # noqa: E731
-        else:
-            out = Radiance(np.empty((n, 3), np.float32), np.empty(n, np.bool_), np.empty(n, np.int32), np.empty(n, np.float32))
-            if argb is not None and not (isinstance(argb, np.ndarray) and argb.dtype == np.uint32 and argb.shape == (n,) and
-                                         argb.flags["C_CONTIGUOUS"]):
-                raise ValueError(f"argb must be a contiguous uint32 array of shape ({n},)")
-            ptr = lambda a: a.ctypes.data  # noqa: E731
+                raise ValueError(f"argb must be a contiguous int32 tensor of shape ({n},) on {o.device}")
+        elif argb is not None and not (isinstance(argb, np.ndarray) and argb.dtype == np.uint32 and argb.shape == (n,) and
+                                       argb.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"argb must be a contiguous uint32 array of shape ({n},)")
         b = self._batch_struct(n, o, d, None, False, ptr)
         r = _abi.rt_ray_radiance(ptr(out.rgb), ptr(out.valid), ptr(out.id), ptr(out.t), ptr(argb) if argb is not None else None)
         lib = _lib.load()
@@ -385,6 +361,18 @@ class DeviceScene:
         return out
 
     # (bool arrays and tensors hold one byte per element, 0 or 1: the uint8 planes of rt_ray_occlusion / rt_ray_radiance)
+
+    @staticmethod
+    def _planes(result, like, n, *spec):
+        """-> (result(...), ptr): an entry point's result planes, one per (name, dtype, columns) of `spec`, uninitialised and
+        of the kind of `like` -- numpy arrays, or tensors on its device -- and the function that takes a plane's address."""
+        if isinstance(like, np.ndarray):
+            new, ptr = np.empty, lambda a: a.ctypes.data
+        else:
+            import torch
+
+            new, ptr = lambda shape, dt: torch.empty(shape, dtype=getattr(torch, dt), device=like.device), lambda a: a.data_ptr()
+        return result(**{name: new((n,) if cols == 1 else (n, cols), dt) for name, dt, cols in spec}), ptr
 
     def _batch(self, origins, directions, max_distance):
         """-> (torch?, n, origins, directions, max_distance) validated and contiguous."""

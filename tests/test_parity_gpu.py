@@ -244,11 +244,21 @@ def test_tiny_triangle_counts_single_leaf_bvh(n_tris):
     compare(cfg, flat, None)
 
 
-def test_candidate_overflow_falls_back_to_per_sample_walk():
+SECONDARY = ["high_resolution", "anti_aliasing", "soft_shadows", "reflections"]
+
+
+@pytest.mark.parametrize("features,extra", [
+    (["high_resolution", "anti_aliasing", "soft_shadows"], {}),
+    (SECONDARY, {"depth_override": 2}),
+    (SECONDARY + ["backface_culling"], {"depth_override": 2}),
+], ids=["no_secondary", "deferred_pairs", "deferred_pairs_culling"])
+def test_candidate_overflow_falls_back_to_per_sample_walk(features, extra):
     """Soft shadows share one BVH walk per (wavefront, light); when the candidate list overflows the
     kernel must fall back to a walk per sample with identical results.  rt_tuning.shadow_candidate_cap forces
-    the overflow."""
-    cfg = RenderConfig.from_features(["high_resolution", "anti_aliasing", "soft_shadows"], n_cloud_sets=64)
+    the overflow.  Without secondary rays the fallback runs inside the kernel; with them the overflowing sets are deferred
+    to rt_hard_kernel's per-lane walk (cap 3: every set with more than three candidates; RT_CAND_CAP_NONE: none; the
+    default: only what overflows by itself), with and without backface culling."""
+    cfg = RenderConfig.from_features(features, n_cloud_sets=64, **extra)
     flat = scenes.semesterbild(cfg, "text_lowres").flatten()
     win = (420, 330, 64, 48)
     a_ref, p_ref, s_ref = gpu_render(cfg, flat, win)
