@@ -15,12 +15,15 @@ from hslu_i.ba_raytracing.f2501_raytracer_amd import RenderConfig
 
 SYN_W, SYN_H = 48, 40
 # synthetic cases: features, depth.  c3 = AA (plain table) + soft shadows; c3rand = the anti_aliasing_randomness table;
-# c4 = reflections + refractions, 24 spp, 28 cloud points per light, depth 3 and 8
+# c4 = reflections + refractions, 24 spp, 28 cloud points per light, depth 3 and 8; c3cull / c4d3cull = c3 / c4d3 with
+# back-face culling, on the scene that has something to cull
 SYN_CASES = {
     "c3": (["anti_aliasing", "soft_shadows"], None),
     "c3rand": (["anti_aliasing_randomness", "soft_shadows"], None),
     "c4d3": (["realistic", "extreme_quality"], 3),
     "c4d8": (["realistic", "extreme_quality"], 8),
+    "c3cull": (["anti_aliasing", "soft_shadows", "backface_culling"], None),
+    "c4d3cull": (["realistic", "extreme_quality", "backface_culling"], 3),
 }
 SPEC_NAMES = ("spec_c3", "spec_c3lowres")
 SPEC_PER_WINDOW = 12  # 48 fixed pixels over the four windows
@@ -30,7 +33,7 @@ def syn_workload(key):
     feats, depth = SYN_CASES[key]
     cfg = RenderConfig.from_features(feats, width_override=SYN_W, height_override=SYN_H, depth_override=depth,
                                      n_cloud_sets=64)
-    return cfg, build_scene(cfg, soft=True)
+    return cfg, build_scene(cfg, soft=True, cull=cfg.has("backface_culling"))
 
 
 def syn_pixels():
@@ -91,7 +94,8 @@ def _eval(px):
             pen = bool(((c > 0) & (c < m.N)).any())
         iv = r["iv"]
         out.append(dict(px=(gx, gy), amb=None, id=r["id"], t=r["t"], written=r["written"],
-                        lo=None if iv is None else iv.lo, hi=None if iv is None else iv.hi, pen=pen))
+                        lo=None if iv is None else iv.lo, hi=None if iv is None else iv.hi, nom=None if iv is None else iv.nom,
+                        pen=pen))
     return out
 
 

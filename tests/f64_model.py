@@ -5,7 +5,10 @@ direction for all, weight 1/(8*ceil(n/8)), hit id and t of sample 0), `single_ra
 `PointLight::calculate_contribution_at`, `has_any_intersection` (the opacity / filter chain walked in object order),
 `calculate_reflection`, `calculate_refractions` (depth step and factor from the ray's own opacity, DESIGN D3),
 `compute_fresnel`, distance attenuation, and `to_point_light_cloud` with the seeded set choice of DESIGN D4
-(set = rt_cloud_hash(cloud_seed, pixel, light) % n_cloud_sets, points at L + p * (fw, fh, fd), intensity L[6] / N).
+(set = rt_cloud_hash(cloud_seed, pixel, light) % n_cloud_sets, points at L + p * (fw, fh, fd), intensity L[6] / N),
+back-face culling (sphere.rs:137-151, triangle.rs:154-168: an object is hit only if d . n < 0.75 or its material is
+transmissive, on every kind of ray), and the ray queries on caller-supplied rays (`cast_ray`, `any_intersection`,
+`trace_ray`, with the dead-ray rules of rt_query.h).
 Textbook ray/sphere and Moeller-Trumbore ray/triangle tests instead of the oracle's matrix-inverse form, numpy float64,
 vectorised over objects.  Only the sample tables themselves (`sampling.aa_offsets`, `sampling.cloud_sets`) are taken as
 data.  The oracle is something this model checks, never something it calls.
@@ -40,6 +43,7 @@ M_TIE = 1e-6    # two nearest-hit candidates of different objects closer than th
 M_COS = 1e-6    # cos_i > 0, diff > 0, inside / outside (n . v against 0), unit vectors
 M_TIR = 1e-6    # total internal reflection: sin^2 against 1, refract's k against 0
 M_OP = 1e-9     # |opacity| <= EPS in the shadow chain
+M_CULL = 1e-6   # back-face culling: |d . n - threshold|, unit vectors; a near culling decision is a near hit decision
 MAX_FLIPS = 2   # near objects on one shadow ray evaluated both ways; above this the pixel is dropped
 TOL = 1e-4      # one tolerance on every interval bound (BASELINE north_star bar)
 PAD = 1e-4      # AABB padding of the shadow-ray prefilter (much larger than M_TMAX: the prefilter stays conservative)
@@ -116,9 +120,17 @@ class Model:
     """float64 restatement of the reference pipeline: spheres + triangles + point lights, light clouds, AA, reflections,
     refractions.  `reflections` / `refractions` default to the config's features."""
 
-    def __init__(self, flat, cfg, reflections=None, refractions=None, aa_offsets=None, cloud=None):
-        assert not cfg.has("backface_culling"), "the model has no back-face culling"
+    def __init__(self, flat, cfg, reflections=None, refractions=None, aa_offsets=None, cloud=None, cull=None,
+                 cull_threshold=0.75, cull_exempts_transmissive=True, cull_shadows=True):
+        """cull: back-face culling (sphere.rs:137-151, triangle.rs:154-168), None = the config's feature: an object is hit
+        only if d . n < cull_threshold or its material is transmissive; the sphere's n is the normal at the chosen root, the
+        triangle's its stored normal; shadow rays cull as every other ray does.  cull_threshold, cull_exempts_transmissive
+        and cull_shadows exist so that a test can mutate the model."""
         self.f, self.cfg = flat, cfg
+        self.cull = cfg.has("backface_culling") if cull is None else bool(cull)
+        self.cull_threshold = float(cull_threshold)
+        self.cull_exempts_transmissive = bool(cull_exempts_transmissive)
+        self.cull_shadows = bool(cull_shadows)
         self.refl = cfg.has("reflections") if reflections is None else bool(reflections)
         self.refr = cfg.has("refractions") if refractions is None else bool(refractions)
         self.eps_d = float(cfg.eps_distance)
@@ -184,27 +196,34 @@ class Model:
         return f0v + (1 - f0v) * (1 - c) ** 5, near
 
     # ---- intersections: rays (R,3) x objects ----------------------------------------------------------------------
-    def intersect(self, O, D, idx=None, tmax=None):
-        """-> ids (K,), t (R,K), valid (R,K), near (R,K), objects in object order (spheres, then triangles)."""
+    def intersect(self, O, D, idx=None, tmax=None, cull=None, scale=1.0):
+        """-> ids (K,), t (R,K), valid (R,K), near (R,K), objects in object order (spheres, then triangles).
+        cull None = the model's own setting.  scale: see `coord_scale` (it multiplies M_TMAX)."""
         R = O.shape[0]
         if idx is None:
             idx = np.arange(self.ns + self.nt)
+        cull = self.cull if cull is None else cull
         sid, tid = idx[idx < self.ns], idx[idx >= self.ns] - self.ns
-        ts, vs, ns_ = self._spheres(O, D, sid)
-        tt, vt, nt_ = self._triangles(O, D, tid)
+        ts, vs, ns_ = self._spheres(O, D, sid, cull)
+        tt, vt, nt_ = self._triangles(O, D, tid, cull)
         t = np.concatenate([ts, tt], axis=1)
         valid = np.concatenate([vs, vt], axis=1)
         near = np.concatenate([ns_, nt_], axis=1)
         ids = np.concatenate([sid, tid + self.ns])
         if tmax is not None and ids.size:
             tm = tmax[:, None]
-            c, n = t <= tm, np.abs(tm - t) < M_TMAX
+            c, n = t <= tm, np.abs(tm - t) < M_TMAX * scale
             near = (valid & n) | (near & (c | n))
             valid = valid & c
         assert t.shape == (R, ids.size)
         return ids, t, valid, near
 
-    def _spheres(self, O, D, sid):
+    def _kept(self, dn, oid):
+        """the culling rule as a condition of _decide: (kept, near) for d . n of shape (R, K) and object ids (K,)"""
+        ex = (self.obj_tr[oid] if self.cull_exempts_transmissive else np.zeros(oid.size, bool))[None]
+        return (dn < self.cull_threshold) | ex, (np.abs(dn - self.cull_threshold) < M_CULL) & ~ex
+
+    def _spheres(self, O, D, sid, cull=False):
         R = O.shape[0]
         if sid.size == 0:
             z = np.zeros((R, 0))
@@ -221,13 +240,17 @@ class Model:
         ncos = s / r  # |d . n| at either root
         c_disc = (disc >= 0, np.abs(disc) < M_DISC * (b * b + vv + r2))
         c_t1 = (t1 >= 0, np.abs(t1) * ncos < M_PLANE)
-        valid, near = _decide([c_disc, c_t1])
+        conds = [c_disc, c_t1]
+        if cull:
+            # the normal at the chosen root: d . n = -s / r at the near root (never culled), +s / r at the far one
+            conds.append(self._kept(np.where(t0 >= 0, -ncos, ncos), sid))
+        valid, near = _decide(conds)
         t = np.where(t0 >= 0, t0, t1)
         # the root choice (t0 >= 0) is a decision too: a flip changes t
         near |= valid & (np.abs(t0) * ncos < M_PLANE)
         return t, valid, near
 
-    def _triangles(self, O, D, tid):
+    def _triangles(self, O, D, tid, cull=False):
         R = O.shape[0]
         if tid.size == 0:
             z = np.zeros((R, 0))
@@ -252,17 +275,25 @@ class Model:
                 (v >= 0, np.abs(v) * ad < M_BARY * nqv),
                 (u + v < 1, np.abs(1 - u - v) * ad < M_BARY * (ntv * npv + nqv + ad)),
             ]
+            if cull:
+                conds.append(self._kept(_dot(Dd, self.tn[tid][None]), tid + self.ns))
         valid, near = _decide(conds)
-        return np.where(valid, t, np.inf), valid, near
+        # A near miss keeps its t: fp32 may take it as a hit in front of the nearest one, or on a shadow ray.  Not so the
+        # surface a shadow or child ray starts on (|t| of about eps_distance): the model takes that start to be on the side
+        # it was pushed to, as it always has -- M_PLANE would otherwise call every ray that leaves under 6 degrees near.
+        with np.errstate(invalid="ignore"):
+            keep = valid | (near & (np.abs(t) > 2 * self.eps_d))
+        return np.where(keep, t, np.inf), valid, near
 
     def normal(self, oid, p):
         if oid < self.ns:
             return norm(p - self.sc[oid])
         return self.tn[oid - self.ns]
 
-    def nearest(self, o, d):
+    def nearest(self, o, d, scale=1.0):
         """cast_ray (raytracer.rs): nearest valid hit, ties to the later object.  Raises Ambiguous if the choice is
-        near.  -> (t, id, p, n, material row) or None."""
+        near.  -> (t, id, p, n, material row) or None.  scale: see `coord_scale` (it multiplies M_TIE)."""
+        tie = M_TIE * scale
         ids, t, valid, near = self.intersect(o[None], d[None])
         t, valid, near = t[0], valid[0], near[0]
         tv = np.where(valid, t, np.inf)
@@ -272,10 +303,10 @@ class Model:
             return None
         k = len(tv) - 1 - int(np.argmin(tv[::-1]))  # ties go to the later object
         tb = tv[k]
-        if near[k] or (near & (t <= tb + M_TIE)).any():
+        if near[k] or (near & (t <= tb + tie)).any():
             self.amb("near decision on the nearest hit")
         others = np.delete(tv, k)
-        if others.size and others.min() - tb < M_TIE:
+        if others.size and others.min() - tb < tie:
             self.amb("two objects tie for the nearest hit")
         oid = int(ids[k])
         p = o + d * tb
@@ -309,21 +340,9 @@ class Model:
             filt = np.where(on[:, None], filt - absorb[:, k], filt)
         return occ, op, filt, near
 
-    def shadows(self, p, n, m, view, LP, LC, LI):
-        """calculate_lighting over the expanded light list from hit point p -> (direct Iv, spec Iv, unoccluded (NL,))"""
-        NL = LP.shape[0]
-        self.counts["rays_shadow"] += NL
-        if not self.shade:
-            return None, None, None
-        ltp = LP - p
-        lmag = np.sqrt(_dot(ltp, ltp))
-        ld = ltp / lmag[:, None]
-        so = p + ld * self.eps_d
-        tmax = np.sqrt(_dot(LP - so, LP - so))
-        idx = self._candidates(so, LP)
-        ids, t, valid, near = self.intersect(so, ld, idx, tmax)
-        # per (ray, object) chain terms
-        K = ids.size
+    def _chain_terms(self, so, ld, ids, t, valid, near):
+        """per (ray, object) terms of the chain: the opacity an object lets through (io) and what it absorbs"""
+        NL, K = so.shape[0], ids.size
         io = np.zeros((NL, K))
         absorb = np.zeros((NL, K, 3))
         for k in np.nonzero((valid | near).any(axis=0))[0]:
@@ -337,6 +356,22 @@ class Model:
                     if fn:
                         self.amb("near inside/outside decision on a shadow ray's Fresnel term")
                     io[r, k] = om["opacity"] * (1 - R[0])
+        return io, absorb
+
+    def shadows(self, p, n, m, view, LP, LC, LI):
+        """calculate_lighting over the expanded light list from hit point p -> (direct Iv, spec Iv, unoccluded (NL,))"""
+        NL = LP.shape[0]
+        self.counts["rays_shadow"] += NL
+        if not self.shade:
+            return None, None, None
+        ltp = LP - p
+        lmag = np.sqrt(_dot(ltp, ltp))
+        ld = ltp / lmag[:, None]
+        so = p + ld * self.eps_d
+        tmax = np.sqrt(_dot(LP - so, LP - so))
+        idx = self._candidates(so, LP)
+        ids, t, valid, near = self.intersect(so, ld, idx, tmax, cull=self.cull and self.cull_shadows)
+        io, absorb = self._chain_terms(so, ld, ids, t, valid, near)
         occ, op, filt, opnear = self._chain(ids, valid, io, absorb)
         if opnear.any():
             self.amb("near |opacity| <= EPS decision")
@@ -393,11 +428,12 @@ class Model:
         return Iv(dn, dlo, dhi), Iv(sn, slo, shi), ~occ
 
     # ---- the light list of one pixel (to_point_light_cloud + preprocess, seeded: D4) -------------------------------
-    def light_list(self, gx, gy):
+    def light_list(self, pix):
+        """pix: the index that keys the cloud sets -- the pixel's row-major index in a frame, the ray's index in a batch"""
         L = self.lights
         if self.N == 1:
             return L[:, 0:3].copy(), L[:, 3:6].copy(), L[:, 6].copy()
-        pix = gy * self.cfg.width + gx
+        pix = int(pix)
         lp, lc, li = [], [], []
         for l in range(L.shape[0]):
             s = cloud_hash(int(self.cfg.cloud_seed), pix, l) % self.cloud.shape[0]
@@ -411,16 +447,17 @@ class Model:
     def atten(t):
         return min(max(1.0 / (1 + abs(t) + 0.1 * t * t), 0.0), 1.0)
 
-    def trace(self, o, d_raw, n_start, depth, kind, lights):
+    def trace(self, o, d_raw, n_start, depth, kind, lights, scale=1.0):
         """single_raytrace.  depth None = a primary ray (children start at the configured depths).
-        -> (color Iv, t, id, unoccluded flags of the hit's lights) or None on a miss"""
+        -> (color Iv, t, id, unoccluded flags of the hit's lights) or None on a miss.  scale: `coord_scale` of this ray (its
+        children start on surfaces of the scene)."""
         if depth == 0:
             return None
         d = norm(d_raw)
         if not np.all(np.isfinite(d)):
             return None
         self.counts[kind] += 1
-        h = self.nearest(o, d)
+        h = self.nearest(o, d, scale)
         if h is None:
             return None
         t, oid, p, n, row = h
@@ -482,12 +519,136 @@ class Model:
         spec = spec.scale(a)
         return ((refl + refr + spec) if T else (direct + refl + spec)), t, oid, reach
 
+    # ---- caller-supplied rays (the ray queries: rt_query.h, include/rt_hip.h) -----------------------------------------
+    @staticmethod
+    def _live(o, d_raw):
+        """-> the unit direction, or None for a dead ray: the direction normalises to NaN (zero or non-finite) or the
+        origin is not finite.  A length whose square leaves fp32's range is not decided here."""
+        o, d_raw = np.asarray(o, np.float64), np.asarray(d_raw, np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            d = norm(d_raw)
+        if not np.all(np.isfinite(d)) or not np.all(np.isfinite(o)):
+            return None
+        if not 1e-30 < d_raw @ d_raw < 1e30:
+            raise Ambiguous("|d|^2 near the ends of fp32's range")
+        return d
+
+    @staticmethod
+    def coord_scale(o):
+        """The margins in scene units (M_TIE, M_TMAX) are stated for coordinates of order 1, where fp32 resolves 1e-7: the
+        render's rays start in the frame or on a surface.  A caller's ray may start 100 extents away, and the fp32 error of
+        every t on it grows with its coordinates: those margins are multiplied by max(1, |o|_inf)."""
+        return max(1.0, float(np.abs(o).max()))
+
+    def hit_error(self, o, d, oid, t, n):
+        """First-order bound of the fp32 error of a hit's t and position: the rounding of the coordinates it is computed
+        from, (|o|_inf + t) eps, and for a sphere the rounding of the discriminant's terms, eps (b^2 + |v|^2 + r^2) / 2s
+        (s the half chord r |d . n|), both over |d . n|."""
+        dn = max(abs(float(d @ n)), 1e-300)
+        e = (float(np.abs(o).max()) + t) * EPS / dn
+        if oid < self.ns:
+            v = o - self.sc[oid]
+            b = d @ v
+            e += EPS * (b * b + v @ v + self.sr2[oid]) / (2 * np.sqrt(self.sr2[oid]) * dn)
+        return e
+
+    def _fresnel_conditioned(self, o, d, oid, t):
+        """A caller's ray that meets a glass sphere from afar or at a grazing angle: the sphere's normal carries the hit's
+        position error over r, and Schlick's (1 - c)^5 passes it on with slope 5 (1 - c)^4.  Where that bound exceeds TOL
+        no comparison to TOL can be made: the ray is ambiguous."""
+        if oid >= self.ns or not self.obj_tr[oid]:
+            return
+        p = o + d * t
+        n = self.normal(oid, p)
+        dn_err = self.hit_error(o, d, oid, t, n) / np.sqrt(self.sr2[oid])
+        c = abs(float(d @ n))
+        if 5 * min(1.0, 1 - c + dn_err) ** 4 * dn_err > TOL:
+            self.amb("the fp32 error of a glass sphere's Fresnel term is not small against TOL")
+
+    def cast_ray(self, o, d_raw):
+        """rt_cast_rays for one ray -> (id, t, point, normal, material row), None on a miss (a dead ray misses), or
+        raises Ambiguous."""
+        d = self._live(o, d_raw)
+        if d is None:
+            return None
+        o = np.asarray(o, np.float64)
+        h = self.nearest(o, d, self.coord_scale(o))
+        if h is None:
+            return None
+        t, oid, p, n, row = h
+        return oid, t, p, n, row
+
+    def any_intersection(self, o, d_raw, max_distance=None):
+        """rt_any_intersection for one segment (max_distance None = +inf) -> dict(has, occluded, op=(lo, hi),
+        filt=(lo (3,), hi (3,))) or raises Ambiguous.  The chain is the shadow rays' (_chain); up to MAX_FLIPS near hits
+        are taken both ways, and a ray whose `has` or `occluded` depends on them is ambiguous.  A dead ray, or a NaN or
+        negative max_distance, is no intersection with opacity 1 and filter 1; an occluded ray has opacity 0 and its
+        filter is not defined."""
+        clear = dict(has=False, occluded=False, op=(1.0, 1.0), filt=(np.ones(3), np.ones(3)))
+        d = self._live(o, d_raw)
+        if d is None:
+            return clear
+        tmax = None
+        if max_distance is not None and not np.isposinf(max_distance):
+            if np.isnan(max_distance) or max_distance < 0:
+                return clear
+            tmax = np.array([float(max_distance)])
+        o1 = np.asarray(o, np.float64)
+        o = o1[None]
+        ids, t, valid, near = self.intersect(o, d[None], None, tmax, cull=self.cull and self.cull_shadows,
+                                             scale=self.coord_scale(o1))
+        io, absorb = self._chain_terms(o, d[None], ids, t, valid, near)
+        flips = np.nonzero(near[0])[0]
+        if flips.size > MAX_FLIPS:
+            self.amb(f"{flips.size} near objects on one segment")
+            flips = flips[:0]
+        outs = []
+        for mask in range(1 << flips.size):
+            vr = valid.copy()
+            for j, k in enumerate(flips):
+                if mask >> j & 1:
+                    vr[0, k] = not vr[0, k]
+            occ, op, filt, opnear = self._chain(ids, vr, io, absorb)
+            if opnear.any():
+                self.amb("near |opacity| <= EPS decision")
+            outs.append((bool(vr.any()), bool(occ[0]), 0.0 if occ[0] else float(op[0]), filt[0]))
+        if any(x[:2] != outs[0][:2] for x in outs[1:]):
+            self.amb("a near hit decides has_intersection or completely_occluded")
+        if not all(x[1] for x in outs):
+            for k in np.nonzero(valid[0] | near[0])[0]:
+                self._fresnel_conditioned(o1, d, int(ids[k]), t[0, k])
+        f = np.array([x[3] for x in outs])
+        return dict(has=outs[0][0], occluded=outs[0][1], op=(min(x[2] for x in outs), max(x[2] for x in outs)),
+                    filt=(f.min(axis=0), f.max(axis=0)))
+
+    def trace_ray(self, o, d_raw, index):
+        """rt_trace_rays for ray `index` of a batch (the index keys its light clouds) -> dict(iv, id, t, valid, counts) with
+        the rays this one ray cast, or raises Ambiguous.  The shading starts its shadow and child rays eps_distance off
+        the hit: a hit whose fp32 position error bound (hit_error) exceeds eps_distance leaves them on either side of the
+        surface, and the ray is ambiguous."""
+        miss = dict(iv=None, id=-1, t=np.inf, valid=False, counts=dict.fromkeys(self.counts, 0))
+        d = self._live(o, d_raw)
+        if d is None:
+            return miss
+        o = np.asarray(o, np.float64)
+        scale = self.coord_scale(o)
+        h = self.nearest(o, d, scale)
+        if h is not None:
+            if self.hit_error(o, d, h[1], h[0], h[3]) > self.eps_d:
+                self.amb("the fp32 position error of the hit is not small against eps_distance")
+            self._fresnel_conditioned(o, d, h[1], h[0])
+        self.counts = dict.fromkeys(self.counts, 0)
+        r = self.trace(o, np.asarray(d_raw, np.float64), self.air, None, "rays_primary", self.light_list(index), scale)
+        if r is None:
+            return dict(miss, counts=dict(self.counts))
+        return dict(iv=r[0], id=r[2], t=r[1], valid=True, counts=dict(self.counts))
+
     # ---- one pixel (antialiased_raytrace / render_pixel_colors) ----------------------------------------------------
     def render_pixel(self, gx, gy):
         """-> dict(iv, id, t, written, reach) ; raises Ambiguous"""
         coords = np.array([gx * self.fwhd[0], gy * self.fwhd[1], 0.0])
         D = coords - self.focus
-        lights = self.light_list(gx, gy)
+        lights = self.light_list(gy * self.cfg.width + gx)
         if self.aa is None:
             r = self.trace(coords, D, self.air, None, "rays_primary", lights)
             if r is None:
@@ -532,12 +693,17 @@ class Model:
         return dict(self.counts, pixels_written=written)
 
 
-def build_scene(cfg, soft=False):
+def build_scene(cfg, soft=False, cull=False):
     """The known-answer scene: a wall of two triangles, a glass, an opaque and a metallic sphere, two lights.
     soft=True adds what soft shadows and AA must get right: a glass pane of two triangles sharing an edge, between the
     wall and light 0 and behind the glass sphere (object order differs from t order on its shadow rays, and shadow rays
     cross the shared edge); a third light whose cloud box holds a small opaque sphere (cloud points inside an occluder);
-    a fourth light grazing the wall (cos_i near 0)."""
+    a fourth light grazing the wall (cos_i near 0).
+    cull=True adds what back-face culling decides (d . n against 0.75): an opaque triangle across the lower part of the
+    frame whose stored normal points away from the camera, turned so that d . n of the camera rays crosses 0.75 along it
+    (its right part is culled, its left part is seen from behind); and an opaque triangle between the wall and light 1,
+    turned so that d . n of the shadow rays from the wall to that light crosses 0.75 across the receivers and, where the
+    cloud straddles it, within one light cloud."""
     f32 = np.float32
     sh, sd = float(cfg.scene_height), float(cfg.scene_depth)
     mats = np.asarray([
@@ -572,6 +738,24 @@ def build_scene(cfg, soft=False):
         lights.append([*L2.tolist(), 0.8, 0.85, 1.0, 0.7])
         # light 3 grazing the wall: its cloud straddles the wall's plane
         lights.append([0.9, 0.5 * sh, z - 0.5 * float(box[2]), 1.0, 0.9, 0.7, 0.6])
+    if cull:
+        c41, s41 = 0.75, float(np.sqrt(1 - 0.75 ** 2))
+        # seen from behind: in the plane spanned by a = (c, 0, -s) and y, normal a x y = (s, 0, c)
+        a, p0 = np.array([c41, 0.0, -s41]), np.array([0.5, 0.80 * sh, 0.3 * sd])
+        y = np.array([0.0, 1.0, 0.0])
+        quad = quad + ([tuple(p0 - 0.38 * a - 0.11 * sh * y), tuple(p0 + 0.38 * a - 0.11 * sh * y), tuple(p0 - 0.1 * a + 0.12 * sh * y)],)
+        # the occluder: centred at q on the way from the wall to light 1, its normal 41.4 degrees off that way
+        l1, q = np.asarray(lights[1][:3]), np.array([0.55, 0.30 * sh, 0.5 * sd])
+        u = norm(l1 - q)
+        p = norm(np.cross(u, y))
+        n = c41 * u + s41 * p
+        e_a, e_b = norm(np.cross(n, y)), None
+        e_b = np.cross(n, e_a)
+        tri = [q - 0.17 * e_a - 0.1 * e_b, q + 0.17 * e_a - 0.1 * e_b, q + 0.2 * e_b]
+        if np.cross(tri[1] - tri[0], tri[2] - tri[0]) @ n < 0:
+            tri[1], tri[2] = tri[2], tri[1]
+        quad = quad + ([tuple(v) for v in tri],)
+        tri_mat += [2, 2]
     v1 = np.asarray([q[0] for q in quad], f32)
     e1 = np.asarray([np.subtract(q[1], q[0]) for q in quad], f32)
     e2 = np.asarray([np.subtract(q[2], q[0]) for q in quad], f32)

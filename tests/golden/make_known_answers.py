@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 rng = np.random.default_rng(20250704)
-cases = {"sphere": [], "triangle": [], "fresnel": [], "atten": [], "pack": [], "refract": []}
+cases = {"sphere": [], "triangle": [], "fresnel": [], "atten": [], "pack": [], "refract": [], "cull_sphere": [], "cull_triangle": []}
 
 
 def unit(v):
@@ -195,6 +195,64 @@ for i, n, eta in [
     (unit([0.3, -0.4, 0.7]), unit([0.1, 0.1, -1.0]), 1.13 / 1.000293),
 ]:
     cases["refract"].append(dict(i=i.tolist(), n=n.tolist(), eta=eta, out=refract_truth(i, n, eta)))
+
+# ---- back-face culling (sphere.rs:137-151, triangle.rs:154-168): hit only if d . n < 0.75 or transmissive -------------
+# (no random numbers here: the seeded cases above stay as they are)
+CULL_DN = [-1.0, 0.0, 0.70, 0.74, 0.76, 0.80, 1.0]
+OPAQUE = [1.0, 1.0, 1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+TRANSMISSIVE = [1.0, 1.0, 1.0, 0.0, 0.0, 1.5, 0.5, 0.0, 1.0]
+
+
+def culled(dn, mat):
+    transmissive = mat[8] != 0 and abs(mat[6]) > 1.1920929e-7
+    return not (dn < 0.75 or transmissive)
+
+
+# the triangle above: e1 x e2 = +z is its stored normal.  A ray with d . n = c through the interior point q; c = 0 runs
+# parallel to the plane and misses whatever the material (|det| <= eps), every other ray meets q at t = 1.5
+q = np.array([0.25, 0.25, 2.0])
+for mat_name, mat in (("opaque", OPAQUE), ("transmissive", TRANSMISSIVE)):
+    for c in CULL_DN:
+        s_ = math.sqrt(1 - c * c)
+        d = np.array([s_ * 0.6, s_ * 0.8, c])
+        o = q - 1.5 * d
+        r, det = tri_truth(o, d, *tri)
+        geo = r is not None and r[0] > 1.2e-7 and r[1] >= 0 and r[2] >= 0 and r[1] + r[2] < 1
+        assert geo == (c != 0.0) and (not geo or abs(r[0] - 1.5) < 1e-12)
+        hit = geo and not culled(float(d.dot([0, 0, 1.0])), mat)
+        cases["cull_triangle"].append(dict(material=mat_name, mat=mat, dn=c, o=o.tolist(), d=d.tolist(), v1=tri[0].tolist(),
+                                           v2=tri[1].tolist(), v3=tri[2].tolist(), hit=bool(hit), t=r[0] if hit else None,
+                                           p=(o + r[0] * d).tolist() if hit else None))
+
+# a unit sphere at (0, 0, 3).  From inside the far root is chosen and d . n = c > 0 there: the ray along +z that leaves
+# through the point whose normal has n_z = c, started 0.3 before it.  From outside the near root is chosen and d . n < 0:
+# never culled.  (d . n = 0 is a tangent ray, which fp32 cannot decide; the triangle covers that value.)
+cs = np.array([0.0, 0.0, 3.0])
+dz = np.array([0.0, 0.0, 1.0])
+for mat_name, mat in (("opaque", OPAQUE), ("transmissive", TRANSMISSIVE)):
+    for c in CULL_DN:
+        if c > 0:
+            nrm = np.array([math.sqrt(1 - c * c), 0.0, c])
+            o, where = cs + nrm - 0.3 * dz, "inside"
+        elif c < 0:
+            nrm = np.array([math.sqrt(1 - c * c), 0.0, c])
+            o, where = cs + nrm - 1.0 * dz, "outside"
+        else:
+            continue
+        tr = sphere_truth(o, dz, cs, 1.0)
+        assert tr is not None and abs(tr[2].dot(dz) - c) < 1e-12 and abs(tr[0] - (0.3 if c > 0 else 1.0)) < 1e-12
+        assert (np.linalg.norm(o - cs) < 1) == (where == "inside")
+        hit = not culled(float(tr[2].dot(dz)), mat)
+        cases["cull_sphere"].append(dict(material=mat_name, mat=mat, dn=c, origin=where, o=o.tolist(), d=dz.tolist(), c=cs.tolist(),
+                                         r=1.0, hit=bool(hit), t=tr[0] if hit else None, p=tr[1].tolist() if hit else None,
+                                         n=tr[2].tolist() if hit else None))
+    # one more from outside, oblique: d . n = -0.5
+    nrm = np.array([math.sqrt(0.75), 0.0, -0.5])
+    o = cs + nrm - 1.0 * dz
+    tr = sphere_truth(o, dz, cs, 1.0)
+    assert abs(tr[2].dot(dz) + 0.5) < 1e-12
+    cases["cull_sphere"].append(dict(material=mat_name, mat=mat, dn=-0.5, origin="outside", o=o.tolist(), d=dz.tolist(), c=cs.tolist(),
+                                     r=1.0, hit=True, t=tr[0], p=tr[1].tolist(), n=tr[2].tolist()))
 
 out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "known_answers.json")
 with open(out, "w") as fh:

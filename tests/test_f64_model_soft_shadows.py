@@ -1,7 +1,8 @@
 """Soft shadows and anti-aliasing against the independent float64 model (tests/f64_model.py), on CPU.
 
 The fp32 oracle renders small synthetic scenes at config-3 features (AA with the plain and the randomness table, 10
-cloud points per light) and config-4 features (reflections, refractions, 24 spp, 28 cloud points, depth 3 and 8); every
+cloud points per light) and config-4 features (reflections, refractions, 24 spp, 28 cloud points, depth 3 and 8), and both
+again with back-face culling on a scene where it decides primary and shadow rays; every
 sampled pixel must lie in the model's per-pixel interval widened by TOL, and the ray counters must match exactly.  The
 committed at-spec fixtures spec_c3 / spec_c3lowres are checked on 48 fixed pixels each (hit id, t to 1e-5 relative,
 RGB).  Oracle renders made with a rotated cloud table or y-negated AA offsets must be rejected.
@@ -42,6 +43,20 @@ def test_oracle_synthetic_scene_within_the_float64_intervals(key):
     assert not s["bad"], s["bad"][:5]
     want = fc.model_counts(key)
     assert {k: st[k] for k in STATS} == want
+
+
+@pytest.mark.parametrize("key", [k for k in sorted(fc.SYN_CASES) if k.endswith("cull")])
+def test_culling_decides_a_tenth_of_the_synthetic_lattice(key):
+    """The culling cases say something only if culling changes the picture: the model's nominal colour with culling on
+    and with culling off differ by more than TOL on at least 10 % of the lattice pixels."""
+    on = fc.syn_intervals(key)
+    off = fc.model_intervals("syn", key, fc.syn_pixels(), cull=False)
+    assert [r["px"] for r in on] == [r["px"] for r in off]
+    z = np.zeros(3)
+    differ = sum(1 for a, b in zip(on, off) if a["amb"] is None and b["amb"] is None and
+                 np.abs((z if a["nom"] is None else a["nom"]) - (z if b["nom"] is None else b["nom"])).max() > fc.TOL)
+    print(f"{key}: culling changes {differ} of {len(on)} lattice pixels by more than {fc.TOL:g}")
+    assert differ >= 0.1 * len(on)
 
 
 @pytest.mark.parametrize("name", fc.SPEC_NAMES)

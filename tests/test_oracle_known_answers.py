@@ -23,9 +23,9 @@ def f3(v):
     return a, a.ctypes.data_as(FP)
 
 
-def one_object_scene(sphere=None, tri=None):
+def one_object_scene(sphere=None, tri=None, mat=(1, 1, 1, 0, 0, 1, 0, 0, 0)):
     z3 = np.zeros((0, 3), np.float32)
-    mats = np.asarray([[1, 1, 1, 0, 0, 1, 0, 0, 0]], np.float32)
+    mats = np.asarray([mat], np.float32)
     if sphere is not None:
         c, r = sphere
         r = np.float32(r)
@@ -64,6 +64,43 @@ def test_triangle(oracle, case):
     out = np.zeros(4, np.float32)
     hit = oracle.rt_oracle_triangle(C.byref(desc), 0, op, dp, 0, out.ctypes.data_as(FP))
     assert bool(hit) == case["hit"]
+    if case["hit"]:
+        assert out[0] == pytest.approx(case["t"], rel=5e-5, abs=5e-6)
+        np.testing.assert_allclose(out[1:4], case["p"], atol=2e-5)
+
+
+def _cull_id(case):
+    return f"{case['material']}-{case.get('origin', 'tri')}-dn{case['dn']:g}"
+
+
+@pytest.mark.parametrize("case", KA["cull_sphere"], ids=_cull_id)
+def test_sphere_backface_culling(oracle, case):
+    """cull = 1: an opaque sphere is hit only where d . n < 0.75 at the chosen root (from inside, the far one); a
+    transmissive one always."""
+    desc, keep = one_object_scene(sphere=(case["c"], case["r"]), mat=case["mat"])
+    o, op = f3(case["o"])
+    d, dp = f3(case["d"])
+    out = np.zeros(7, np.float32)
+    hit = oracle.rt_oracle_sphere(C.byref(desc), 0, op, dp, 1, out.ctypes.data_as(FP))
+    assert bool(hit) == case["hit"]
+    assert case["hit"] or case["material"] == "opaque"
+    if case["hit"]:
+        assert out[0] == pytest.approx(case["t"], rel=2e-5, abs=2e-6)
+        np.testing.assert_allclose(out[1:4], case["p"], atol=5e-6)
+        np.testing.assert_allclose(out[4:7], case["n"], atol=2e-5)
+
+
+@pytest.mark.parametrize("case", KA["cull_triangle"], ids=_cull_id)
+def test_triangle_backface_culling(oracle, case):
+    """cull = 1: an opaque triangle is hit only where d . (stored normal) < 0.75; a transmissive one wherever the ray
+    meets it (d . n = 0 runs parallel to it and misses either way)."""
+    desc, keep = one_object_scene(tri=(case["v1"], case["v2"], case["v3"]), mat=case["mat"])
+    o, op = f3(case["o"])
+    d, dp = f3(case["d"])
+    out = np.zeros(4, np.float32)
+    hit = oracle.rt_oracle_triangle(C.byref(desc), 0, op, dp, 1, out.ctypes.data_as(FP))
+    assert bool(hit) == case["hit"]
+    assert case["hit"] or case["material"] == "opaque" or case["dn"] == 0
     if case["hit"]:
         assert out[0] == pytest.approx(case["t"], rel=5e-5, abs=5e-6)
         np.testing.assert_allclose(out[1:4], case["p"], atol=2e-5)
