@@ -157,6 +157,31 @@ class rt_ray_order_info(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+RT_VIEW_PINHOLE, RT_VIEW_REFERENCE = 0, 1
+RT_VIEW_ORDER_ONCE, RT_VIEW_ORDER_ALWAYS, RT_VIEW_ORDER_NONE = 0, 1, 2
+RT_VIEW_MAX_SAMPLES = 64
+
+
+class rt_view_desc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("n_samples", C.c_uint32),
+                ("samples", C.c_void_p), ("order", C.c_uint32)]
+
+
+class rt_view_camera(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("kind", C.c_uint32), ("eye", C.c_float * 3), ("right", C.c_float * 3),
+                ("up", C.c_float * 3), ("forward", C.c_float * 3), ("tan_half_fov_y", C.c_float), ("focus", C.c_float * 3),
+                ("fw", C.c_float), ("fh", C.c_float)]
+
+
+class rt_view_info(C.Structure):
+    _fields_ = [("n_pixels", C.c_uint32), ("n_samples", C.c_uint32), ("n_distinct", C.c_uint32), ("n_rays", C.c_uint32),
+                ("bytes", C.c_uint64), ("order_built", C.c_uint32), ("reserved", C.c_uint32),
+                ("rays_ms", C.c_double), ("order_ms", C.c_double), ("resolve_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 RT_UPDATE_INVALIDATES_RECEIVER_TABLES, RT_UPDATE_INVALIDATES_TILE_COSTS, RT_UPDATE_INVALIDATES_QUEUE_SIZES = 1, 2, 4
 
 

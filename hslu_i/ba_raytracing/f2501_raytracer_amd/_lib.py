@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
-                   rt_scene_desc, rt_scene_info, rt_stats, rt_update_info)
+                   rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_camera, rt_view_desc, rt_view_info)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_HIP_LIB selects a diagnostic build of the same library (tools/, A/B timing); default: in-tree
@@ -20,6 +20,8 @@ EXPORTS = (
     "rt_trace_rays", "rt_trace_rays_device", "rt_scene_update", "rt_scene_update_device",
     "rt_ray_order_create", "rt_ray_order_destroy", "rt_ray_order_build", "rt_ray_order_build_device", "rt_ray_order_set", "rt_ray_order_read",
     "rt_trace_rays_ordered", "rt_trace_rays_ordered_device",
+    "rt_view_create", "rt_view_destroy", "rt_view_set_camera", "rt_view_rays_device", "rt_view_rays", "rt_render_view_device", "rt_render_view",
+    "rt_view_read", "rt_view_rays_model", "rt_view_resolve_model",
 )
 
 _lib = None
@@ -117,6 +119,26 @@ def load():
     lib.rt_trace_rays_ordered_device.restype = C.c_int
     lib.rt_trace_rays_ordered_device.argtypes = [C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_ray_batch), C.c_void_p, C.POINTER(rt_ray_radiance),
                                                  C.c_void_p]
+    lib.rt_view_create.restype = C.c_int
+    lib.rt_view_create.argtypes = [C.POINTER(rt_view_desc), C.c_int, C.POINTER(C.c_void_p)]
+    lib.rt_view_destroy.restype = None
+    lib.rt_view_destroy.argtypes = [C.c_void_p]
+    lib.rt_view_set_camera.restype = C.c_int
+    lib.rt_view_set_camera.argtypes = [C.c_void_p, C.POINTER(rt_view_camera)]
+    lib.rt_view_rays_device.restype = C.c_int
+    lib.rt_view_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_view_rays.restype = C.c_int
+    lib.rt_view_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_render_view_device.restype = C.c_int
+    lib.rt_render_view_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_ray_radiance), C.c_void_p]
+    lib.rt_render_view.restype = C.c_int
+    lib.rt_render_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_ray_radiance), C.POINTER(rt_stats)]
+    lib.rt_view_read.restype = C.c_int
+    lib.rt_view_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_view_info)]
+    lib.rt_view_rays_model.restype = C.c_int
+    lib.rt_view_rays_model.argtypes = [C.POINTER(rt_view_desc), C.POINTER(rt_view_camera), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.rt_view_resolve_model.restype = C.c_int
+    lib.rt_view_resolve_model.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(rt_ray_radiance), C.POINTER(rt_ray_radiance)]
     _lib = lib
     return lib
 

@@ -1,4 +1,6 @@
 """Ray sources for `DeviceScene.trace_rays`: the render's own camera rays, and a pinhole camera anywhere in the scene.
+The same two cameras as `rt_view_camera`s (`view_camera`, `reference_view_camera`) make their rays on the device
+(`renderer.DeviceView`), with the sample offsets of `view_samples`.
 
 The reference has one view, fixed at compile time (`src/lib.rs:81-92`): pixel (x, y) sends a ray from
 `(x * fw, y * fh, 0)` in the direction `origin - RENDER_RAY_FOCUS` (`src/renderer/mod.rs:176-180`,
@@ -13,6 +15,7 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
+from . import _abi, sampling
 from .config import RenderConfig
 
 
@@ -27,6 +30,35 @@ def reference_rays(cfg: RenderConfig) -> Tuple[np.ndarray, np.ndarray]:
     f = cfg.focus
     d = o - np.array([f.x, f.y, f.z], np.float32)
     return o, np.ascontiguousarray(d, np.float32)
+
+
+def _view_camera(kind: int, **members) -> "_abi.rt_view_camera":
+    c = _abi.rt_view_camera()
+    c.abi_version, c.kind = _abi.RT_ABI_VERSION, kind
+    for name, value in members.items():
+        if np.ndim(value):
+            for k in range(3):
+                getattr(c, name)[k] = float(np.float32(value[k]))
+        else:
+            setattr(c, name, float(np.float32(value)))
+    return c
+
+
+def reference_view_camera(cfg: RenderConfig) -> "_abi.rt_view_camera":
+    """The reference's own view (`reference_rays`) as the camera of a DeviceView: RT_VIEW_REFERENCE with cfg's focus, fw, fh."""
+    f = cfg.focus
+    return _view_camera(_abi.RT_VIEW_REFERENCE, focus=(f.x, f.y, f.z), fw=cfg.fw, fh=cfg.fh)
+
+
+def view_samples(cfg: RenderConfig, kind: int) -> np.ndarray:
+    """The configuration's anti-aliasing table as the (n, 2) float32 sample offsets of a DeviceView: `sampling.aa_offsets(cfg)`
+    for RT_VIEW_REFERENCE (scene units); for RT_VIEW_PINHOLE the same offsets in pixels, divided by (fw, fh) in float32."""
+    off = np.ascontiguousarray(sampling.aa_offsets(cfg), np.float32)
+    if kind == _abi.RT_VIEW_REFERENCE:
+        return off
+    if kind != _abi.RT_VIEW_PINHOLE:
+        raise ValueError(f"unknown camera kind {kind}")
+    return np.ascontiguousarray(off / np.array([cfg.fw, cfg.fh], np.float32), np.float32)
 
 
 @dataclass(frozen=True)
@@ -69,6 +101,15 @@ class PinholeCamera:
         sx = (2.0 * px - self.width) / self.height * half  # square pixels: both axes in units of the image height
         sy = (self.height - 2.0 * py) / self.height * half
         return fwd + sx[..., None] * right + sy[..., None] * up
+
+    def view_camera(self) -> "_abi.rt_view_camera":
+        """This camera for a DeviceView (RT_VIEW_PINHOLE): the eye, the basis of `basis()` and tan(fov_y / 2), rounded to
+        float32.  Its width and height belong to the view."""
+        if not 0.0 < self.fov_y_deg < 180.0:
+            raise ValueError("fov_y_deg must lie in (0, 180)")
+        right, up, fwd = self.basis()
+        return _view_camera(_abi.RT_VIEW_PINHOLE, eye=self.eye, right=right, up=up, forward=fwd,
+                            tan_half_fov_y=np.tan(np.radians(self.fov_y_deg) / 2.0))
 
     def rays(self) -> Tuple[np.ndarray, np.ndarray]:
         """One ray through the centre of every pixel."""

@@ -265,6 +265,10 @@ int rt_render_device_staged(rt_scene* s, const rt_params* p, uint32_t* out_dev, 
 int rt_validate_params(const rt_params* p);
 // a ray batch through the frame scheduler (rt_api.cpp; entry points and validation: rt_rays.cpp)
 int rt_trace_rays_enqueue(rt_scene* s, const rt_params* p, const RtRayArgs& r, hipStream_t stream);
+// what rt_trace_rays* refuse in a call, before any HIP call and without looking at the scene (rt_rays.cpp); `fn` names the caller
+int rt_trace_rays_check(const rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, const char* fn);
+// the device memory an order holds (rt_ray_order_info.bytes), readable before the order was ever built (rt_rays.cpp)
+size_t rt_ray_order_bytes(const rt_ray_order* o);
 // `stream` has drained and is about to be destroyed: what the scene enqueued on it is done, and its handle must not be used again
 void rt_scene_forget_stream(rt_scene* s, hipStream_t stream);
 // the ray counters of the frame that used frame slot `slot` of the scene last (rt_scene::cur_block right after a frame

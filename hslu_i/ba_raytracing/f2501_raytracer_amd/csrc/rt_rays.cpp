@@ -200,6 +200,13 @@ int trace_host(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_
 
 }  // namespace
 
+int rt_trace_rays_check(const rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, const char* fn) {
+  rt_params q;
+  return check_call(s, p, b, out, fn, &q);
+}
+
+size_t rt_ray_order_bytes(const rt_ray_order* o) { return o ? o->buf.cap : 0; }
+
 extern "C" {
 
 int rt_trace_rays_device(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, void* hip_stream) {
@@ -316,7 +323,7 @@ int rt_ray_order_read(rt_ray_order* o, uint32_t* perm, uint32_t* keys, rt_ray_or
   if (keys && o->n) HIP_TRY(hipMemcpy(keys, o->ws.keys, (size_t)o->n * 4, hipMemcpyDeviceToHost));
   if (info) {
     *info = rt_ray_order_info{};
-    info->n_rays = o->n, info->bytes = o->buf.cap, info->device_ms = o->device_ms;
+    info->n_rays = o->n, info->bytes = rt_ray_order_bytes(o), info->device_ms = o->device_ms;
     if (o->has_keys && o->n) {
       RtKeyFrame f;
       HIP_TRY(hipMemcpy(&f, o->ws.frame, sizeof(f), hipMemcpyDeviceToHost));

@@ -1,0 +1,337 @@
+// rt_view.cpp -- the host side of device-side camera views (rt_view*, rt_render_view*): validation (before any HIP call),
+// the handle and its one device allocation, the launch sequence generator -> order -> trace -> resolve, the host forms'
+// staging, and the host models of the two formulas (the functions of rt_view.h in loops).
+//
+// A view is built ON TOP of the radiance queries: it makes a ray batch and hands it to rt_ray_order_build_device and
+// rt_trace_rays[_ordered]_device through their public entry points, so every blocking, validation and scene-state rule of a
+// frame is the trace's.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstring>
+
+#include "rt_host.h"
+#include "rt_view.h"
+
+struct rt_view {
+  int device = 0;
+  uint32_t width = 0, height = 0, n_pixels = 0, n_samples = 0, n_distinct = 0, n_rays = 0, order_mode = RT_VIEW_ORDER_ONCE;
+  float distinct[2 * RT_VIEW_MAX_SAMPLES] = {};
+  uint8_t plane_of[RT_VIEW_MAX_SAMPLES] = {};
+  rt_view_desc desc{};  // (samples: not kept)
+  bool has_camera = false;
+  RtViewCam cam{};
+  // one allocation: origin, direction, the per-ray rgb / valid / id / t planes, the two sample tables
+  DevBuf buf;
+  float *origin = nullptr, *direction = nullptr, *rgb = nullptr, *t = nullptr, *distinct_dev = nullptr;
+  uint8_t *valid = nullptr, *plane_of_dev = nullptr;
+  int32_t* id = nullptr;
+  rt_ray_order* order = nullptr;  // capacity n_rays; none with RT_VIEW_ORDER_NONE
+  bool order_built = false;
+  hipEvent_t done_ev = nullptr;  // behind the last work enqueued for this view
+  bool pending = false;
+  hipEvent_t ev[5] = {};         // host form: before / after the generator, after the order, before / after the resolve
+  double rays_ms = 0.0, order_ms = 0.0, resolve_ms = 0.0;
+};
+
+int rt_view_check_desc(const rt_view_desc* d, const char* fn) {
+  if (!d) return fail(RT_ERR_INVALID_ARG, "%s: null view description", fn);
+  if (d->abi_version != RT_ABI_VERSION) return fail(RT_ERR_INVALID_ARG, "%s: rt_view_desc.abi_version %u != %u", fn, d->abi_version, RT_ABI_VERSION);
+  if (d->width == 0 || d->height == 0) return fail(RT_ERR_INVALID_ARG, "%s: empty frame (%u x %u)", fn, d->width, d->height);
+  if (d->n_samples == 0 || d->n_samples > RT_VIEW_MAX_SAMPLES)
+    return fail(RT_ERR_INVALID_ARG, "%s: n_samples %u outside 1 .. %u", fn, d->n_samples, RT_VIEW_MAX_SAMPLES);
+  if (!d->samples) return fail(RT_ERR_INVALID_ARG, "%s: null sample table", fn);
+  if (d->order > RT_VIEW_ORDER_NONE) return fail(RT_ERR_INVALID_ARG, "%s: unknown order mode %u", fn, d->order);
+  for (uint32_t k = 0; k < 2u * d->n_samples; k++)
+    if (!rt_finite(d->samples[k])) return fail(RT_ERR_INVALID_ARG, "%s: sample %u has a non-finite offset", fn, k / 2u);
+  float distinct[2 * RT_VIEW_MAX_SAMPLES];
+  uint8_t plane_of[RT_VIEW_MAX_SAMPLES];
+  const uint64_t n_rays = (uint64_t)rt_view_dedup(d->samples, d->n_samples, distinct, plane_of) * d->width * d->height;
+  if ((uint64_t)d->width * d->height > ((uint64_t)1 << 27) || n_rays > ((uint64_t)1 << 27))
+    return fail(RT_ERR_INVALID_ARG, "%s: %u x %u pixels of distinct samples exceed the 2^27 rays a ray order sorts", fn, d->width, d->height);
+  return RT_OK;
+}
+
+int rt_view_check_camera(const rt_view_camera* c, const char* fn) {
+  if (!c) return fail(RT_ERR_INVALID_ARG, "%s: null camera", fn);
+  if (c->abi_version != RT_ABI_VERSION) return fail(RT_ERR_INVALID_ARG, "%s: rt_view_camera.abi_version %u != %u", fn, c->abi_version, RT_ABI_VERSION);
+  if (c->kind != RT_VIEW_PINHOLE && c->kind != RT_VIEW_REFERENCE) return fail(RT_ERR_INVALID_ARG, "%s: unknown camera kind %u", fn, c->kind);
+  bool finite = rt_finite(c->tan_half_fov_y) && rt_finite(c->fw) && rt_finite(c->fh);
+  for (int k = 0; k < 3; k++)
+    finite = finite && rt_finite(c->eye[k]) && rt_finite(c->right[k]) && rt_finite(c->up[k]) && rt_finite(c->forward[k]) && rt_finite(c->focus[k]);
+  if (!finite) return fail(RT_ERR_INVALID_ARG, "%s: a camera member is not finite", fn);
+  if (c->kind == RT_VIEW_PINHOLE && !(c->tan_half_fov_y > 0.0f))
+    return fail(RT_ERR_INVALID_ARG, "%s: tan_half_fov_y %g must be positive", fn, (double)c->tan_half_fov_y);
+  return RT_OK;
+}
+
+RtViewCam rt_view_cam_of(const rt_view_desc& d, const rt_view_camera& c) {
+  RtViewCam m{};
+  m.kind = c.kind, m.width = d.width, m.height = d.height, m.n_pixels = d.width * d.height;
+  for (int k = 0; k < 3; k++) m.eye[k] = c.eye[k], m.right[k] = c.right[k], m.up[k] = c.up[k], m.forward[k] = c.forward[k], m.focus[k] = c.focus[k];
+  m.tan_half = c.tan_half_fov_y, m.fw = c.fw, m.fh = c.fh;
+  return m;
+}
+
+namespace {
+
+int view_alloc(rt_view* v) {
+  const size_t n = v->n_rays;
+  const size_t b3 = rt_pad256(n * 12), b1 = rt_pad256(n * 4), bv = rt_pad256(n), tab = rt_pad256(sizeof(v->distinct)), po = rt_pad256(sizeof(v->plane_of));
+  int rc = v->buf.ensure(3 * b3 + 2 * b1 + bv + tab + po);
+  if (rc != RT_OK) return rc;
+  char* p = (char*)v->buf.p;
+  v->origin = (float*)p, v->direction = (float*)(p + b3), v->rgb = (float*)(p + 2 * b3);
+  v->id = (int32_t*)(p + 3 * b3), v->t = (float*)(p + 3 * b3 + b1), v->valid = (uint8_t*)(p + 3 * b3 + 2 * b1);
+  v->distinct_dev = (float*)(p + 3 * b3 + 2 * b1 + bv), v->plane_of_dev = (uint8_t*)(p + 3 * b3 + 2 * b1 + bv + tab);
+  HIP_TRY(hipMemcpy(v->distinct_dev, v->distinct, sizeof(v->distinct), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(v->plane_of_dev, v->plane_of, sizeof(v->plane_of), hipMemcpyHostToDevice));
+  HIP_TRY(hipEventCreate(&v->done_ev));
+  for (hipEvent_t& e : v->ev) HIP_TRY(hipEventCreate(&e));
+  if (v->order_mode != RT_VIEW_ORDER_NONE) {
+    rt_ray_order_desc od{};
+    od.abi_version = RT_ABI_VERSION, od.capacity = v->n_rays;
+    if ((rc = rt_ray_order_create(&od, v->device, &v->order)) != RT_OK) return rc;
+  }
+  return RT_OK;
+}
+
+int view_wait(rt_view* v) {
+  if (v->pending) {
+    HIP_TRY(hipEventSynchronize(v->done_ev));
+    v->pending = false;
+  }
+  return RT_OK;
+}
+
+void view_free(rt_view* v) {
+  if (!v) return;
+  (void)hipSetDevice(v->device);
+  if (v->pending) (void)hipEventSynchronize(v->done_ev);
+  rt_ray_order_destroy(v->order);
+  if (v->done_ev) (void)hipEventDestroy(v->done_ev);
+  for (hipEvent_t e : v->ev)
+    if (e) (void)hipEventDestroy(e);
+  v->buf.release();
+  delete v;
+}
+
+int view_mark(rt_view* v, hipStream_t stream) {
+  HIP_TRY(hipEventRecord(v->done_ev, stream));
+  v->pending = true;
+  return RT_OK;
+}
+
+int rays_enqueue(rt_view* v, float* origin, float* direction, hipStream_t stream) {
+  const hipError_t e = (hipError_t)rt_launch_view_rays(v->cam, v->distinct_dev, v->n_distinct, origin, direction, stream);
+  if (e != hipSuccess) return fail(RT_ERR_HIP, "view ray generator launch failed: %s", hipGetErrorString(e));
+  return RT_OK;
+}
+
+// everything a render refuses, before any HIP call; the scene and the view are looked at last
+int check_render(const rt_scene* s, const rt_view* v, const rt_params* p, const rt_ray_radiance* out, const char* fn) {
+  if (!s) return fail(RT_ERR_INVALID_ARG, "%s: null scene", fn);
+  if (!v) return fail(RT_ERR_INVALID_ARG, "%s: null view", fn);
+  if (!p) return fail(RT_ERR_INVALID_ARG, "%s: null shading parameters", fn);
+  if (!out) return fail(RT_ERR_INVALID_ARG, "%s: null output struct", fn);
+  // the trace's own checks of `shading` (a batch of one ray stands in: they do not depend on the batch)
+  static const float one_ray[3] = {0.f, 0.f, 0.f};
+  rt_ray_batch b{};
+  b.abi_version = RT_ABI_VERSION, b.n_rays = 1, b.origin = one_ray, b.direction = one_ray;
+  const int rc = rt_trace_rays_check(s, p, &b, out, fn);
+  if (rc != RT_OK) return rc;
+  if (!v->has_camera) return fail(RT_ERR_INVALID_ARG, "%s: the view has no camera yet (rt_view_set_camera)", fn);
+  // (the trace refuses this too, but behind the generator's launch: a refusal comes before any HIP call)
+  if (s->progress_active) return fail(RT_ERR_INVALID_ARG, "%s: a progressive render owns this scene until rt_render_end", fn);
+  if (v->device != s->device) return fail(RT_ERR_INVALID_ARG, "%s: the view lives on device %d, the scene on device %d", fn, v->device, s->device);
+  return RT_OK;
+}
+
+// generator -> order -> trace -> resolve on `stream`; `out`: DEVICE pixel planes.  timed: record the view's stage events.
+int render_enqueue(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_radiance* out, hipStream_t stream, bool timed) {
+  int rc;
+  if (timed) HIP_TRY(hipEventRecord(v->ev[0], stream));
+  if ((rc = rays_enqueue(v, v->origin, v->direction, stream)) != RT_OK) return rc;
+  if (timed) HIP_TRY(hipEventRecord(v->ev[1], stream));
+  rt_ray_batch b{};
+  b.abi_version = RT_ABI_VERSION, b.n_rays = v->n_rays, b.origin = v->origin, b.direction = v->direction;
+  const bool build = v->order && (v->order_mode == RT_VIEW_ORDER_ALWAYS || !v->order_built);
+  if (build) {
+    if ((rc = rt_ray_order_build_device(v->order, &b, stream)) != RT_OK) return rc;
+    v->order_built = true;
+  }
+  if (timed) HIP_TRY(hipEventRecord(v->ev[2], stream));
+  rt_ray_radiance rays{};
+  rays.rgb = v->rgb, rays.valid = v->valid, rays.id = v->id, rays.t = v->t;
+  rc = v->order ? rt_trace_rays_ordered_device(s, p, &b, v->order, &rays, stream) : rt_trace_rays_device(s, p, &b, &rays, stream);
+  if (rc != RT_OK) return rc;
+  if (timed) HIP_TRY(hipEventRecord(v->ev[3], stream));
+  const hipError_t e = (hipError_t)rt_launch_view_resolve(v->n_pixels, v->n_samples, v->plane_of_dev, v->rgb, v->valid, v->id, v->t, *out, stream);
+  if (e != hipSuccess) return fail(RT_ERR_HIP, "view resolve launch failed: %s", hipGetErrorString(e));
+  if (timed) HIP_TRY(hipEventRecord(v->ev[4], stream));
+  if (timed) v->order_ms = build ? -1.0 : 0.0;  // (-1: read from the events once the stream has drained)
+  return view_mark(v, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_view_create(const rt_view_desc* d, int device, rt_view** out) {
+  if (!d || !out) return fail(RT_ERR_INVALID_ARG, "rt_view_create: null argument");
+  *out = nullptr;
+  int rc = rt_view_check_desc(d, "rt_view_create");
+  if (rc != RT_OK) return rc;
+  const int ndev = rt_device_count();
+  if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
+  if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+  rt_view* v = new rt_view();
+  v->device = device, v->width = d->width, v->height = d->height, v->n_pixels = d->width * d->height, v->n_samples = d->n_samples;
+  v->order_mode = d->order;
+  v->desc = *d, v->desc.samples = nullptr;
+  v->n_distinct = rt_view_dedup(d->samples, d->n_samples, v->distinct, v->plane_of);
+  v->n_rays = v->n_distinct * v->n_pixels;
+  if ((rc = view_alloc(v)) != RT_OK) {
+    view_free(v);
+    return rc;
+  }
+  *out = v;
+  return RT_OK;
+}
+
+void rt_view_destroy(rt_view* v) { view_free(v); }
+
+int rt_view_set_camera(rt_view* v, const rt_view_camera* c) {
+  if (!v) return fail(RT_ERR_INVALID_ARG, "rt_view_set_camera: null view");
+  const int rc = rt_view_check_camera(c, "rt_view_set_camera");
+  if (rc != RT_OK) return rc;
+  v->cam = rt_view_cam_of(v->desc, *c), v->has_camera = true;
+  return RT_OK;
+}
+
+int rt_view_rays_device(rt_view* v, float* origin, float* direction, void* hip_stream) {
+  const char* fn = "rt_view_rays_device";
+  if (!v) return fail(RT_ERR_INVALID_ARG, "%s: null view", fn);
+  if (!origin || !direction) return fail(RT_ERR_INVALID_ARG, "%s: origin / direction missing", fn);
+  if (!v->has_camera) return fail(RT_ERR_INVALID_ARG, "%s: the view has no camera yet (rt_view_set_camera)", fn);
+  HIP_TRY(hipSetDevice(v->device));
+  const int rc = rays_enqueue(v, origin, direction, (hipStream_t)hip_stream);
+  return rc != RT_OK ? rc : view_mark(v, (hipStream_t)hip_stream);
+}
+
+int rt_view_rays(rt_view* v, float* origin, float* direction) {
+  const char* fn = "rt_view_rays";
+  if (!v) return fail(RT_ERR_INVALID_ARG, "%s: null view", fn);
+  if (!origin || !direction) return fail(RT_ERR_INVALID_ARG, "%s: origin / direction missing", fn);
+  if (!v->has_camera) return fail(RT_ERR_INVALID_ARG, "%s: the view has no camera yet (rt_view_set_camera)", fn);
+  HIP_TRY(hipSetDevice(v->device));
+  HostCall c;
+  c.out(&origin, (size_t)v->n_rays * 12), c.out(&direction, (size_t)v->n_rays * 12);
+  int rc = c.begin();
+  if (rc != RT_OK) return rc;
+  if ((rc = rays_enqueue(v, origin, direction, c.stream)) != RT_OK) return rc;
+  return c.finish();
+}
+
+int rt_render_view_device(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_radiance* out, void* hip_stream) {
+  const int rc = check_render(s, v, p, out, "rt_render_view_device");
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return render_enqueue(s, v, p, out, (hipStream_t)hip_stream, false);
+}
+
+int rt_render_view(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_radiance* out, rt_stats* stats) {
+  int rc = check_render(s, v, p, out, "rt_render_view");
+  if (rc != RT_OK) return rc;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = view_wait(v)) != RT_OK) return rc;
+  const auto t_begin = std::chrono::steady_clock::now();
+  const size_t n = v->n_pixels;
+  rt_ray_radiance dev = *out;
+  HostCall c;
+  c.out(&dev.rgb, n * 12), c.out(&dev.valid, n), c.out(&dev.id, n * 4), c.out(&dev.t, n * 4), c.out(&dev.argb, n * 4, true);
+  struct Forget {  // (as rt_trace_rays: the scene must not remember a stream that is gone)
+    rt_scene* scene;
+    HostCall& c;
+    ~Forget() {
+      if (c.stream) (void)hipStreamSynchronize(c.stream), rt_scene_forget_stream(scene, c.stream);
+    }
+  } forget{s, c};
+  if ((rc = c.begin()) != RT_OK) return rc;
+  if ((rc = render_enqueue(s, v, p, &dev, c.stream, true)) != RT_OK) return rc;
+  if ((rc = c.finish()) != RT_OK) return rc;
+  v->pending = false;
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, v->ev[0], v->ev[1]));
+  v->rays_ms = ms;
+  if (v->order_ms < 0.0) {
+    HIP_TRY(hipEventElapsedTime(&ms, v->ev[1], v->ev[2]));
+    v->order_ms = ms;
+  }
+  HIP_TRY(hipEventElapsedTime(&ms, v->ev[3], v->ev[4]));
+  v->resolve_ms = ms;
+  if (stats) {
+    if ((rc = rt_render_collect_stats(s, stats)) != RT_OK) return rc;
+    HIP_TRY(hipEventElapsedTime(&ms, v->ev[0], v->ev[4]));
+    stats->kernel_ms = ms;  // generator .. resolve (with secondary rays: every attempt of the batch, as rt_trace_rays)
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+
+int rt_view_read(rt_view* v, uint8_t* plane_of, rt_view_info* info) {
+  if (!v) return fail(RT_ERR_INVALID_ARG, "rt_view_read: null view");
+  HIP_TRY(hipSetDevice(v->device));
+  const int rc = view_wait(v);
+  if (rc != RT_OK) return rc;
+  if (plane_of) memcpy(plane_of, v->plane_of, v->n_samples);
+  if (info) {
+    *info = rt_view_info{};
+    info->n_pixels = v->n_pixels, info->n_samples = v->n_samples, info->n_distinct = v->n_distinct, info->n_rays = v->n_rays;
+    info->bytes = v->buf.cap + rt_ray_order_bytes(v->order);
+    info->order_built = v->order_built ? 1u : 0u;
+    info->rays_ms = v->rays_ms, info->order_ms = v->order_ms < 0.0 ? 0.0 : v->order_ms, info->resolve_ms = v->resolve_ms;
+  }
+  return RT_OK;
+}
+
+int rt_view_rays_model(const rt_view_desc* d, const rt_view_camera* c, float* origin, float* direction, uint8_t* plane_of, uint32_t* n_distinct) {
+  int rc = rt_view_check_desc(d, "rt_view_rays_model");
+  if (rc != RT_OK) return rc;
+  if ((rc = rt_view_check_camera(c, "rt_view_rays_model")) != RT_OK) return rc;
+  float distinct[2 * RT_VIEW_MAX_SAMPLES];
+  uint8_t po[RT_VIEW_MAX_SAMPLES];
+  const uint32_t nd = rt_view_dedup(d->samples, d->n_samples, distinct, po);
+  if (plane_of) memcpy(plane_of, po, d->n_samples);
+  if (n_distinct) *n_distinct = nd;
+  if (!origin && !direction) return RT_OK;
+  const RtViewCam cam = rt_view_cam_of(*d, *c);
+  for (uint32_t u = 0; u < nd; u++)
+    for (uint32_t p = 0; p < cam.n_pixels; p++) {
+      float o[3], dir[3];
+      rt_view_ray(cam, p % cam.width, p / cam.width, distinct[2 * u], distinct[2 * u + 1], o, dir);
+      const size_t k = 3u * ((size_t)u * cam.n_pixels + p);
+      if (origin) memcpy(origin + k, o, 12);
+      if (direction) memcpy(direction + k, dir, 12);
+    }
+  return RT_OK;
+}
+
+int rt_view_resolve_model(uint32_t n_pixels, uint32_t n_samples, const uint8_t* plane_of, const rt_ray_radiance* rays, const rt_ray_radiance* pixels) {
+  const char* fn = "rt_view_resolve_model";
+  if (!plane_of || !rays || !pixels) return fail(RT_ERR_INVALID_ARG, "%s: null argument", fn);
+  if (n_samples == 0 || n_samples > RT_VIEW_MAX_SAMPLES) return fail(RT_ERR_INVALID_ARG, "%s: n_samples %u outside 1 .. %u", fn, n_samples, RT_VIEW_MAX_SAMPLES);
+  if (!rays->rgb || !rays->valid || !rays->id || !rays->t) return fail(RT_ERR_INVALID_ARG, "%s: the per-ray rgb, valid, id and t planes are all required", fn);
+  if (plane_of[0] != 0) return fail(RT_ERR_INVALID_ARG, "%s: plane_of[0] must be 0", fn);
+  for (uint32_t k = 0; k < n_samples; k++)
+    if (plane_of[k] > k) return fail(RT_ERR_INVALID_ARG, "%s: plane_of[%u] = %u is not a first-occurrence index", fn, k, plane_of[k]);
+  const float scale = rt_view_scale(n_samples);
+  for (uint32_t p = 0; p < n_pixels; p++)
+    rt_view_resolve_pixel(p, n_pixels, n_samples, scale, plane_of, rays->rgb, rays->valid, rays->id, rays->t, pixels->rgb, pixels->valid, pixels->id,
+                          pixels->t, pixels->argb);
+  return RT_OK;
+}
+
+}  // extern "C"

@@ -152,6 +152,85 @@ class RayOrder:
             pass
 
 
+class DeviceView:
+    """Owns an `rt_view*`: a frame shape, a table of sample offsets and a camera on one device, with the device memory a
+    frame of it needs -- the rays of every (pixel, distinct sample), their radiance planes and a ray order.
+    `DeviceScene.render_view` makes the rays, traces them and resolves the samples into pixels, all on the device.
+
+    samples: (n, 2) float32 offsets (None: one ray through the pixel centre) -- pixels from the pixel centre for a pinhole
+    camera, the units of `sampling.aa_offsets` for the reference's (`camera.view_samples`).  order: "once" (the first frame
+    builds the ray order, later frames reuse it), "always" or "none"; the image is the same.  camera: an `rt_view_camera`
+    (`PinholeCamera.view_camera()`, `camera.reference_view_camera(cfg)`); `set_camera` moves it between frames."""
+
+    ORDERS = {"once": _abi.RT_VIEW_ORDER_ONCE, "always": _abi.RT_VIEW_ORDER_ALWAYS, "none": _abi.RT_VIEW_ORDER_NONE}
+
+    def __init__(self, device: int, width: int, height: int, samples=None, order: str = "once", camera=None):
+        if order not in self.ORDERS:
+            raise ValueError(f"order must be one of {sorted(self.ORDERS)}")
+        smp = np.zeros((1, 2), np.float32) if samples is None else np.ascontiguousarray(samples, np.float32)
+        if smp.ndim != 2 or smp.shape[1] != 2:
+            raise ValueError(f"samples must be (n, 2), got {smp.shape}")
+        lib = _lib.load()
+        desc = _abi.rt_view_desc(_abi.RT_ABI_VERSION, int(width), int(height), int(smp.shape[0]), smp.ctypes.data, self.ORDERS[order])
+        h = C.c_void_p()
+        _lib.check(lib.rt_view_create(C.byref(desc), int(device), C.byref(h)))
+        self._h = h
+        self.device, self.width, self.height, self.n_samples = int(device), int(width), int(height), int(smp.shape[0])
+        if camera is not None:
+            self.set_camera(camera)
+
+    @property
+    def handle(self) -> C.c_void_p:
+        if self._h is None:
+            raise RuntimeError("view destroyed")
+        return self._h
+
+    def set_camera(self, camera: "_abi.rt_view_camera") -> "DeviceView":
+        _lib.check(_lib.load().rt_view_set_camera(self.handle, C.byref(camera)))
+        return self
+
+    @property
+    def info(self) -> Dict:
+        """rt_view_info: pixels, samples, distinct samples, rays, device bytes, and the stage times of the last host-form frame."""
+        info = _abi.rt_view_info()
+        _lib.check(_lib.load().rt_view_read(self.handle, None, C.byref(info)))
+        return info.as_dict()
+
+    def plane_of(self) -> np.ndarray:
+        """plane_of[k] = the distinct sample (ray plane) sample k reads."""
+        out = np.empty(self.n_samples, np.uint8)
+        _lib.check(_lib.load().rt_view_read(self.handle, out.ctypes.data, None))
+        return out
+
+    def rays(self, torch_device=None):
+        """The generator alone -> (origins, directions), (n_rays, 3) float32; ray u * width * height + p belongs to pixel p
+        and distinct sample u.  numpy arrays (blocks), or with torch_device=True tensors on the view's device, enqueued on
+        torch.cuda.current_stream()."""
+        lib = _lib.load()
+        n = self.info["n_rays"]
+        if not torch_device:
+            o, d = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+            _lib.check(lib.rt_view_rays(self.handle, o.ctypes.data, d.ctypes.data))
+            return o, d
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        o, d = torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.rt_view_rays_device(self.handle, o.data_ptr(), d.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return o, d
+
+    def close(self):
+        if self._h is not None:
+            _lib.load().rt_view_destroy(self._h)  # (waits for the view's device work)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceScene:
     """Owns an `rt_scene*` (device copies + BVH)."""
 
@@ -296,6 +375,17 @@ class DeviceScene:
         ptr = (lambda a: a.data_ptr()) if torch_in else (lambda a: a.ctypes.data)
         return order.build(self._batch_struct(n, o, d, None, False, ptr), self._stream_of(o) if torch_in else None)
 
+    def _shading_params(self, cfg: RenderConfig, traversal: int, tuning: Optional[Dict]):
+        """The rt_params a radiance call shades with: `cfg` without its anti-aliasing (the caller's rays, or a view's samples,
+        are the samples).  The parameters of the last configuration are kept: building the light-cloud table is the expensive
+        part of a call."""
+        if cfg.has("anti_aliasing"):
+            cfg = RenderConfig(**{**cfg.__dict__, "features": cfg.features - {"anti_aliasing"}})
+        key = (cfg, int(traversal), tuple(sorted((tuning or {}).items())))
+        if self._trace_params is None or self._trace_params[0] != key:
+            self._trace_params = (key,) + _abi.make_params(cfg, traversal=traversal, tuning=tuning)
+        return self._trace_params[1]
+
     def trace_rays(self, origins, directions, cfg: RenderConfig, tuning: Optional[Dict] = None, traversal: int = _abi.RT_TRAVERSAL_BVH,
                    argb=None, order=None) -> "Radiance":
         """`single_raytrace` (raytracer_renderer.rs:147-264) for a batch of rays: the colour the render gives a pixel whose
@@ -313,13 +403,7 @@ class DeviceScene:
         torch_in, n, o, d, _ = self._batch(origins, directions, None)
         if order is not None and order is not True and not isinstance(order, RayOrder):
             raise ValueError("order must be None, True or a RayOrder")
-        if cfg.has("anti_aliasing"):
-            cfg = RenderConfig(**{**cfg.__dict__, "features": cfg.features - {"anti_aliasing"}})
-        # (the parameters of the last configuration are kept: building the light-cloud table is the expensive part of a call)
-        key = (cfg, int(traversal), tuple(sorted((tuning or {}).items())))
-        if self._trace_params is None or self._trace_params[0] != key:
-            self._trace_params = (key,) + _abi.make_params(cfg, traversal=traversal, tuning=tuning)
-        p = self._trace_params[1]
+        p = self._shading_params(cfg, traversal, tuning)
         out, ptr = self._planes(Radiance, o, n, ("rgb", "float32", 3), ("valid", "bool", 1), ("id", "int32", 1), ("t", "float32", 1))
         if torch_in:
             import torch
@@ -358,6 +442,39 @@ class DeviceScene:
                 _lib.check(lib.rt_trace_rays_ordered(self.handle, C.byref(p), C.byref(b), None if order is True else order.handle, C.byref(r),
                                                      C.byref(st)))
             self.last_trace_stats = st.as_dict()
+        return out
+
+    def render_view(self, view: DeviceView, cfg: RenderConfig, tuning: Optional[Dict] = None, traversal: int = _abi.RT_TRAVERSAL_BVH,
+                    argb=None, torch_out: bool = False) -> "Radiance":
+        """A frame of `view` (`rt_render_view*`): its rays are made on the device, traced as `trace_rays` traces them --
+        shaded with `cfg`, whose own camera and anti-aliasing are not used: the view's samples are the anti-aliasing -- and
+        resolved into pixels with the reference's accumulation.  Returns the per-pixel Radiance planes (rgb, valid, and the id
+        and t of sample 0), row-major with row 0 at the top.  argb: optional packed pixels as in trace_rays; pixels without a
+        valid sample keep their value.  numpy results (the host entry point; `last_trace_stats` is filled), or with
+        torch_out=True (or an argb tensor) tensors on this scene's device, enqueued on torch.cuda.current_stream().
+        With soft shadows every distinct sample of a pixel draws its own light-cloud set."""
+        p = self._shading_params(cfg, traversal, tuning)
+        n = view.width * view.height
+        lib = _lib.load()
+        if torch_out or (argb is not None and not isinstance(argb, np.ndarray)):
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            if argb is not None and not (isinstance(argb, torch.Tensor) and argb.dtype == torch.int32 and argb.device == dev and
+                                         tuple(argb.shape) == (n,) and argb.is_contiguous()):
+                raise ValueError(f"argb must be a contiguous int32 tensor of shape ({n},) on {dev}")
+            like = torch.empty(0, device=dev)
+            out, ptr = self._planes(Radiance, like, n, ("rgb", "float32", 3), ("valid", "bool", 1), ("id", "int32", 1), ("t", "float32", 1))
+            r = _abi.rt_ray_radiance(ptr(out.rgb), ptr(out.valid), ptr(out.id), ptr(out.t), ptr(argb) if argb is not None else None)
+            _lib.check(lib.rt_render_view_device(self.handle, view.handle, C.byref(p), C.byref(r), self._stream_of(like)))
+            return out
+        if argb is not None and not (argb.dtype == np.uint32 and argb.shape == (n,) and argb.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"argb must be a contiguous uint32 array of shape ({n},)")
+        out, ptr = self._planes(Radiance, np.empty(0), n, ("rgb", "float32", 3), ("valid", "bool", 1), ("id", "int32", 1), ("t", "float32", 1))
+        r = _abi.rt_ray_radiance(ptr(out.rgb), ptr(out.valid), ptr(out.id), ptr(out.t), ptr(argb) if argb is not None else None)
+        st = _abi.rt_stats()
+        _lib.check(lib.rt_render_view(self.handle, view.handle, C.byref(p), C.byref(r), C.byref(st)))
+        self.last_trace_stats = st.as_dict()
         return out
 
     # (bool arrays and tensors hold one byte per element, 0 or 1: the uint8 planes of rt_ray_occlusion / rt_ray_radiance)
@@ -515,16 +632,32 @@ class RaytracerRenderer:
         self.last_stats = st.as_dict()
         return planes
 
-    def render_camera(self, buffer: ImageBuffer, scene, camera, tuning: Optional[Dict] = None, order=False) -> Radiance:
+    def render_camera(self, buffer: ImageBuffer, scene, camera, tuning: Optional[Dict] = None, order=False, samples=None) -> Radiance:
         """Renders `scene` as `camera` sees it (anything with width, height and rays() -> (origins, directions), row-major
         with row 0 at the top: camera.PinholeCamera) into `buffer`: the rays go through DeviceScene.trace_rays with this
         renderer's configuration, hit pixels are written, misses keep the buffer's fill.  One ray per pixel -- the
         configuration's anti-aliasing belongs to the reference's own view and is not applied.  Returns the Radiance planes.
         order: False = the camera's row-major order; True = a ray order is built on the device for this call; a RayOrder
-        (of a camera that does not move relative to its rays' pattern) is reused.  The image is the same."""
+        (of a camera that does not move relative to its rays' pattern) is reused.  The image is the same.
+        samples: None = that path, one ray per pixel made on the host.  "config" (the configuration's anti-aliasing table,
+        `camera.view_samples`) or an (n, 2) array of offsets in pixels: the frame goes through a DeviceView (camera needs
+        view_camera()) -- rays made, traced in a device-built order (order=False: none) and resolved on the device."""
         if buffer.width != camera.width or buffer.height != camera.height:
             raise ValueError(f"buffer is {buffer.width}x{buffer.height}, the camera renders {camera.width}x{camera.height}")
         ds = self.device_scene(scene)
+        if samples is not None:
+            from . import camera as _camera
+
+            if isinstance(order, RayOrder):
+                raise ValueError("a view builds its own ray order: order must be True or False with samples")
+            smp = _camera.view_samples(self.cfg, _abi.RT_VIEW_PINHOLE) if isinstance(samples, str) and samples == "config" else samples
+            view = DeviceView(ds.device, camera.width, camera.height, smp, order="once" if order else "none", camera=camera.view_camera())
+            try:
+                out = ds.render_view(view, self.cfg, tuning=tuning, traversal=self.traversal, argb=buffer.buffer)
+            finally:
+                view.close()
+            self.last_stats = ds.last_trace_stats
+            return out
         o, d = camera.rays()
         out = ds.trace_rays(o, d, self.cfg, tuning=tuning, traversal=self.traversal, argb=buffer.buffer, order=order or None)
         self.last_stats = ds.last_trace_stats

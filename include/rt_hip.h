@@ -581,6 +581,110 @@ int rt_trace_rays_ordered(rt_scene* scene, const rt_params* shading, const rt_ra
 int rt_trace_rays_ordered_device(rt_scene* scene, const rt_params* shading, const rt_ray_batch* batch, const rt_ray_order* order,
                                  const rt_ray_radiance* out, void* hip_stream);
 
+/* ---- camera views: anti-aliased frames from any camera, rays made and samples resolved on the device -------------------------
+ *
+ * No reference counterpart beyond its one compile-time view (renderer/mod.rs:176-180, antialiased_raytrace,
+ * raytracer_renderer.rs:918-1016).  An rt_view is a frame shape, a table of sample offsets and, once set, a camera; it owns
+ * the device memory a frame of it needs.  rt_render_view_device enqueues, all on the caller's stream:
+ *   1. the ray generator: one ray per (pixel, DISTINCT sample),
+ *   2. rt_ray_order_build_device on those rays, when the order mode asks for it,
+ *   3. rt_trace_rays_ordered_device (RT_VIEW_ORDER_NONE: rt_trace_rays_device) into the view's per-ray planes,
+ *   4. the resolve: the reference's accumulation of a pixel's sample colours, into the caller's per-pixel planes.
+ * It allocates nothing itself.  Blocking, validation of `shading` and the one-render-call-per-scene rule are the trace's,
+ * unchanged: with REFLECTIONS / REFRACTIONS the call blocks in step 3 and allocates there what rt_trace_rays_device
+ * allocates; it is refused while rt_render_begin owns the scene.  RT_FLAG_ANTI_ALIASING in `shading` is refused: the view's
+ * samples are the anti-aliasing.
+ *
+ * Rays.  The caller gives n_samples (1..64) offsets; the bit-distinct ones, in first-occurrence order, are the n_distinct
+ * sample planes (the reference's deterministic table repeats 7 of 16), and plane_of[k] is the plane of sample k.  The ray
+ * of pixel p = y * width + x (row 0 is the top) and distinct sample u has batch index i = u * width * height + p, which is
+ * also its light-cloud key (rt_trace_rays' rule).  Repeated samples read the plane they repeat: exact by definition.
+ *   RT_VIEW_PINHOLE    offsets (sx, sy) in PIXELS from the pixel centre; origin = eye, direction = forward + a right + b up,
+ *                      a = (2 (x + 0.5 + sx) - W) / H * tan_half_fov_y, b = (H - 2 (y + 0.5 + sy)) / H * tan_half_fov_y
+ *                      (square pixels; right / up / forward: the caller's orthonormal basis; not normalised -- the trace does)
+ *   RT_VIEW_REFERENCE  offsets in the units of rt_params.aa_offsets (that table can be passed as is);
+ *                      coords = (float(x) fw, float(y) fh, 0), origin = coords + (sx, sy, 0), direction = coords - focus
+ * Every operation is one correctly rounded fp32 operation, evaluated as written, left to right.
+ *
+ * Resolve, over all n_samples with repeats read through plane_of: scale = 1 / (8 ceil(n / 8)); a valid sample k contributes
+ * cs = c scale -- k < 8: first[k] = cs, else rest[k & 7] = cs + rest[k & 7]; lane[l] = rest[l] + first[l]; the pixel is
+ * ((l0 + l4) + (l2 + l6)) + ((l1 + l5) + (l3 + l7)).  n_samples == 1: the sample's colour, unscaled.  The pixel planes are
+ * an rt_ray_radiance of width * height entries: rgb (0, 0, 0) if no sample is valid; valid = any sample valid; id / t those
+ * of sample 0 (-1 / +inf on its miss); argb packed as everywhere, UNTOUCHED when no sample is valid.
+ * Both formulas are specified by a host model compiled from the same source as the kernels (csrc/rt_view.h):
+ * rt_view_rays_model and rt_view_resolve_model.
+ *
+ * Order modes.  RT_VIEW_ORDER_ONCE (0, the default): the first render after rt_view_create builds the order, later ones
+ * reuse it -- an order depends only on the batch, and a camera that moves keeps its pixel-to-ray pattern.
+ * RT_VIEW_ORDER_ALWAYS rebuilds it every frame, RT_VIEW_ORDER_NONE traces without one.  Same image, bit for bit.
+ *
+ * Memory: rt_view_create allocates everything the device form needs -- per ray 24 bytes of origin and direction, 21 bytes
+ * of rgb / valid / id / t planes and the 20 bytes of an rt_ray_order of capacity n_rays (+ tables); rt_view_info.bytes.
+ * n_rays = n_distinct * width * height must not exceed 2^27, the orders' limit.
+ *
+ * rt_stats are the trace's (host form; device form: rt_render_collect_stats after synchronising): rays_primary counts the
+ * live DISTINCT rays, pixels_written the valid RAYS (not pixels), the others as rt_trace_rays counts them.
+ *
+ * Soft shadows, a deviation from rt_render: each distinct sample of a pixel draws its own light-cloud set, keyed by
+ * u * width * height + p, where rt_render gives every sample of a pixel the pixel's set.  Both are seeded stand-ins for the
+ * reference's unseeded per-pixel sets; a view frame with soft shadows is not comparable pixel for pixel with rt_render's.
+ *
+ * Refused with RT_ERR_INVALID_ARG (+ rt_last_error) before any HIP call: a NULL pointer or wrong abi_version; width or
+ * height 0; n_samples 0 or above 64; a non-finite sample offset; n_rays above 2^27; an unknown kind or order mode; a
+ * non-finite camera member; tan_half_fov_y <= 0 (pinhole); a render before any rt_view_set_camera; a view on another device
+ * than the scene; every output plane NULL; and whatever rt_trace_rays refuses in `shading`.
+ * One render per view at a time, and a view's frames go on one stream or are ordered by the caller (a reused order is
+ * read by the next frame's trace); rt_view_destroy and rt_view_read wait for the view's last work. */
+#define RT_VIEW_PINHOLE 0u
+#define RT_VIEW_REFERENCE 1u
+#define RT_VIEW_ORDER_ONCE 0u
+#define RT_VIEW_ORDER_ALWAYS 1u
+#define RT_VIEW_ORDER_NONE 2u
+typedef struct rt_view rt_view;
+typedef struct rt_view_desc {
+  uint32_t abi_version; /* RT_ABI_VERSION */
+  uint32_t width, height;
+  uint32_t n_samples;   /* 1 .. 64 */
+  const float* samples; /* [n_samples][2] */
+  uint32_t order;       /* RT_VIEW_ORDER_* */
+} rt_view_desc;
+typedef struct rt_view_camera {
+  uint32_t abi_version; /* RT_ABI_VERSION */
+  uint32_t kind;        /* RT_VIEW_PINHOLE: eye .. tan_half_fov_y are read; RT_VIEW_REFERENCE: focus, fw, fh */
+  float eye[3], right[3], up[3], forward[3];
+  float tan_half_fov_y;
+  float focus[3], fw, fh;
+} rt_view_camera;
+typedef struct rt_view_info {
+  uint32_t n_pixels, n_samples, n_distinct, n_rays;
+  uint64_t bytes;       /* device memory the view holds, its ray order included */
+  uint32_t order_built; /* 1: the view holds a built order */
+  uint32_t reserved;
+  double rays_ms, order_ms, resolve_ms; /* rt_render_view: device time of the generator, the order build (0 when reused) and the resolve */
+} rt_view_info;
+
+int rt_view_create(const rt_view_desc* desc, int device, rt_view** out);
+void rt_view_destroy(rt_view* view);
+/* validates and stores the camera of the next frames; no allocation, no HIP call */
+int rt_view_set_camera(rt_view* view, const rt_view_camera* camera);
+/* the generator alone, for callers with a pipeline of their own: n_rays rays into DEVICE arrays [n_rays][3] on the view's device */
+int rt_view_rays_device(rt_view* view, float* origin_dev, float* direction_dev, void* hip_stream);
+/* HOST arrays; blocks */
+int rt_view_rays(rt_view* view, float* origin_host, float* direction_host);
+/* pixels_dev: DEVICE planes of width * height entries on the scene's device; enqueued on `hip_stream` */
+int rt_render_view_device(rt_scene* scene, rt_view* view, const rt_params* shading, const rt_ray_radiance* pixels_dev, void* hip_stream);
+/* HOST planes (argb is uploaded first: pixels without a valid sample keep the caller's value); blocks.  stats may be NULL. */
+int rt_render_view(rt_scene* scene, rt_view* view, const rt_params* shading, const rt_ray_radiance* pixels_host, rt_stats* stats);
+/* waits for the view's device work; plane_of_host [n_samples] bytes and info are nullable */
+int rt_view_read(rt_view* view, uint8_t* plane_of_host, rt_view_info* info);
+/* The host models (no device needed).  origin / direction: [n_distinct * width * height][3], sized by the caller for
+ * n_samples planes at most; plane_of [n_samples]; every output nullable. */
+int rt_view_rays_model(const rt_view_desc* desc, const rt_view_camera* camera, float* origin, float* direction, uint8_t* plane_of,
+                       uint32_t* n_distinct);
+/* rays: the per-ray planes of a trace of the model's rays (all four required); pixels: [n_pixels] planes, every member nullable */
+int rt_view_resolve_model(uint32_t n_pixels, uint32_t n_samples, const uint8_t* plane_of, const rt_ray_radiance* rays,
+                          const rt_ray_radiance* pixels);
+
 /* thread-local message for the last non-RT_OK return on this thread */
 const char* rt_last_error(void);
 

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Renders semesterbild on GPU 0 from a viewpoint of the caller's choosing (the reference has one, fixed at compile
-time) and writes a PNG: camera.PinholeCamera -> RaytracerRenderer.render_camera -> rt_trace_rays.
+time) and writes a PNG: camera.PinholeCamera -> RaytracerRenderer.render_camera -> rt_trace_rays, or with --aa through a
+device-side view (rt_render_view: rays made, traced and resolved on the device, the configuration's anti-aliasing table).
 
-    render_view.py OUT.png [--eye X,Y,Z] [--target X,Y,Z] [--fov DEG] [--size WxH] [--features f,g] [--model text|text_lowres] [--order]
+    render_view.py OUT.png [--eye X,Y,Z] [--target X,Y,Z] [--fov DEG] [--size WxH] [--features f,g] [--model text|text_lowres] [--order] [--aa]
 
 eye / target are in units of the scene's width, height and depth (the reference's own focus is 0.5,0.5,-1.9; image y points
 down, so the camera's up vector is (0, -1, 0))."""
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--model", default="text")
     ap.add_argument("--fill", default="0xFF101010")
     ap.add_argument("--order", action="store_true", help="pack the camera's rays into coherent wavefronts (a ray order built on the device)")
+    ap.add_argument("--aa", action="store_true", help="anti-aliased: the configuration's sample table through a device-side view")
     args = ap.parse_args()
     cfg = RenderConfig.from_features([f for f in args.features.split(",") if f])
     scale = (float(cfg.scene_width), float(cfg.scene_height), float(cfg.scene_depth))
@@ -40,8 +42,8 @@ def main():
     buf = ImageBuffer.new_with_color(w, h, int(args.fill, 0))
     r = RaytracerRenderer(cfg)
     t = time.time()
-    out = r.render_camera(buf, scene, cam, order=args.order)
-    print(f"semesterbild {w}x{h} from eye={eye} features={sorted(cfg.features)} order={args.order} valid={float(out.valid.mean()):.3f} "
+    out = r.render_camera(buf, scene, cam, order=args.order, samples="config" if args.aa else None)
+    print(f"semesterbild {w}x{h} from eye={eye} features={sorted(cfg.features)} order={args.order} aa={args.aa} valid={float(out.valid.mean()):.3f} "
           f"wall={time.time() - t:.3f}s stats={r.last_stats}")
     Image.fromarray(buf.as_rgb8()).save(args.out)
 

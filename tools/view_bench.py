@@ -1,0 +1,134 @@
+"""What a device-side camera view (rt_view*, rt_render_view_device) costs, on the config-3 scene (semesterbild with
+text.obj) and config 3's frame shape, 1620 x 1350, one GPU, every figure from the same process:
+
+  per shading (direct light; soft shadows = config 3) and camera (the reference's; a pinhole elsewhere in the scene):
+      view_1 / view_16      rt_render_view_device end to end, 1 sample and the configuration's 16 (9 distinct), for the order
+                            modes none / once (the order is reused: a steady frame) / always (rebuilt every frame)
+      stages                device time of generator, order build, trace and resolve of one frame (the view's own events,
+                            host form, median of 5 frames), mode always
+      frame_aa / frame_1    rt_render_device of the same configuration's frame with and without anti-aliasing, beside them
+                            (the reference's camera; merged levels, one set of light clouds per pixel)
+      host_rays_1           today's host path for one sample: numpy rays + upload + trace_rays, wall time to a synchronise
+
+Every shape is warmed up, then timed with device events over repeated calls until at least --seconds of work.  The three
+order modes are compared (equal bits) before anything is timed.  Prints one JSON line; two runs give the spread.
+
+    python tools/view_bench.py [--device 0] [--seconds 1.0] [--only direct,soft] [--size 1620x1350]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import torch  # (before the library: one HIP runtime in the process)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+from hslu_i.ba_raytracing.f2501_raytracer_amd import RenderConfig, _abi, _lib, camera, scenes  # noqa: E402
+from hslu_i.ba_raytracing.f2501_raytracer_amd.renderer import DeviceScene, DeviceView  # noqa: E402
+
+
+def time_it(fn, seconds):
+    fn()
+    fn()  # warm-up
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    one = e0.elapsed_time(e1) / 1e3
+    reps = max(3, int(np.ceil(seconds / max(one, 1e-6))))
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return round(e0.elapsed_time(e1) / reps, 4)  # ms
+
+
+def same(a, b):
+    return all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--only", default="direct,soft")
+    ap.add_argument("--size", default="1620x1350")
+    args = ap.parse_args()
+    only = set(args.only.split(","))
+    w, h = (int(v) for v in args.size.split("x"))
+    dev = torch.device("cuda", args.device)
+    torch.cuda.set_device(dev)
+    size = dict(width_override=w, height_override=h)
+    base = RenderConfig.from_features(["anti_aliasing"], **size)
+    flat = scenes.semesterbild(base, "text").flatten()
+    ds = DeviceScene(flat, args.device)
+    lib = _lib.load()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    scale = (float(base.scene_width), float(base.scene_height), float(base.scene_depth))
+    pin = camera.PinholeCamera([v * s for v, s in zip((-0.45, 0.25, -1.1), scale)], [v * s for v, s in zip((0.5, 0.5, 0.6), scale)],
+                               (0.0, -1.0, 0.0), 38.0, w, h)
+    cams = {"reference": (_abi.RT_VIEW_REFERENCE, camera.reference_view_camera(base)), "pinhole": (_abi.RT_VIEW_PINHOLE, pin.view_camera())}
+
+    res = {}
+    for name, features in (("direct", []), ("soft", ["soft_shadows"])):
+        if name not in only:
+            continue
+        cfg = RenderConfig.from_features(features, **size)
+        r = {}
+        for cam_name, (kind, cam) in cams.items():
+            c = {}
+            for label, smp in (("view_1", None), ("view_16", camera.view_samples(base, kind))):
+                views = {mode: DeviceView(args.device, w, h, smp, order=mode, camera=cam) for mode in ("none", "once", "always")}
+                frames = {mode: ds.render_view(v, cfg, torch_out=True) for mode, v in views.items()}
+                info = views["always"].info
+                e = dict(rays=info["n_rays"], distinct=info["n_distinct"], view_bytes=info["bytes"],
+                         modes_equal=bool(same(frames["none"], frames["once"]) and same(frames["none"], frames["always"])))
+                del frames
+                for mode, v in views.items():
+                    e[f"{mode}_ms"] = time_it(lambda: ds.render_view(v, cfg, torch_out=True), args.seconds)
+                stages = []
+                for _ in range(6):  # (host form: the view records its stage events; the first frame warms the staging up)
+                    ds.render_view(views["always"], cfg)
+                    i, st = views["always"].info, ds.last_trace_stats
+                    stages.append((i["rays_ms"], i["order_ms"], st["kernel_ms"] - i["rays_ms"] - i["order_ms"] - i["resolve_ms"], i["resolve_ms"]))
+                med = np.median(np.array(stages[1:]), axis=0)
+                e["stages_ms"] = dict(zip(("generator", "order", "trace", "resolve"), (round(float(x), 4) for x in med)))
+                for v in views.values():
+                    v.close()
+                c[label] = e
+            r[cam_name] = c
+        frame = torch.zeros(w * h, dtype=torch.int32, device=dev)
+        for label, feats in (("frame_aa_ms", features + ["anti_aliasing"]), ("frame_1_ms", features)):
+            p, keep = _abi.make_params(RenderConfig.from_features(feats, **size))
+            r[label] = time_it(lambda: _lib.check(lib.rt_render_device(ds.handle, C.byref(p), frame.data_ptr(), None, stream)), args.seconds)
+
+        def host_path():
+            o, d = pin.rays()
+            ds.trace_rays(torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev), cfg)
+            torch.cuda.synchronize()
+
+        host_path()
+        t = time.perf_counter()
+        for _ in range(3):
+            host_path()
+        r["host_rays_1_wall_ms"] = round((time.perf_counter() - t) / 3 * 1e3, 3)
+        res[name] = r
+    torch.cuda.synchronize()
+    print(json.dumps(dict(metric=f"camera views: ms per {w}x{h} frame (config-3 scene, text.obj)", gpu=torch.cuda.get_device_name(dev),
+                          build_id=lib.rt_build_id().decode(), workloads=res)))
+    ds.close()
+
+
+if __name__ == "__main__":
+    main()
