@@ -196,6 +196,60 @@ class rt_update_info(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class rt_transform(C.Structure):
+    _fields_ = [("translation", C.c_float * 3), ("rotor", C.c_float * 4), ("scale", C.c_float)]
+
+
+class rt_pose_part(C.Structure):
+    _fields_ = [("tri_first", C.c_uint32), ("tri_count", C.c_uint32), ("sphere_first", C.c_uint32), ("sphere_count", C.c_uint32)]
+
+
+class rt_pose_desc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("n_parts", C.c_uint32), ("parts", C.c_void_p), ("n_triangles", C.c_uint32),
+                ("n_spheres", C.c_uint32), ("tri_v1", C.c_void_p), ("tri_v2", C.c_void_p), ("tri_v3", C.c_void_p),
+                ("tri_normal", C.c_void_p), ("sphere_center", C.c_void_p), ("sphere_radius", C.c_void_p)]
+
+
+class rt_bvh_quality(C.Structure):
+    _fields_ = [("sah_created", C.c_double), ("sah_now", C.c_double), ("inner_q", C.c_uint64), ("leaf_q", C.c_uint64),
+                ("n_bad", C.c_uint32), ("reserved", C.c_uint32), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def transform_row(t):
+    """Similarity3 -> the 8 floats of an rt_transform: translation, rotor s / xy / xz / yz, scale"""
+    r = t.rotation
+    return [np.float32(v) for v in (t.translation.x, t.translation.y, t.translation.z, r.s, r.xy, r.xz, r.yz, t.scale)]
+
+
+def transform_rows(transforms):
+    """a list of Similarity3, or anything numpy turns into (n, 8) floats -> contiguous (n, 8) float32"""
+    if isinstance(transforms, (list, tuple)) and transforms and hasattr(transforms[0], "rotation"):
+        transforms = [transform_row(t) for t in transforms]
+    a = np.ascontiguousarray(transforms, np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError(f"transforms must be (n_parts, 8), got {a.shape}")
+    return a
+
+
+def make_pose_desc(parts, n_triangles, n_spheres, v1=None, v2=None, v3=None, normal=None, centre=None, radius=None):
+    """rt_pose_desc of `parts` [(tri_first, tri_count, sphere_first, sphere_count)] over rest arrays (float32 numpy, or None).
+    Returns (desc, keepalive)."""
+    pa = np.ascontiguousarray(parts, np.uint32).reshape(-1, 4)
+    keep = [pa]
+    d = rt_pose_desc()
+    d.abi_version, d.n_parts, d.parts = RT_ABI_VERSION, int(pa.shape[0]), pa.ctypes.data
+    d.n_triangles, d.n_spheres = int(n_triangles), int(n_spheres)
+    for field, a in (("tri_v1", v1), ("tri_v2", v2), ("tri_v3", v3), ("tri_normal", normal), ("sphere_center", centre), ("sphere_radius", radius)):
+        if a is not None:
+            a = np.ascontiguousarray(a, np.float32)
+            keep.append(a)
+            setattr(d, field, a.ctypes.data)
+    return d, keep
+
+
 def fptr(a: np.ndarray):
     assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(_fp)

@@ -119,6 +119,11 @@ int rt_scene_create(const rt_scene_desc* d, int device, rt_scene** out) {
   if (rc == RT_OK) rc = s->counters.ensure(RT_SLOTS * RT_COUNTER_REPLICAS * 16 * sizeof(unsigned long long));
   if (rc == RT_OK) rc = upload(s->blob, pk.blob.data(), pk.blob.size());
   if (rc == RT_OK) rc = rt_scene_upload_plan(s, pk);  // (in-place updates: rt_update.cpp)
+  if (rc == RT_OK) rc = s->sah_dev.ensure(256);
+  if (rc == RT_OK) {  // (SAH report: the sums of creation)
+    rt_sah_packed(pk, s->sah_created, nullptr);
+    s->sah_tri_cost = d->bvh.tri_cost > 0.f ? d->bvh.tri_cost : 2.0f;  // (as rt_build_bvh applies it)
+  }
   if (rc != RT_OK) {
     rt_scene_destroy(s);
     return rc;

@@ -250,6 +250,11 @@ struct rt_scene {
   void* upd_stage = nullptr;
   size_t upd_stage_cap = 0;
   float* upd_back = nullptr;
+  // SAH report (rt_scene_bvh_quality): the integer sums of rt_sah.h over the tree as created, the triangle cost the tree
+  // was built with, and the three 64-bit words the kernel adds into
+  uint64_t sah_created[2] = {0, 0};
+  float sah_tri_cost = 2.0f;
+  DevBuf sah_dev;
 };
 
 

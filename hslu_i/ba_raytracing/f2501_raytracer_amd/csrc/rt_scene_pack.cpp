@@ -11,6 +11,7 @@
 #include <string>
 
 #include "rt_refit.h"
+#include "rt_sah.h"
 #include "rt_scene_pack.h"
 
 static thread_local std::string g_err;
@@ -418,6 +419,17 @@ int rt_refit_packed(RtPackedScene* pk, const rt_scene_delta* d) {
   if (d->lights)
     for (uint32_t i = 0; i < sc.n_lights; i++) rt_upd_light(sc, base, i, d->lights);
   return RT_OK;
+}
+
+void rt_sah_packed(const RtPackedScene& pk, uint64_t sums[2], uint32_t* n_bad) {
+  sums[0] = sums[1] = 0u;
+  uint32_t bad = 0u;
+  const RtNode* nodes = (const RtNode*)(pk.blob.data() + pk.dev.off_nodes);
+  if (pk.dev.n_triangles && pk.dev.n_nodes) {
+    const double a_root = rt_sah_root_area(nodes[0]);
+    for (uint32_t i = 0; i < pk.dev.n_nodes; i++) rt_sah_node(nodes[i], a_root, sums, &bad);
+  }
+  if (n_bad) *n_bad = bad;
 }
 
 int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {

@@ -53,6 +53,11 @@ int rt_check_scene_delta(const RtDevScene& dev, const RtRefitPlan& plan, const r
 // functions): the specification of rt_scene_update, checked on the CPU.  Same return codes as rt_check_scene_delta.
 int rt_refit_packed(RtPackedScene* pk, const rt_scene_delta* d);
 
+// ---- SAH report ------------------------------------------------------------------------------------------------------------
+// The two integer sums of rt_sah.h over the tree of a packed scene as it stands: sums[0] = inner_q, sums[1] = leaf_q, and
+// the number of refused ratios.  The specification of rt_scene_bvh_quality, checked on the CPU; all zero without triangles.
+void rt_sah_packed(const RtPackedScene& pk, uint64_t sums[2], uint32_t* n_bad);
+
 // ---- parameter tables of a frame -----------------------------------------------------------------------------------------
 // AA samples: the distinct offsets in first-occurrence order (compared as values; `dedup` off: every sample is distinct),
 // their multiplicities and the sample -> thread map, as the device image [2U offsets (float bits) | U | n].  Returns U.

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "rt_host.h"
+#include "rt_sah.h"
 
 // the device copy of RtRefitPlan: [height_nodes | thr_src | recv_cell | tri_slot | 8 words: bounds, counter], 256-byte aligned parts
 int rt_scene_upload_plan(rt_scene* s, const RtPackedScene& pk) {
@@ -27,6 +28,7 @@ int rt_scene_upload_plan(rt_scene* s, const RtPackedScene& pk) {
 void rt_scene_release_update(rt_scene* s) {
   s->plan_dev.release();
   s->upd_dev.release();
+  s->sah_dev.release();
   if (s->upd_stage) (void)hipHostFree(s->upd_stage);
   if (s->upd_back) (void)hipHostFree(s->upd_back);
   s->upd_stage = nullptr, s->upd_back = nullptr, s->upd_stage_cap = 0;
@@ -167,6 +169,40 @@ int rt_scene_update_device(rt_scene* s, const rt_scene_delta* d, void* hip_strea
   if (rc == RT_OK) rc = rt_check_scene_delta(s->dev, s->plan, d, nullptr);  // (material classes: update_impl, after a read-back)
   if (rc != RT_OK) return rc;
   return update_impl(s, nullptr, *d, (hipStream_t)hip_stream, info);
+}
+
+// The SAH report of the tree as it stands.  A stream of its own: the call neither waits for nor delays the caller's frames.
+int rt_scene_bvh_quality(rt_scene* s, rt_bvh_quality* out) {
+  if (!s || !out) return fail(RT_ERR_INVALID_ARG, "rt_scene_bvh_quality: null argument");
+  *out = rt_bvh_quality{};
+  if (!s->dev.n_triangles) return RT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  struct Stream {  // destroyed on every return path
+    hipStream_t st = nullptr;
+    ~Stream() {
+      if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
+    }
+  } q;
+  HIP_TRY(hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking));
+  EventPair ev;
+  HIP_TRY(hipEventCreate(&ev.e0));
+  HIP_TRY(hipEventCreate(&ev.e1));
+  HIP_TRY(hipEventRecord(ev.e0, q.st));
+  unsigned long long* dev = (unsigned long long*)s->sah_dev.p;
+  const hipError_t e = (hipError_t)rt_launch_sah((const RtNode*)((const char*)s->blob.p + s->dev.off_nodes), s->dev.n_nodes, dev, q.st);
+  if (e != hipSuccess) return fail(RT_ERR_HIP, "SAH report launch failed: %s", hipGetErrorString(e));
+  HIP_TRY(hipEventRecord(ev.e1, q.st));
+  unsigned long long host[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, q.st));
+  HIP_TRY(hipStreamSynchronize(q.st));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  const double cost = (double)s->sah_tri_cost;
+  out->inner_q = host[0], out->leaf_q = host[1], out->n_bad = (uint32_t)host[2];
+  out->sah_created = ((double)s->sah_created[0] + cost * (double)s->sah_created[1]) / RT_SAH_ONE;
+  out->sah_now = ((double)host[0] + cost * (double)host[1]) / RT_SAH_ONE;
+  out->device_ms = ms;
+  return RT_OK;
 }
 
 }  // extern "C"

@@ -263,6 +263,13 @@ class DeviceScene:
         _lib.check(_lib.load().rt_scene_memory_info(self.handle, C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in info._fields_}
 
+    def bvh_quality(self) -> Dict:
+        """`rt_scene_bvh_quality`: the SAH cost of the tree as it stands (`sah_now`) next to the one it had at creation
+        (`sah_created`), the integer sums behind it and the device time of the report.  Blocks; runs on a stream of its own."""
+        q = _abi.rt_bvh_quality()
+        _lib.check(_lib.load().rt_scene_bvh_quality(self.handle, C.byref(q)))
+        return q.as_dict()
+
     def update(self, flat, info: bool = False, tri_first: int = 0):
         """New values for the objects this scene already has, in place (`rt_scene_update`): the BVH is refitted on the
         device, not rebuilt, and afterwards every render and query behaves as on a DeviceScene created from the new
@@ -548,6 +555,103 @@ class DeviceScene:
         if self._call_order is not None:
             self._call_order.close()
             self._call_order = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DevicePose:
+    """Owns an `rt_pose*`: the rest pose of rigid parts of a DeviceScene on its device.  `apply` places every part with a
+    similarity transform (32 bytes per part) in one kernel and refits the scene in place, as `DeviceScene.update` would
+    with arrays posed on the host.
+
+    parts: [(tri_first, tri_count, sphere_first, sphere_count)], ranges pairwise disjoint.  The rest pose is taken from
+    `scene.flat`.  rest_v2 / rest_v3: the rest VERTICES, (n_triangles, 3) float32; default `v1 + e1` / `v1 + e2` in fp32.
+    rest_radius: (n_spheres,) float32; default `sqrt(r_sq)` in fp32.  The defaults are rounded reconstructions: pass the exact
+    vertices and radii where you have them (a loader's), only then does the identity transform restate the scene bit for
+    bit and a posed mesh equal the mesh loaded with that transform."""
+
+    def __init__(self, scene: "DeviceScene", parts, rest_v2=None, rest_v3=None, rest_radius=None):
+        f = scene.flat
+        v2 = (f.tri_v1 + f.tri_e1).astype(np.float32) if rest_v2 is None else np.ascontiguousarray(rest_v2, np.float32)
+        v3 = (f.tri_v1 + f.tri_e2).astype(np.float32) if rest_v3 is None else np.ascontiguousarray(rest_v3, np.float32)
+        rad = np.sqrt(f.sphere_r_sq).astype(np.float32) if rest_radius is None else np.ascontiguousarray(rest_radius, np.float32)
+        if v2.shape != f.tri_v1.shape or v3.shape != f.tri_v1.shape or rad.shape != f.sphere_r_sq.shape:
+            raise ValueError("rest_v2 / rest_v3 must be (n_triangles, 3) and rest_radius (n_spheres,)")
+        desc, keep = _abi.make_pose_desc(parts, f.n_triangles, f.n_spheres, f.tri_v1, v2, v3, f.tri_normal, f.sphere_center, rad)
+        h = C.c_void_p()
+        _lib.check(_lib.load().rt_pose_create(C.byref(desc), scene.device, C.byref(h)))
+        self._h = h
+        self.scene, self.n_parts = scene, int(desc.n_parts)
+        self._parts = keep[0]
+
+    @property
+    def handle(self) -> C.c_void_p:
+        if self._h is None:
+            raise RuntimeError("pose destroyed")
+        return self._h
+
+    def geometry(self) -> Dict:
+        """`rt_pose_read`: the posed arrays as the last apply left them -- tri_first, tri_count and tri_v1 / tri_e1 / tri_e2 /
+        tri_normal over the pose's covering triangle range; sphere_center / sphere_r_sq / sphere_r_inv over all spheres
+        (None when no part has spheres)."""
+        lib = _lib.load()
+        first, count = C.c_uint32(), C.c_uint32()
+        _lib.check(lib.rt_pose_read(self.handle, None, None, None, None, C.byref(first), C.byref(count), None, None, None))
+        n = int(count.value)
+        ns = self.scene.flat.n_spheres if self._has_spheres() else 0
+        out = {k: np.empty((n, 3), np.float32) for k in _abi.TRIANGLE_GROUP}
+        out.update(sphere_center=np.empty((ns, 3), np.float32), sphere_r_sq=np.empty(ns, np.float32), sphere_r_inv=np.empty(ns, np.float32))
+        _lib.check(lib.rt_pose_read(self.handle, *[out[k].ctypes.data for k in _abi.TRIANGLE_GROUP], None, None,
+                                    *[out[k].ctypes.data for k in _abi.SPHERE_GROUP]))
+        if not ns:
+            out.update({k: None for k in _abi.SPHERE_GROUP})
+        out.update(tri_first=int(first.value), tri_count=n)
+        return out
+
+    def _has_spheres(self) -> bool:
+        return bool(self._parts[:, 3].any())
+
+    def apply(self, transforms, info: bool = False):
+        """Places every part and refits the scene (`rt_pose_apply`; blocks).  transforms: a list of n_parts `Similarity3`,
+        an (n_parts, 8) float32 numpy array of rt_transform rows (`_abi.transform_row`), or a float32 torch tensor of that
+        shape on the scene's device (`rt_pose_apply_device` on torch.cuda.current_stream(): no transform crosses the bus).
+        `scene.flat` follows.  Returns None, or with info=True the rt_update_info of the call as a dict."""
+        lib = _lib.load()
+        inf = _abi.rt_update_info()
+        if isinstance(transforms, (list, tuple, np.ndarray)):
+            rows = _abi.transform_rows(transforms)
+            if rows.shape[0] != self.n_parts:
+                raise ValueError(f"{rows.shape[0]} transforms for {self.n_parts} parts")
+            _lib.check(lib.rt_pose_apply(self.scene.handle, self.handle, rows.ctypes.data, C.byref(inf)))
+        else:
+            import torch
+
+            want = torch.device("cuda", self.scene.device)
+            t = transforms
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != want or tuple(t.shape) != (self.n_parts, 8):
+                raise ValueError(f"transforms must be a float32 tensor of shape ({self.n_parts}, 8) on {want} (the scene's device)")
+            t = t.contiguous()
+            _lib.check(lib.rt_pose_apply_device(self.scene.handle, self.handle, C.c_void_p(t.data_ptr()), DeviceScene._stream_of(t), C.byref(inf)))
+        # the description the scene holds follows (the call has synchronised its stream)
+        g = self.geometry()
+        old = self.scene.flat
+        new = {k: np.array(getattr(old, k), copy=True) for k in FlatScene.__dataclass_fields__}
+        for k in _abi.TRIANGLE_GROUP:
+            new[k][g["tri_first"]:g["tri_first"] + g["tri_count"]] = g[k]
+        if g["sphere_center"] is not None:
+            for k in _abi.SPHERE_GROUP:
+                new[k] = g[k]
+        self.scene.flat = FlatScene(**new).contiguous()
+        return inf.as_dict() if info else None
+
+    def close(self):
+        if self._h is not None:
+            _lib.load().rt_pose_destroy(self._h)  # (waits for the pose's device work)
+            self._h = None
 
     def __del__(self):
         try:

@@ -782,6 +782,114 @@ int rt_scene_update(rt_scene* scene, const rt_scene_delta* delta, rt_update_info
 /* device arrays on the scene's device; the kernels run on `hip_stream` */
 int rt_scene_update_device(rt_scene* scene, const rt_scene_delta* delta, void* hip_stream, rt_update_info* info);
 
+/* ---- part poses: rigid parts of a scene placed by similarity transforms on the device, then refitted ------------------------
+ *
+ * Reference: Scene::from_obj(path, Some(Similarity3)) (src/scene/scene.rs:43-134) places a mesh with
+ * Similarity3::transform_vec on its vertices and rotated_by(rotation) on its normals, once, at load time.  An rt_pose does
+ * that per frame: it holds the REST pose of the parts of a scene on the device, one kernel (csrc/rt_pose.hip) writes the
+ * posed arrays of an rt_scene_delta from 32 bytes of transform per part, and rt_scene_update_device takes them.
+ *
+ * A transform is 8 floats: translation, a rotor {s, xy, xz, yz} in the layout of ultraviolet's Rotor3 (NOT normalised by the
+ * library), and a scale.  Every operation is one correctly rounded fp32 operation, evaluated as written, left to right,
+ * never fused; a - b is a + (-b):
+ *   rotate(v):  fx = (s vx + xy vy) + xz vz      fy = (s vy - xy vx) + yz vz
+ *               fz = (s vz - xz vx) - yz vy      fw = (xy vz - xz vy) + yz vx
+ *               x' = ((s fx + xy fy) + xz fz) + yz fw
+ *               y' = ((s fy - xy fx) - xz fw) + yz fz
+ *               z' = ((s fz + xy fw) - xz fx) - yz fy
+ *   T(v)     =  rotate(v) scale + translation        (per component: one multiply, one add)
+ *   triangle:   v1' = T(v1), v2' = T(v2), v3' = T(v3);  e1' = v2' - v1';  e2' = v3' - v1';  n' = rotate(n)
+ *   sphere:     c' = T(c);  r' = r scale;  r_sq' = r' r';  r_inv' = 1 / r'
+ * The formulas are specified by a host model compiled from the same source as the kernel (csrc/rt_pose.h): rt_pose_model.
+ * The rest pose holds the VERTICES v2 and v3, not the edges, and the radius, not its square: only then is a posed mesh the
+ * mesh from_obj would have loaded, v1 / e1 / e2 bit for bit.  Deviation: the reference rotates per-vertex normals and lerps
+ * afterwards, a pose rotates the stored normal; the two differ by a few 2^-24 per component (csrc/rt_pose.h).
+ *
+ * Parts.  A part is a range of canonical triangles and / or a range of spheres that share one transform.  The pose's
+ * COVERING triangle range [tri_first, tri_first + tri_count) is the smallest range that holds every part's triangles; it is
+ * the triangle group of every apply, and the posed triangle arrays (rt_pose_read, rt_pose_model) cover it, element 0 being
+ * triangle tri_first.  A triangle of the covering range that belongs to no part is restated by every apply with its rest
+ * values v1, v2 - v1, v3 - v1, normal.  When some part has spheres, every apply carries the sphere group (an update replaces
+ * all spheres): spheres of no part are restated as centre, r r, 1 / r, and the posed sphere arrays cover all n_spheres;
+ * otherwise the pose has no sphere arrays and the sphere outputs are not written.  The rest arrays are read inside the
+ * covering range (triangles) and in full (spheres, when a part has some), at rt_pose_create only.
+ *
+ * rt_pose_create allocates everything: the rest pose, the part tables, the posed arrays (initialised with the rest values)
+ * and room for n_parts staged transforms.  The device forms allocate nothing.
+ * rt_pose_apply_device enqueues the kernel on `hip_stream` and calls rt_scene_update_device with the pose's own device
+ * arrays: everything about blocking, invalidation, refusals (RT_ERR_UNSUPPORTED on split-clipped trees included) and
+ * rt_update_info is that call's, unchanged.  rt_pose_apply stages the transforms through the pose's buffer on the null
+ * stream and does the same.  rt_pose_geometry_device is the kernel alone, for callers with a pipeline of their own.
+ * One apply per pose at a time; a pose's work goes on one stream or is ordered by the caller.
+ *
+ * Refused with RT_ERR_INVALID_ARG (+ rt_last_error) before any HIP call: a NULL pointer or wrong abi_version; n_parts == 0
+ * or a part with both counts 0; a range beyond n_triangles / n_spheres; overlapping ranges; NULL rest arrays for a kind some
+ * part uses; on apply a pose whose counts differ from the scene's, a pose on another device than the scene, and what
+ * rt_scene_update_device refuses in the delta; in the HOST form only, a non-finite transform member.  The device form
+ * cannot look at the transforms: what non-finite geometry does is what rt_scene_update_device does with it.
+ * Out of scope: lights are not posed (a caller moves them through rt_scene_update); hierarchies of parts; skinning. */
+typedef struct rt_transform {
+  float translation[3];
+  float rotor[4]; /* s, xy, xz, yz */
+  float scale;
+} rt_transform;
+typedef struct rt_pose_part {
+  uint32_t tri_first, tri_count, sphere_first, sphere_count;
+} rt_pose_part;
+typedef struct rt_pose_desc {
+  uint32_t abi_version; /* RT_ABI_VERSION */
+  uint32_t n_parts;
+  const rt_pose_part* parts;        /* triangle ranges pairwise disjoint, sphere ranges pairwise disjoint; either count may be 0, not both */
+  uint32_t n_triangles, n_spheres;  /* those of the scene the pose is for */
+  const float* tri_v1;              /* rest pose, [n_triangles][3]; read only inside the covering range */
+  const float* tri_v2;
+  const float* tri_v3;
+  const float* tri_normal;
+  const float* sphere_center;       /* rest pose, [n_spheres][3]; ALL spheres (an update replaces all) */
+  const float* sphere_radius;       /* [n_spheres] */
+} rt_pose_desc;
+typedef struct rt_pose rt_pose;
+
+int rt_pose_create(const rt_pose_desc* desc, int device, rt_pose** out);
+void rt_pose_destroy(rt_pose* pose);
+/* the kernel alone: transforms_dev [n_parts] on the pose's device; enqueued on `hip_stream` */
+int rt_pose_geometry_device(rt_pose* pose, const rt_transform* transforms_dev, void* hip_stream);
+/* kernel + rt_scene_update_device on `hip_stream`; blocks as that call does; `info` may be NULL */
+int rt_pose_apply_device(rt_scene* scene, rt_pose* pose, const rt_transform* transforms_dev, void* hip_stream, rt_update_info* info);
+/* host transforms [n_parts]; blocks */
+int rt_pose_apply(rt_scene* scene, rt_pose* pose, const rt_transform* transforms_host, rt_update_info* info);
+/* waits for the pose's device work; the posed arrays as the last kernel left them: triangle arrays [tri_count][3] over the
+ * covering range, sphere arrays [n_spheres][3] / [n_spheres]; every output nullable */
+int rt_pose_read(rt_pose* pose, float* tri_v1, float* tri_e1, float* tri_e2, float* tri_normal, uint32_t* tri_first, uint32_t* tri_count,
+                 float* sphere_center, float* sphere_r_sq, float* sphere_r_inv);
+/* The host model (no device needed): the same layout as rt_pose_read; every output nullable.  Transforms are not checked. */
+int rt_pose_model(const rt_pose_desc* desc, const rt_transform* transforms, float* tri_v1, float* tri_e1, float* tri_e2, float* tri_normal,
+                  float* sphere_center, float* sphere_r_sq, float* sphere_r_inv);
+
+/* ---- SAH report: how good is the tree an update left behind? -----------------------------------------------------------------
+ *
+ * No reference counterpart.  A refit keeps the topology of creation, so a tree that is deformed without bound decays; this
+ * is the number that says by how much.  For every node and every present child, ratio = half_area(child box) / A_root, with
+ * half_area(lo, hi) = dx dy + dy dz + dz dx in fp64 (left to right, never fused) and A_root the half area of the union of
+ * the root's present child boxes.  q = (uint64_t)(ratio 2^30), truncated; inner_q sums q over inner children, leaf_q sums
+ * q n over leaves of n slots; a ratio that is NaN, negative or above 1 counts in n_bad and adds nothing.
+ *   sah = (inner_q + tri_cost leaf_q) / 2^30,   tri_cost: rt_bvh_tuning.tri_cost as applied at creation.
+ * The sums are 64-bit integers, so the device's are the host model's (rt_sah_packed, csrc/rt_scene_pack.cpp) bit for bit.
+ * sah_created is the value of the tree rt_scene_create built, sah_now of the tree as it stands; their ratio is what a
+ * caller watches.  A scene without triangles reports 0 for both.
+ *
+ * The call BLOCKS and runs on a stream of its own (csrc/rt_sah.hip: one thread per node, one atomic add per sum and
+ * workgroup).  It only reads the node array, as a query does: it may run while frames render.  It must not overlap an
+ * rt_scene_update* / rt_pose_apply* of the same scene; both block, so this is a rule about the caller's threads only.
+ * Out of scope: an automatic rebuild -- the threshold at which recreating the scene pays has not been measured. */
+typedef struct rt_bvh_quality {
+  double sah_created, sah_now;
+  uint64_t inner_q, leaf_q; /* the integer sums behind sah_now */
+  uint32_t n_bad, reserved;
+  double device_ms;
+} rt_bvh_quality;
+int rt_scene_bvh_quality(rt_scene* scene, rt_bvh_quality* out);
+
 /* ---- multi-GPU: tile-partitioned frame + ONE gather of the packed pixels to rank 0 (RCCL over xGMI) ---------
  *
  * Reference: Renderer::render hands RENDER_STRIDE tiles to rayon workers that all write one ImageBuffer
