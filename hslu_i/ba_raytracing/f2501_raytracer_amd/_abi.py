@@ -218,6 +218,14 @@ class rt_bvh_quality(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class rt_rebuild_info(C.Structure):
+    _fields_ = [("device_ms", C.c_double), ("total_ms", C.c_double), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
+                ("max_depth", C.c_uint32), ("max_leaf_size", C.c_uint32), ("tables_invalidated", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 def transform_row(t):
     """Similarity3 -> the 8 floats of an rt_transform: translation, rotor s / xy / xz / yz, scale"""
     r = t.rotation

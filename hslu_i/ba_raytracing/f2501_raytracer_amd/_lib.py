@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
-                   rt_bvh_quality, rt_pose_desc, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_camera, rt_view_desc, rt_view_info)
+                   rt_bvh_quality, rt_pose_desc, rt_rebuild_info, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_camera, rt_view_desc, rt_view_info)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_HIP_LIB selects a diagnostic build of the same library (tools/, A/B timing); default: in-tree
@@ -23,7 +23,7 @@ EXPORTS = (
     "rt_view_create", "rt_view_destroy", "rt_view_set_camera", "rt_view_rays_device", "rt_view_rays", "rt_render_view_device", "rt_render_view",
     "rt_view_read", "rt_view_rays_model", "rt_view_resolve_model",
     "rt_pose_create", "rt_pose_destroy", "rt_pose_geometry_device", "rt_pose_apply_device", "rt_pose_apply", "rt_pose_read", "rt_pose_model",
-    "rt_scene_bvh_quality",
+    "rt_scene_bvh_quality", "rt_scene_rebuild", "rt_scene_rebuild_device",
 )
 
 _lib = None
@@ -157,6 +157,10 @@ def load():
     lib.rt_pose_model.argtypes = [C.POINTER(rt_pose_desc), C.c_void_p] + [C.c_void_p] * 7
     lib.rt_scene_bvh_quality.restype = C.c_int
     lib.rt_scene_bvh_quality.argtypes = [C.c_void_p, C.POINTER(rt_bvh_quality)]
+    lib.rt_scene_rebuild.restype = C.c_int
+    lib.rt_scene_rebuild.argtypes = [C.c_void_p, C.POINTER(rt_rebuild_info)]
+    lib.rt_scene_rebuild_device.restype = C.c_int
+    lib.rt_scene_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_rebuild_info)]
     _lib = lib
     return lib
 

@@ -134,6 +134,7 @@ int rt_scene_create(const rt_scene_desc* d, int device, rt_scene** out) {
   s->n_cells = pk.n_cells;
   s->n_tri_cells = pk.n_tri_cells;
   s->bytes_bvh = pk.bytes_bvh;
+  s->max_leaf = pk.max_leaf;
   memcpy(s->aabb_lo, pk.aabb_lo, sizeof(s->aabb_lo));
   memcpy(s->aabb_hi, pk.aabb_hi, sizeof(s->aabb_hi));
   *out = s;

@@ -255,12 +255,37 @@ struct rt_scene {
   uint64_t sah_created[2] = {0, 0};
   float sah_tri_cost = 2.0f;
   DevBuf sah_dev;
+  uint32_t max_leaf = 4;  // rt_bvh_tuning.max_leaf as applied at creation: what rt_scene_rebuild* collapses its tree to
 };
 
 
 // rt_update.cpp: the device copy of pk.plan (rt_scene_create) and the release of everything an update allocated (rt_scene_destroy)
 int rt_scene_upload_plan(rt_scene* s, const RtPackedScene& pk);
 void rt_scene_release_update(rt_scene* s);
+
+// rt_update.cpp: waits for every frame of the scene still in flight (they read the records an update or a rebuild replaces)
+int rt_scene_wait_frames(rt_scene* s);
+
+// rt_rebuild.cpp: the device side of rt_scene_rebuild* without a handle -- from a blob and two plan parts on the device to
+// a new blob and a new plan, both allocated here (the layout of rt_scene_upload_plan).  Blocks on `stream`.  On any
+// failure nothing is left allocated and `in` is untouched.
+struct RtRebuildIn {
+  RtDevScene dev;             // the scene as it stands, base set
+  const uint32_t* recv_cell;  // device: RtRefitPlan::recv_cell
+  const uint32_t* tri_slot;   // device: RtRefitPlan::tri_slot
+  uint32_t max_leaf, n_materials;
+};
+struct RtRebuildOut {
+  DevBuf blob, plan_dev;
+  size_t plan_off[5] = {0, 0, 0, 0, 0};
+  RtDevScene dev{};           // base set
+  RtRebuildShape shape;
+  std::vector<uint32_t> height_nodes, thr_src, tri_slot;  // host copies of the new plan parts
+  float bounds[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
+  uint32_t receivers_disabled = 0;
+  float device_ms = 0.f;
+};
+int rt_rebuild_device(const RtRebuildIn& in, hipStream_t stream, RtRebuildOut* out);
 
 // rt_api.cpp internals used by the multi-GPU path
 // Multi-GPU staging: when `stage_slot` (device, [tiles_x * tiles_y]) is given, packed pixels are stored into the

@@ -259,6 +259,9 @@ struct RtUpdateArgs {
   uint32_t n_heights, n_materials;
 };
 int rt_launch_update(const RtDevScene& sc, const RtUpdateArgs& u, const rt_scene_delta& d, void* stream, uint32_t* n_launches);
+// The refit half of an update alone, over the whole tree (rt_scene_rebuild*): nodes group by group, octant copies, threaded
+// copy, bounds, receivers.  The groups need only hold every child before its parent.
+int rt_launch_refit(const RtDevScene& sc, const RtUpdateArgs& u, void* stream);
 
 #define RT_QUEUE_QUADS 4u   // float4 per ray record
 #define RT_SORT_TILE 4096u  // buckets per workgroup of the offset scan

@@ -12,7 +12,7 @@
 // group of equal digits); global memory sees no atomics at all.  HBM-bound integer work: 20 bytes per ray and pass.
 #include <hip/hip_runtime.h>
 
-#include "rt_ray_key.h"
+#include "rt_lbvh.h"  // (rt_ray_key.h; the declarations of rt_launch_sort_keys / rt_launch_exclusive_scan)
 
 namespace {
 
@@ -230,32 +230,46 @@ __global__ __launch_bounds__(RT_ORDER_WG) void rt_order_scatter_kernel(const uin
 
 }  // namespace
 
-int rt_launch_order_build(const RtOrderWs& w, const float* origin, const float* direction, uint32_t n, uint32_t origin_bits, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const uint32_t n_wgs = (n + RT_ORDER_WG - 1u) / RT_ORDER_WG, n_tiles = (n + RT_ORDER_TILE - 1u) / RT_ORDER_TILE;
-  const uint32_t n_partial = n_wgs < RT_ORDER_BOUNDS_WGS ? n_wgs : RT_ORDER_BOUNDS_WGS;
-  const uint32_t n_blocks = (256u * n_tiles + RT_ORDER_SCAN_BLOCK - 1u) / RT_ORDER_SCAN_BLOCK;  // <= RT_ORDER_SCAN_BLOCKS (RT_ORDER_MAX_RAYS)
 #define RT_ORDER_LAUNCH(kernel, grid, block, ...)                         \
   do {                                                                    \
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
     const hipError_t e_ = hipGetLastError();                              \
     if (e_ != hipSuccess) return (int)e_;                                 \
   } while (0)
-  RT_ORDER_LAUNCH(rt_order_bounds_kernel, n_partial, RT_ORDER_WG, origin, direction, n, w.partial);
-  RT_ORDER_LAUNCH(rt_order_frame_kernel, 1u, RT_ORDER_WG, (const RtKeyBounds*)w.partial, n_partial, origin_bits, w.frame);
-  RT_ORDER_LAUNCH(rt_order_keys_kernel, n_wgs, RT_ORDER_WG, origin, direction, n, (const RtKeyFrame*)w.frame, w.keys);
+
+int rt_launch_exclusive_scan(uint32_t* counts, uint32_t total, uint32_t* sums, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const uint32_t n_blocks = (total + RT_ORDER_SCAN_BLOCK - 1u) / RT_ORDER_SCAN_BLOCK;  // <= RT_ORDER_SCAN_BLOCKS
+  RT_ORDER_LAUNCH(rt_order_sums_kernel, n_blocks, RT_ORDER_WG, (const uint32_t*)counts, total, sums);
+  RT_ORDER_LAUNCH(rt_order_tops_kernel, 1u, RT_ORDER_SCAN_WG, sums, n_blocks);
+  RT_ORDER_LAUNCH(rt_order_scan_kernel, n_blocks, RT_ORDER_WG, counts, total, (const uint32_t*)sums);
+  return (int)hipSuccess;
+}
+
+int rt_launch_sort_keys(const RtOrderWs& w, uint32_t n, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const uint32_t n_tiles = (n + RT_ORDER_TILE - 1u) / RT_ORDER_TILE;
   const uint32_t* key_in = w.keys;
   const uint32_t* idx_in = nullptr;
   for (uint32_t pass = 0; pass < 4u; pass++) {
     uint32_t* key_out = (pass & 1u) ? w.key_b : w.key_a;
     uint32_t* idx_out = (pass & 1u) ? w.idx_b : w.idx_a;
     RT_ORDER_LAUNCH(rt_order_hist_kernel, n_tiles, RT_ORDER_WG, key_in, n, 8u * pass, w.hist, n_tiles);
-    RT_ORDER_LAUNCH(rt_order_sums_kernel, n_blocks, RT_ORDER_WG, (const uint32_t*)w.hist, 256u * n_tiles, w.sums);
-    RT_ORDER_LAUNCH(rt_order_tops_kernel, 1u, RT_ORDER_SCAN_WG, w.sums, n_blocks);
-    RT_ORDER_LAUNCH(rt_order_scan_kernel, n_blocks, RT_ORDER_WG, w.hist, 256u * n_tiles, (const uint32_t*)w.sums);
+    const int e = rt_launch_exclusive_scan(w.hist, 256u * n_tiles, w.sums, stream_);  // (256 n_tiles / 2048 blocks <= RT_ORDER_SCAN_BLOCKS: RT_ORDER_MAX_RAYS)
+    if (e != (int)hipSuccess) return e;
     RT_ORDER_LAUNCH(rt_order_scatter_kernel, n_tiles, RT_ORDER_WG, key_in, idx_in, key_out, idx_out, n, 8u * pass, (const uint32_t*)w.hist, n_tiles);
     key_in = key_out, idx_in = idx_out;
   }
-#undef RT_ORDER_LAUNCH
   return (int)hipSuccess;
 }
+
+int rt_launch_order_build(const RtOrderWs& w, const float* origin, const float* direction, uint32_t n, uint32_t origin_bits, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const uint32_t n_wgs = (n + RT_ORDER_WG - 1u) / RT_ORDER_WG;
+  const uint32_t n_partial = n_wgs < RT_ORDER_BOUNDS_WGS ? n_wgs : RT_ORDER_BOUNDS_WGS;
+  RT_ORDER_LAUNCH(rt_order_bounds_kernel, n_partial, RT_ORDER_WG, origin, direction, n, w.partial);
+  RT_ORDER_LAUNCH(rt_order_frame_kernel, 1u, RT_ORDER_WG, (const RtKeyBounds*)w.partial, n_partial, origin_bits, w.frame);
+  RT_ORDER_LAUNCH(rt_order_keys_kernel, n_wgs, RT_ORDER_WG, origin, direction, n, (const RtKeyFrame*)w.frame, w.keys);
+  return rt_launch_sort_keys(w, n, stream_);
+}
+#undef RT_ORDER_LAUNCH

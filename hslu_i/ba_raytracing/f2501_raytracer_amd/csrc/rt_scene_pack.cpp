@@ -10,6 +10,7 @@
 #include <cstring>
 #include <string>
 
+#include "rt_lbvh.h"
 #include "rt_refit.h"
 #include "rt_sah.h"
 #include "rt_scene_pack.h"
@@ -49,11 +50,37 @@ int rt_check_scene_desc(const rt_scene_desc* d) {
 // All scene arrays live in ONE device allocation (`blob`): the kernels address them as base + 32-bit byte offset, which
 // the scalar loads take as an SGPR offset (2 scalar instructions per address instead of 4, and one base pointer instead
 // of nine in SGPRs).  Every section starts on a multiple of 256 bytes.
-static void put(std::vector<unsigned char>& blob, uint32_t* off, const void* src, size_t bytes) {
-  blob.resize((blob.size() + 255) / 256 * 256);
-  *off = (uint32_t)blob.size();
-  if (bytes) blob.insert(blob.end(), (const unsigned char*)src, (const unsigned char*)src + bytes);
-  blob.resize(blob.size() + 64);  // the widest scalar load may read past the last record
+// rt_blob_layout decides where every section goes; put() fills one.
+static void put(std::vector<unsigned char>& blob, const uint32_t* off, const void* src, size_t bytes) {
+  if (bytes) memcpy(blob.data() + *off, src, bytes);
+}
+
+size_t rt_blob_layout(const RtBlobCounts& c, RtDevScene* dev) {
+  size_t at = 0;
+  bool fits = true;
+  auto place = [&](uint32_t* off, size_t bytes) {
+    at = (at + 255) / 256 * 256;
+    fits = fits && at < ((size_t)1 << 32);
+    *off = (uint32_t)at;
+    at += bytes + 64;  // the widest scalar load may read past the last record
+  };
+  const size_t ns = c.n_spheres, nt = c.n_triangles, n_slots = c.n_slots, nn = c.n_nodes;
+  place(&dev->off_spheres, 16 * ns);
+  place(&dev->off_sphere_rad, 4 * ns);
+  place(&dev->off_sphere_mat, 4 * ns);
+  place(&dev->off_tri_isect, 48 * n_slots);
+  place(&dev->off_recv, 48 * nt);
+  place(&dev->off_srecv, 4 * (2 * ns + 2));
+  place(&dev->off_tri_shade, 16 * (n_slots + nt));
+  place(&dev->off_tri_id, 4 * n_slots);
+  place(&dev->off_nodes, sizeof(RtNode) * nn);
+  place(&dev->off_nodes_oct, sizeof(RtNode) * 8 * nn);
+  place(&dev->off_nodes_thr, sizeof(RtThrNode) * (size_t)c.n_thr);
+  place(&dev->off_materials, 48 * (size_t)c.n_materials);
+  place(&dev->off_lights, 32 * (size_t)c.n_lights);
+  dev->n_thr = c.n_thr, dev->n_spheres = c.n_spheres, dev->n_triangles = c.n_triangles, dev->n_lights = c.n_lights;
+  dev->n_nodes = c.n_nodes, dev->n_slots = c.n_slots;
+  return fits && at < ((size_t)1 << 32) ? at : 0;
 }
 
 // {cx, cy, cz, r_sq} per sphere, then one float per sphere: an upper bound of the radius (candidate culling)
@@ -435,12 +462,17 @@ void rt_sah_packed(const RtPackedScene& pk, uint64_t sums[2], uint32_t* n_bad) {
 int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {
   *o = RtPackedScene();
   const uint32_t nt = d->n_triangles;
-  pack_spheres(d, o);
   RtBvh bvh;
   std::vector<uint8_t> no_split;
   build_bvh(d, &no_split, &bvh);
   const uint32_t n_slots = (uint32_t)bvh.tri_order.size();
   if (n_slots >= (1u << 24)) return rt_fail(RT_ERR_UNSUPPORTED, "more than 2^24 triangle references");
+  RtBlobCounts counts{d->n_spheres, nt, n_slots, (uint32_t)bvh.nodes.size(), 0u, d->n_materials, d->n_lights};
+  for (const RtNode& nd : bvh.nodes) counts.n_thr += (nd.c0 != RT_NODE_EMPTY) + (nd.c1 != RT_NODE_EMPTY);  // (one threaded entry per child)
+  const size_t bytes = rt_blob_layout(counts, &o->dev);
+  if (!bytes) return rt_fail(RT_ERR_UNSUPPORTED, "scene data exceeds 4 GiB");
+  o->blob.assign(bytes, 0);
+  pack_spheres(d, o);
   scene_bounds(d, o->aabb_lo, o->aabb_hi);
   pack_isect_records(d, bvh, o);
   const double cell = pack_triangle_receivers(d, budget, o);
@@ -458,15 +490,9 @@ int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {
   pack_materials(d, o);
   pack_lights(d, o);
   make_refit_plan(d, bvh, no_split, o);
-  if (o->blob.size() >= (size_t)1 << 32) return rt_fail(RT_ERR_UNSUPPORTED, "scene data exceeds 4 GiB");
   if (bvh.max_depth + 2 > 64) return rt_fail(RT_ERR_UNSUPPORTED, "BVH depth %u exceeds the traversal stack", bvh.max_depth);
 
   o->bytes_bvh = bvh.nodes.size() * sizeof(RtNode) * 9u + (size_t)o->dev.n_thr * sizeof(RtThrNode);
-  o->dev.n_spheres = d->n_spheres;
-  o->dev.n_triangles = nt;
-  o->dev.n_slots = n_slots;
-  o->dev.n_lights = d->n_lights;
-  o->dev.n_nodes = (uint32_t)bvh.nodes.size();
   o->info.n_nodes = (uint32_t)bvh.nodes.size();
   o->info.n_leaves = bvh.n_leaves;
   o->info.max_depth = bvh.max_depth;
@@ -474,5 +500,153 @@ int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {
   o->info.bytes_nodes = bvh.nodes.size() * sizeof(RtNode);
   o->info.bytes_triangles = (size_t)n_slots * (48 + 16 + 4) + (size_t)nt * 16;
   o->info.n_references = n_slots;
+  o->max_leaf = rt_lbvh_max_leaf(d->bvh.max_leaf);
   return RT_OK;
+}
+
+// ---- rebuild --------------------------------------------------------------------------------------------------------------------
+int rt_check_rebuild(const RtDevScene& dev) {
+  if (!dev.n_triangles) return rt_fail(RT_ERR_INVALID_ARG, "rt_scene_rebuild: the scene has no triangles: nothing to rebuild");
+  if (dev.n_slots > dev.n_triangles)
+    return rt_fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: the tree was built with split clipping (%u references of %u triangles); "
+                   "clipped boxes cannot be rebuilt from the slot records", dev.n_slots, dev.n_triangles);
+  if (dev.n_triangles > RT_LBVH_MAX_TRIANGLES)
+    return rt_fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: more than %u triangles", RT_LBVH_MAX_TRIANGLES);
+  return RT_OK;
+}
+
+int rt_rebuild_shape(uint32_t n_triangles, uint32_t max_leaf, const uint32_t* result, RtRebuildShape* out) {
+  RtRebuildShape& sh = *out;
+  sh = RtRebuildShape();
+  if (n_triangles <= max_leaf) {
+    sh.n_nodes = 1u, sh.n_thr = 1u, sh.n_leaves = 1u, sh.max_leaf_size = n_triangles, sh.max_depth = 1u;
+    sh.group_offset = {0u, 1u};
+    return RT_OK;
+  }
+  const uint32_t deepest = result[RT_LBVH_RES_DEPTH];
+  sh.n_nodes = result[RT_LBVH_RES_NODES], sh.n_thr = 2u * sh.n_nodes;
+  sh.n_leaves = result[RT_LBVH_RES_LEAVES], sh.max_leaf_size = result[RT_LBVH_RES_LARGEST];
+  sh.max_depth = deepest + 1u;  // (the leaves below the deepest kept node: rt_build_bvh's count)
+  if (sh.max_depth + 2u > 64u) return rt_fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: BVH depth %u exceeds the traversal stack", sh.max_depth);
+  // groups by descending depth: every child before its parent
+  sh.group_offset.assign(deepest + 1u, 0u);
+  for (uint32_t g = 0; g < deepest; g++) sh.group_offset[g + 1u] = sh.group_offset[g] + result[RT_LBVH_RES_HIST + (deepest - 1u - g)];
+  return RT_OK;
+}
+
+int rt_rebuild_packed(RtPackedScene* pk, uint32_t max_leaf) {
+  if (!pk) return rt_fail(RT_ERR_INVALID_ARG, "null argument");
+  int rc = rt_check_rebuild(pk->dev);
+  if (rc != RT_OK) return rc;
+  max_leaf = rt_lbvh_max_leaf(max_leaf);
+  const RtDevScene& old = pk->dev;
+  const char* old_base = (const char*)pk->blob.data();
+  const uint32_t n = old.n_triangles;
+  const uint32_t* old_tri_slot = pk->plan.tri_slot.data();
+  // keys
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  std::vector<float> centre(3 * (size_t)n);
+  for (uint32_t t = 0; t < n; t++) {
+    float* c = &centre[3 * (size_t)t];
+    rt_lbvh_centre((const float*)(old_base + old.off_tri_isect) + 12 * (size_t)old_tri_slot[t], c);
+    rt_bounds_grow(lo, hi, c[0], c[1], c[2]);
+  }
+  std::vector<uint32_t> key_of(n), idx(n), key(n);
+  for (uint32_t t = 0; t < n; t++) key_of[t] = rt_lbvh_key(lo, hi, &centre[3 * (size_t)t]), idx[t] = t;
+  std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return key_of[a] < key_of[b]; });
+  for (uint32_t s = 0; s < n; s++) key[s] = key_of[idx[s]];
+  // hierarchy
+  std::vector<RtLbvhNode> kn(n);
+  std::vector<uint32_t> rank(n, 0u), depth(n, 0u), start(n, 0u), result(RT_LBVH_RES_WORDS, 0u);
+  if (n > max_leaf) {
+    for (uint32_t i = 0; i + 1u < n; i++) {
+      RtLbvhNode nd;
+      rt_lbvh_karras(key.data(), idx.data(), n, i, &nd);
+      kn[i].f = nd.f, kn[i].l = nd.l, kn[i].split = nd.split;
+      if (i == 0u) kn[0].parent = RT_LBVH_NONE;
+      if (nd.split > nd.f) kn[nd.split].parent = i;
+      if (nd.split + 1u < nd.l) kn[nd.split + 1u].parent = i;
+    }
+    uint32_t run = 0;
+    for (uint32_t i = 0; i < n; i++) rank[i] = run, run += (i + 1u < n && rt_lbvh_keeps(kn[i], max_leaf)) ? 1u : 0u;
+    result[RT_LBVH_RES_NODES] = rank[n - 1u];
+    for (uint32_t i = 0; i + 1u < n; i++) {
+      if (!rt_lbvh_keeps(kn[i], max_leaf)) continue;
+      rt_lbvh_climb(kn.data(), rank.data(), max_leaf, i, &depth[i], &start[i]);
+      result[RT_LBVH_RES_DEPTH] = std::max(result[RT_LBVH_RES_DEPTH], depth[i]);
+      result[RT_LBVH_RES_HIST + (depth[i] - 1u)]++;
+      for (int k = 0; k < 2; k++) {
+        const RtLbvhChild ch = rt_lbvh_child(rank.data(), max_leaf, kn[i], k);
+        if (ch.n) result[RT_LBVH_RES_LEAVES]++, result[RT_LBVH_RES_LARGEST] = std::max(result[RT_LBVH_RES_LARGEST], ch.n);
+      }
+    }
+  }
+  RtRebuildShape sh;
+  rc = rt_rebuild_shape(n, max_leaf, result.data(), &sh);
+  if (rc != RT_OK) return rc;
+  // the new blob
+  RtPackedScene o;
+  const RtBlobCounts counts{old.n_spheres, n, n, sh.n_nodes, sh.n_thr, (uint32_t)pk->plan.mat_class.size(), old.n_lights};
+  const size_t bytes = rt_blob_layout(counts, &o.dev);
+  if (!bytes) return rt_fail(RT_ERR_UNSUPPORTED, "scene data exceeds 4 GiB");
+  o.blob.assign(bytes, 0);
+  char* base = (char*)o.blob.data();
+  RtBlobSection sec[RT_BLOB_CANONICAL_SECTIONS];
+  rt_blob_canonical_sections(old, o.dev, counts.n_materials, sec);
+  for (const RtBlobSection& c : sec)
+    if (c.bytes) memcpy(base + c.to, old_base + c.from, c.bytes);
+  o.plan = pk->plan;
+  RtRefitPlan& pl = o.plan;
+  pl.height_nodes.assign(sh.n_nodes, 0u), pl.height_offset = sh.group_offset, pl.thr_src.assign(sh.n_thr, 0u);
+  for (uint32_t s = 0; s < n; s++) rt_lbvh_gather(old, old_base, old_tri_slot, o.dev, base, pl.tri_slot.data(), s, idx[s]);
+  if (n <= max_leaf) {
+    rt_lbvh_single_root(n, (RtNode*)(base + o.dev.off_nodes), (RtThrNode*)(base + o.dev.off_nodes_thr), pl.thr_src.data(), pl.height_nodes.data());
+  } else {
+    std::vector<uint32_t> cursor(RT_LBVH_DEPTH_BINS + 1u, 0u);
+    for (uint32_t g = 0; g + 1u < sh.group_offset.size(); g++) cursor[sh.max_depth - 2u - g] = sh.group_offset[g];  // (depth k + 1 at k)
+    for (uint32_t i = 0; i + 1u < n; i++) {  // (ascending Karras index = ascending node number: a stable counting sort by depth)
+      if (!rt_lbvh_keeps(kn[i], max_leaf)) continue;
+      rt_lbvh_emit(rank.data(), max_leaf, kn[i], rank[i], start[i], (RtNode*)(base + o.dev.off_nodes), (RtThrNode*)(base + o.dev.off_nodes_thr),
+                   pl.thr_src.data());
+      pl.height_nodes[cursor[depth[i] - 1u]++] = rank[i];
+    }
+  }
+  // the boxes: the refit of this topology
+  for (uint32_t i : pl.height_nodes) rt_upd_node(o.dev, base, i);
+  for (uint32_t oc = 0; oc < 8; oc++)
+    for (uint32_t i = 0; i < o.dev.n_nodes; i++) rt_upd_octant(o.dev, base, oc, i);
+  for (uint32_t i = 0; i < o.dev.n_thr; i++) rt_upd_thr(o.dev, base, pl.thr_src.data(), i);
+  float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY}, b[6];
+  for (uint32_t i = 0; i < o.dev.n_spheres; i++) rt_bounds_sphere(o.dev, base, i, blo, bhi);
+  for (uint32_t s = 0; s < o.dev.n_slots; s++) rt_bounds_slot(o.dev, base, s, blo, bhi);
+  rt_bounds_finish(blo, bhi, b);
+  memcpy(o.aabb_lo, b, 12), memcpy(o.aabb_hi, b + 3, 12);
+  pl.receivers_disabled = 0;
+  for (uint32_t t = 0; t < n; t++) pl.receivers_disabled += rt_upd_recv(o.dev, base, pl.recv_cell.data(), pl.tri_slot.data(), b, t) ? 1u : 0u;
+  // what stays, what follows the new tree
+  o.flag_geo = pk->flag_geo, o.n_cells = pk->n_cells, o.n_tri_cells = pk->n_tri_cells, o.max_leaf = pk->max_leaf;
+  o.info = pk->info;
+  rt_rebuild_info_of(sh, n, &o.info, &o.bytes_bvh);
+  *pk = std::move(o);
+  return RT_OK;
+}
+
+void rt_rebuild_info_of(const RtRebuildShape& sh, uint32_t n_triangles, rt_bvh_info* info, size_t* bytes_bvh) {
+  info->n_nodes = sh.n_nodes, info->n_leaves = sh.n_leaves, info->max_depth = sh.max_depth, info->max_leaf_size = sh.max_leaf_size;
+  info->bytes_nodes = (size_t)sh.n_nodes * sizeof(RtNode);
+  info->bytes_triangles = (size_t)n_triangles * (48 + 16 + 4) + (size_t)n_triangles * 16;
+  info->n_references = n_triangles;
+  *bytes_bvh = (size_t)sh.n_nodes * sizeof(RtNode) * 9u + (size_t)sh.n_thr * sizeof(RtThrNode);
+}
+
+void rt_blob_canonical_sections(const RtDevScene& from, const RtDevScene& to, uint32_t n_materials, RtBlobSection out[RT_BLOB_CANONICAL_SECTIONS]) {
+  const size_t ns = from.n_spheres, nt = from.n_triangles;
+  out[0] = {from.off_spheres, to.off_spheres, 16 * ns};
+  out[1] = {from.off_sphere_rad, to.off_sphere_rad, 4 * ns};
+  out[2] = {from.off_sphere_mat, to.off_sphere_mat, 4 * ns};
+  out[3] = {from.off_tri_shade + 16 * (size_t)from.n_slots, to.off_tri_shade + 16 * (size_t)to.n_slots, 16 * nt};
+  out[4] = {from.off_recv, to.off_recv, 48 * nt};
+  out[5] = {from.off_srecv, to.off_srecv, 4 * (2 * ns + 2)};
+  out[6] = {from.off_materials, to.off_materials, 48 * (size_t)n_materials};
+  out[7] = {from.off_lights, to.off_lights, 32 * (size_t)from.n_lights};
 }

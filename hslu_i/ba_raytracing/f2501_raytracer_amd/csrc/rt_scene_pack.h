@@ -36,7 +36,24 @@ struct RtPackedScene {
   size_t bytes_bvh = 0;             // of `blob`: nodes + octant copies + threaded copy
   float aabb_lo[3] = {0.f, 0.f, 0.f}, aabb_hi[3] = {1.f, 1.f, 1.f};  // bounds of everything a ray can hit
   RtRefitPlan plan;
+  uint32_t max_leaf = 4;            // rt_bvh_tuning.max_leaf as applied at creation (a rebuild collapses to the same size)
 };
+
+// ---- blob layout ------------------------------------------------------------------------------------------------------------
+// The one place that decides where the sections of a blob go (rt_pack_scene, rt_rebuild_packed, rt_scene_rebuild*): every
+// section on a multiple of 256 bytes with 64 bytes of slack behind it.  Sets every off_* and count of `dev` (base stays) and
+// returns the size of the blob, or 0 when it would not stay below 4 GiB.
+struct RtBlobCounts {
+  uint32_t n_spheres, n_triangles, n_slots, n_nodes, n_thr, n_materials, n_lights;
+};
+size_t rt_blob_layout(const RtBlobCounts& c, RtDevScene* dev);
+// the sections that do not depend on the tree (spheres, their radii and materials, canonical shading records, receiver
+// records, sphere receivers, materials, lights): where each lies in one layout and in another
+#define RT_BLOB_CANONICAL_SECTIONS 8
+struct RtBlobSection {
+  size_t from, to, bytes;
+};
+void rt_blob_canonical_sections(const RtDevScene& from, const RtDevScene& to, uint32_t n_materials, RtBlobSection out[RT_BLOB_CANONICAL_SECTIONS]);
 
 // the checks of an rt_scene_desc that need no device: RT_OK or RT_ERR_INVALID_ARG
 int rt_check_scene_desc(const rt_scene_desc* d);
@@ -52,6 +69,24 @@ int rt_check_scene_delta(const RtDevScene& dev, const RtRefitPlan& plan, const r
 // Applies a delta of HOST arrays to a packed scene with the arithmetic of the update kernels (rt_refit.h: the same
 // functions): the specification of rt_scene_update, checked on the CPU.  Same return codes as rt_check_scene_delta.
 int rt_refit_packed(RtPackedScene* pk, const rt_scene_delta* d);
+
+// ---- rebuild (rt_scene_rebuild*; the tree: rt_lbvh.h) ----------------------------------------------------------------------------
+// what a rebuild refuses of a scene, without a device: no triangles (RT_ERR_INVALID_ARG), a split-clipped tree or too many
+// triangles (RT_ERR_UNSUPPORTED)
+int rt_check_rebuild(const RtDevScene& dev);
+// The shape of a rebuilt tree from the counts of phase 1 (`result`: the words RT_LBVH_RES_* of rt_lbvh.h; not read when
+// n_triangles <= max_leaf): what the new blob is laid out with, and the plan's groups -- kept nodes by descending depth.
+// RT_ERR_UNSUPPORTED for a tree deeper than the traversal stack (the rule of rt_pack_scene).
+struct RtRebuildShape {
+  uint32_t n_nodes = 0, n_thr = 0, n_leaves = 0, max_leaf_size = 0, max_depth = 0;
+  std::vector<uint32_t> group_offset;
+};
+int rt_rebuild_shape(uint32_t n_triangles, uint32_t max_leaf, const uint32_t* result, RtRebuildShape* out);
+void rt_rebuild_info_of(const RtRebuildShape& sh, uint32_t n_triangles, rt_bvh_info* info, size_t* bytes_bvh);
+// Rebuilds the tree of a packed scene from the slot records it holds, with the functions of rt_lbvh.h and rt_refit.h -- the
+// same functions the kernels are made of: the specification of rt_scene_rebuild, checked on the CPU.  max_leaf as
+// rt_bvh_tuning.max_leaf (0 = default).  Any refusal leaves `pk` untouched.
+int rt_rebuild_packed(RtPackedScene* pk, uint32_t max_leaf);
 
 // ---- SAH report ------------------------------------------------------------------------------------------------------------
 // The two integer sums of rt_sah.h over the tree of a packed scene as it stands: sums[0] = inner_q, sums[1] = leaf_q, and

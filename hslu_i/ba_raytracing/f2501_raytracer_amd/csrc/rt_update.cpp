@@ -34,6 +34,19 @@ void rt_scene_release_update(rt_scene* s) {
   s->upd_stage = nullptr, s->upd_back = nullptr, s->upd_stage_cap = 0;
 }
 
+int rt_scene_wait_frames(rt_scene* s) {
+  if (s->tables_pending) {
+    HIP_TRY(hipStreamSynchronize(s->tables_stream));
+    s->tables_pending = false;
+  }
+  for (int b = 0; b < RT_SLOTS; b++)
+    if (s->frame_pending[b]) {
+      HIP_TRY(hipEventSynchronize(s->frame_ev[b]));
+      s->frame_pending[b] = false;
+    }
+  return RT_OK;
+}
+
 namespace {
 
 // the arrays of a delta as one run of floats: {array, floats} in staging order (sphere_r_inv is not read: not staged)
@@ -59,15 +72,8 @@ int update_impl(rt_scene* s, const rt_scene_delta* host, rt_scene_delta dev, hip
   const auto t0 = std::chrono::steady_clock::now();
   HIP_TRY(hipSetDevice(s->device));
   // every frame of this scene still in flight reads the old records
-  if (s->tables_pending) {
-    HIP_TRY(hipStreamSynchronize(s->tables_stream));
-    s->tables_pending = false;
-  }
-  for (int b = 0; b < RT_SLOTS; b++)
-    if (s->frame_pending[b]) {
-      HIP_TRY(hipEventSynchronize(s->frame_ev[b]));
-      s->frame_pending[b] = false;
-    }
+  const int rc_wait = rt_scene_wait_frames(s);
+  if (rc_wait != RT_OK) return rc_wait;
   if (!host && dev.materials) {  // the transmissive classes of device rows: read them back to check them
     std::vector<float> rows(s->plan.mat_class.size() * RT_MATERIAL_STRIDE);
     HIP_TRY(hipMemcpyAsync(rows.data(), dev.materials, rows.size() * 4, hipMemcpyDeviceToHost, stream));

@@ -118,7 +118,22 @@ int rt_launch_update(const RtDevScene& sc, const RtUpdateArgs& u, const rt_scene
   }
   if (d.materials && u.n_materials) RT_UPD_LAUNCH(rt_upd_materials_kernel, dim3(wgs(u.n_materials)), RT_UPD_WG, sc, u.base, d.materials, u.n_materials);
   if (d.lights && sc.n_lights) RT_UPD_LAUNCH(rt_upd_lights_kernel, dim3(wgs(sc.n_lights)), RT_UPD_WG, sc, u.base, d.lights);
-#undef RT_UPD_LAUNCH
   if (n_launches) *n_launches = n;
   return (int)hipSuccess;
 }
+
+int rt_launch_refit(const RtDevScene& sc, const RtUpdateArgs& u, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  uint32_t n = 0;
+  for (uint32_t h = 0; h < u.n_heights; h++) {
+    const uint32_t first = u.height_offset[h], cnt = u.height_offset[h + 1] - first;
+    if (cnt) RT_UPD_LAUNCH(rt_upd_nodes_kernel, dim3(wgs(cnt)), RT_UPD_WG, sc, u.base, u.height_nodes + first, cnt);
+  }
+  RT_UPD_LAUNCH(rt_upd_octants_kernel, dim3(wgs(sc.n_nodes), 8), RT_UPD_WG, sc, u.base);
+  if (sc.n_thr) RT_UPD_LAUNCH(rt_upd_threaded_kernel, dim3(wgs(sc.n_thr)), RT_UPD_WG, sc, u.base, u.thr_src);
+  RT_UPD_LAUNCH(rt_upd_bounds_kernel, dim3(1), RT_UPD_BOUNDS_WG, sc, (const char*)u.base, u.bounds);
+  if (sc.n_triangles) RT_UPD_LAUNCH(rt_upd_recv_kernel, dim3(wgs(sc.n_triangles)), RT_UPD_WG, sc, u.base, u.recv_cell, u.tri_slot, u.bounds);
+  (void)n;
+  return (int)hipSuccess;
+}
+#undef RT_UPD_LAUNCH

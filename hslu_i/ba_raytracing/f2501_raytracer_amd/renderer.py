@@ -270,6 +270,16 @@ class DeviceScene:
         _lib.check(_lib.load().rt_scene_bvh_quality(self.handle, C.byref(q)))
         return q.as_dict()
 
+    def rebuild(self, info: bool = False):
+        """`rt_scene_rebuild`: a new tree for this scene, built on the device from the geometry it holds right now -- the
+        repair for a tree that `update` / `DevicePose.apply` have refitted until it decayed (`bvh_quality`).  The tree is an
+        LBVH with the leaf size of creation; renders and queries behave as on a DeviceScene created from the current
+        description.  Blocks; runs on a stream of its own; waits for the scene's frames in flight.  The description this
+        scene holds (`flat`) is unchanged.  Returns None, or with info=True the rt_rebuild_info of the call as a dict."""
+        inf = _abi.rt_rebuild_info()
+        _lib.check(_lib.load().rt_scene_rebuild(self.handle, C.byref(inf)))
+        return inf.as_dict() if info else None
+
     def update(self, flat, info: bool = False, tri_first: int = 0):
         """New values for the objects this scene already has, in place (`rt_scene_update`): the BVH is refitted on the
         device, not rebuilt, and afterwards every render and query behaves as on a DeviceScene created from the new

@@ -738,7 +738,7 @@ int rt_scene_memory_info(const rt_scene* scene, rt_scene_info* out);
  * Both forms BLOCK: at entry they wait for every frame of this scene still in flight, at exit they synchronise their
  * stream (the new scene bounds are read back there).  Ray queries the caller still has in flight on streams of its own are
  * NOT waited for: finish them first.  Asynchronous updates are out of scope; so are adding or removing
- * objects, a rebuild heuristic, and the refit of split-clipped trees.
+ * objects, a rebuild heuristic (the rebuild itself: rt_scene_rebuild), and the refit of split-clipped trees.
  *
  * RT_ERR_INVALID_ARG (rt_last_error names the field): NULL scene or delta; wrong abi_version; a partial group;
  * tri_first + tri_count > n_triangles; a delta that changes nothing; a progressive render owns the scene; a material row
@@ -881,7 +881,7 @@ int rt_pose_model(const rt_pose_desc* desc, const rt_transform* transforms, floa
  * The call BLOCKS and runs on a stream of its own (csrc/rt_sah.hip: one thread per node, one atomic add per sum and
  * workgroup).  It only reads the node array, as a query does: it may run while frames render.  It must not overlap an
  * rt_scene_update* / rt_pose_apply* of the same scene; both block, so this is a rule about the caller's threads only.
- * Out of scope: an automatic rebuild -- the threshold at which recreating the scene pays has not been measured. */
+ * Out of scope: an automatic rebuild -- the threshold at which rebuilding (rt_scene_rebuild) pays has not been measured. */
 typedef struct rt_bvh_quality {
   double sah_created, sah_now;
   uint64_t inner_q, leaf_q; /* the integer sums behind sah_now */
@@ -889,6 +889,54 @@ typedef struct rt_bvh_quality {
   double device_ms;
 } rt_bvh_quality;
 int rt_scene_bvh_quality(rt_scene* scene, rt_bvh_quality* out);
+
+/* ---- BVH rebuild: a new tree for an existing handle, on the device, from the geometry the handle holds right now --------------
+ *
+ * No reference counterpart.  A refit (rt_scene_update*, rt_pose_apply*) keeps the topology of creation, so a scene that keeps
+ * deforming gets slower; rt_scene_bvh_quality says by how much.  A rebuild replaces the tree without a host round trip: its
+ * input is the leaf-slot intersection records of the scene as it stands, nothing comes from the caller.
+ *
+ * The tree is an LBVH (csrc/rt_lbvh.h): canonical triangle t gets a 30-bit Morton key of its centre, 0.5 (min + max) of its
+ * three vertices per axis, quantised to 10 bits per axis inside the bounds of all finite centres; the triangles are sorted
+ * by (key, canonical index), the sorted position being the new leaf slot; the hierarchy is Karras' radix tree over the sorted
+ * 62-bit values key << 32 | index, in which every range of at most max_leaf triangles (rt_bvh_tuning.max_leaf as applied at
+ * creation) becomes one leaf.  The boxes, the per-octant copies, the threaded copy, the scene bounds and the receiver records
+ * are then computed by the refit kernels of rt_scene_update.  A host model compiled from the same sources specifies every
+ * byte (rt_rebuild_packed, csrc/rt_scene_pack.cpp).  An LBVH splits at Morton cells, not by surface area: on UNDEFORMED
+ * geometry it is looser than the binned-SAH tree of rt_scene_create; it pays once a refitted tree has decayed past it
+ * (profiles/rebuild.md has the SAH figures).
+ *
+ * After the call returns, renders and queries behave as on a handle freshly created from the current geometry: hit ids and
+ * distances are the same bits; colours agree within the rounding of sums taken in another leaf order.  rt_scene_bvh_info
+ * and rt_scene_memory_info describe the new tree; rt_scene_bvh_quality.sah_created stays the value of creation, sah_now is
+ * the rebuilt tree's.  Receiver tables, tile costs and queue estimates are invalidated as a geometry update invalidates
+ * them (the cell lists hold leaf slots).  rt_pose, rt_ray_order and rt_view handles stay valid: they speak in canonical
+ * indices.  Later rt_scene_update* / rt_pose_apply* calls refit the new tree.
+ *
+ * Both forms BLOCK: at entry they wait for every frame of this scene still in flight, at exit they synchronise their stream.
+ * Ray queries the caller still has in flight on streams of its own are NOT waited for: finish them first.  While the call
+ * runs the scene holds a SECOND blob next to the old one, plus 48 bytes of scratch per triangle; the old blob and the
+ * scratch are freed before it returns.  Any failure before the swap -- a refusal, an allocation, a HIP error -- leaves the
+ * handle exactly as it was.
+ *
+ * RT_ERR_INVALID_ARG, before any HIP call: NULL scene; a progressive render owns the scene; a scene without triangles
+ * ("nothing to rebuild").
+ * RT_ERR_UNSUPPORTED: a split-clipped tree (n_references > n_triangles: a clipped reference has no record to rebuild
+ * from), also before any HIP call; more than 2^23 - 8 triangles; a rebuilt tree deeper than the traversal stack (max_depth
+ * + 2 > 64, the rule of rt_scene_create -- a guard only: a radix tree over 30 key bits and 23 index bits is at most 53 deep).
+ * Multi-GPU: the caller rebuilds each per_gpu[i].  Out of scope: an automatic trigger (profiles/rebuild.md has the numbers of
+ * tools/rebuild_bench.py on one scene: not enough to pick a threshold, and a rebuild can lose); asynchronous rebuilds;
+ * rebuilding with another max_leaf than the one of creation. */
+typedef struct rt_rebuild_info {
+  double device_ms, total_ms;
+  uint32_t n_nodes, n_leaves, max_depth, max_leaf_size; /* of the new tree, as rt_bvh_info */
+  uint32_t tables_invalidated;                          /* RT_UPDATE_INVALIDATES_* */
+  uint32_t reserved;
+} rt_rebuild_info;
+/* on a private stream; `info` may be NULL */
+int rt_scene_rebuild(rt_scene* scene, rt_rebuild_info* info);
+/* the kernels run on `hip_stream` */
+int rt_scene_rebuild_device(rt_scene* scene, void* hip_stream, rt_rebuild_info* info);
 
 /* ---- multi-GPU: tile-partitioned frame + ONE gather of the packed pixels to rank 0 (RCCL over xGMI) ---------
  *
