@@ -210,6 +210,12 @@ class rt_pose_desc(C.Structure):
                 ("tri_normal", C.c_void_p), ("sphere_center", C.c_void_p), ("sphere_radius", C.c_void_p)]
 
 
+class rt_skin_desc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("n_vertices", C.c_uint32), ("n_bones", C.c_uint32), ("tri_first", C.c_uint32),
+                ("tri_count", C.c_uint32), ("n_triangles", C.c_uint32), ("position", C.c_void_p), ("normal", C.c_void_p),
+                ("indices", C.c_void_p), ("bone", C.c_void_p), ("weight", C.c_void_p)]
+
+
 class rt_bvh_quality(C.Structure):
     _fields_ = [("sah_created", C.c_double), ("sah_now", C.c_double), ("inner_q", C.c_uint64), ("leaf_q", C.c_uint64),
                 ("n_bad", C.c_uint32), ("reserved", C.c_uint32), ("device_ms", C.c_double)]
@@ -255,6 +261,30 @@ def make_pose_desc(parts, n_triangles, n_spheres, v1=None, v2=None, v3=None, nor
             a = np.ascontiguousarray(a, np.float32)
             keep.append(a)
             setattr(d, field, a.ctypes.data)
+    return d, keep
+
+
+def make_skin_desc(position, normal, indices, bone, weight, n_bones, tri_first, n_triangles):
+    """rt_skin_desc of an indexed mesh: position (V, 3) float32, normal (V, 3) float32 or None, indices (T, 3) uint32, bone
+    (V, 4) uint16, weight (V, 4) float32; the mesh is canonical triangles [tri_first, tri_first + T) of a scene of
+    n_triangles.  Returns (desc, keepalive)."""
+    pos = np.ascontiguousarray(position, np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+    b = np.ascontiguousarray(bone, np.uint16).reshape(-1, 4)
+    w = np.ascontiguousarray(weight, np.float32).reshape(-1, 4)
+    keep = [pos, idx, b, w]
+    if b.shape[0] != pos.shape[0] or w.shape[0] != pos.shape[0]:
+        raise ValueError(f"bone {b.shape} and weight {w.shape} must be (n_vertices, 4) for {pos.shape[0]} vertices")
+    d = rt_skin_desc()
+    d.abi_version, d.n_vertices, d.n_bones = RT_ABI_VERSION, int(pos.shape[0]), int(n_bones)
+    d.tri_first, d.tri_count, d.n_triangles = int(tri_first), int(idx.shape[0]), int(n_triangles)
+    d.position, d.indices, d.bone, d.weight = pos.ctypes.data, idx.ctypes.data, b.ctypes.data, w.ctypes.data
+    if normal is not None:
+        nrm = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        if nrm.shape != pos.shape:
+            raise ValueError(f"normal {nrm.shape} must match position {pos.shape}")
+        keep.append(nrm)
+        d.normal = nrm.ctypes.data
     return d, keep
 
 

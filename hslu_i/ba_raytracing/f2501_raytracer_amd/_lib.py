@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
-                   rt_bvh_quality, rt_pose_desc, rt_rebuild_info, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_camera, rt_view_desc, rt_view_info)
+                   rt_bvh_quality, rt_pose_desc, rt_rebuild_info, rt_skin_desc, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_camera, rt_view_desc, rt_view_info)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_HIP_LIB selects a diagnostic build of the same library (tools/, A/B timing); default: in-tree
@@ -23,6 +23,7 @@ EXPORTS = (
     "rt_view_create", "rt_view_destroy", "rt_view_set_camera", "rt_view_rays_device", "rt_view_rays", "rt_render_view_device", "rt_render_view",
     "rt_view_read", "rt_view_rays_model", "rt_view_resolve_model",
     "rt_pose_create", "rt_pose_destroy", "rt_pose_geometry_device", "rt_pose_apply_device", "rt_pose_apply", "rt_pose_read", "rt_pose_model",
+    "rt_skin_create", "rt_skin_destroy", "rt_skin_geometry_device", "rt_skin_apply_device", "rt_skin_apply", "rt_skin_read", "rt_skin_model",
     "rt_scene_bvh_quality", "rt_scene_rebuild", "rt_scene_rebuild_device",
 )
 
@@ -155,6 +156,20 @@ def load():
     lib.rt_pose_read.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.POINTER(C.c_uint32)] * 2 + [C.c_void_p] * 3
     lib.rt_pose_model.restype = C.c_int
     lib.rt_pose_model.argtypes = [C.POINTER(rt_pose_desc), C.c_void_p] + [C.c_void_p] * 7
+    lib.rt_skin_create.restype = C.c_int
+    lib.rt_skin_create.argtypes = [C.POINTER(rt_skin_desc), C.c_int, C.POINTER(C.c_void_p)]
+    lib.rt_skin_destroy.restype = None
+    lib.rt_skin_destroy.argtypes = [C.c_void_p]
+    lib.rt_skin_geometry_device.restype = C.c_int
+    lib.rt_skin_geometry_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_skin_apply_device.restype = C.c_int
+    lib.rt_skin_apply_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rt_update_info)]
+    lib.rt_skin_apply.restype = C.c_int
+    lib.rt_skin_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rt_update_info)]
+    lib.rt_skin_read.restype = C.c_int
+    lib.rt_skin_read.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+    lib.rt_skin_model.restype = C.c_int
+    lib.rt_skin_model.argtypes = [C.POINTER(rt_skin_desc), C.c_void_p] + [C.c_void_p] * 6
     lib.rt_scene_bvh_quality.restype = C.c_int
     lib.rt_scene_bvh_quality.argtypes = [C.c_void_p, C.POINTER(rt_bvh_quality)]
     lib.rt_scene_rebuild.restype = C.c_int

@@ -9,7 +9,7 @@ yields them (models in order of appearance, faces in order inside a model).
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -122,6 +122,36 @@ def _load_packed(path: str):
                                     TransmissionProperties(F(r[5]), F(r[6]), bool(r[8] != 0), F(r[7])))
     fmat = [str(i) if i >= 0 else None for i in z["face_material"]]
     return z["positions"].astype(np.float32), z["normals"].astype(np.float32), z["corners"].astype(np.int64), fmat, mats
+
+
+class IndexedMesh(NamedTuple):
+    """an indexed triangle mesh: position (V, 3) float32, normal (V, 3) float32 or None, indices (T, 3) uint32"""
+
+    position: np.ndarray
+    normal: Optional[np.ndarray]
+    indices: np.ndarray
+
+
+def load_indexed_mesh(path: str) -> IndexedMesh:
+    """The mesh of an .obj (or packed .npz) unified as tobj's `single_index: true` unifies it (scene.rs:43-134): one vertex per
+    distinct (v, vn) corner pair, in the order of first occurrence; triangles in file order.  Nothing is transformed: this is
+    the rest mesh a `DeviceSkin` takes.  Raises if only some corners have normals."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    pos, nrm, corners = (_load_packed(path) if path.endswith(".npz") else parse_obj(path))[:3]
+    pairs = corners.reshape(-1, 2)
+    have = pairs[:, 1] >= 0
+    if have.any() and not have.all():
+        raise ValueError(f"{path}: {int((~have).sum())} of {len(have)} corners have no normal; an indexed mesh has normals on all corners or on none")
+    key = pairs[:, 0] * (int(pairs[:, 1].max(initial=0)) + 2) + (pairs[:, 1] + 1)
+    _, first, inverse = np.unique(key, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")  # distinct pairs by first occurrence
+    rank = np.empty(len(order), np.int64)
+    rank[order] = np.arange(len(order))
+    unified = pairs[first[order]]
+    position = np.ascontiguousarray(pos[unified[:, 0]], np.float32)
+    normal = np.ascontiguousarray(nrm[unified[:, 1]], np.float32) if have.all() and len(have) else None
+    return IndexedMesh(position, normal, np.ascontiguousarray(rank[inverse.reshape(-1)].reshape(-1, 3), np.uint32))
 
 
 def load_obj_scene(path: str, transform: Optional[Similarity3], continue_on_material_failure: bool = True) -> Scene:

@@ -272,7 +272,7 @@ class DeviceScene:
 
     def rebuild(self, info: bool = False):
         """`rt_scene_rebuild`: a new tree for this scene, built on the device from the geometry it holds right now -- the
-        repair for a tree that `update` / `DevicePose.apply` have refitted until it decayed (`bvh_quality`).  The tree is an
+        repair for a tree that `update` / `DevicePose.apply` / `DeviceSkin.apply` have refitted until it decayed (`bvh_quality`).  The tree is an
         LBVH with the leaf size of creation; renders and queries behave as on a DeviceScene created from the current
         description.  Blocks; runs on a stream of its own; waits for the scene's frames in flight.  The description this
         scene holds (`flat`) is unchanged.  Returns None, or with info=True the rt_rebuild_info of the call as a dict."""
@@ -661,6 +661,91 @@ class DevicePose:
     def close(self):
         if self._h is not None:
             _lib.load().rt_pose_destroy(self._h)  # (waits for the pose's device work)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceSkin:
+    """Owns an `rt_skin*`: an indexed mesh in rest pose on the device of a DeviceScene, deformed by linear blend skinning.
+    `apply` takes 32 bytes per bone, skins the shared vertices, rebuilds the mesh's triangles from them and refits the scene
+    in place, as `DeviceScene.update` would with arrays skinned on the host.
+
+    mesh: an `obj.IndexedMesh` (position, normal or None, indices); it IS canonical triangles [tri_first, tri_first + T) of
+    the scene.  bone: (V, 4) integers below n_bones, weight: (V, 4) float32; a zero weight skips its slot, weights are not
+    normalised.  n_bones: default the largest bone index used + 1."""
+
+    SKIN_OUT = ("position", "normal") + _abi.TRIANGLE_GROUP
+
+    def __init__(self, scene: "DeviceScene", mesh, bone, weight, tri_first: int = 0, n_bones: Optional[int] = None):
+        b = np.asarray(bone)
+        if b.size and (b.min() < 0 or b.max() > 0xFFFF):
+            raise ValueError("bone indices must be in [0, 65536)")
+        if n_bones is None:
+            n_bones = int(b.max()) + 1 if b.size else 1
+        desc, keep = _abi.make_skin_desc(mesh.position, mesh.normal, mesh.indices, b, weight, n_bones, tri_first, scene.flat.n_triangles)
+        h = C.c_void_p()
+        _lib.check(_lib.load().rt_skin_create(C.byref(desc), scene.device, C.byref(h)))
+        self._h = h
+        self.scene, self.n_bones, self.has_normals = scene, int(n_bones), mesh.normal is not None
+        self.n_vertices, self.tri_first, self.tri_count = int(desc.n_vertices), int(desc.tri_first), int(desc.tri_count)
+
+    @property
+    def handle(self) -> C.c_void_p:
+        if self._h is None:
+            raise RuntimeError("skin destroyed")
+        return self._h
+
+    def geometry(self) -> Dict:
+        """`rt_skin_read`: the arrays as the last apply left them (before any: the rest mesh) -- position / normal over the
+        vertices (normal None for a mesh without vertex normals), tri_v1 / tri_e1 / tri_e2 / tri_normal over the mesh's
+        triangles, and tri_first, tri_count."""
+        out = {k: np.empty((self.n_vertices if k in ("position", "normal") else self.tri_count, 3), np.float32) for k in self.SKIN_OUT}
+        if not self.has_normals:
+            out["normal"] = None
+        _lib.check(_lib.load().rt_skin_read(self.handle, *[None if out[k] is None else out[k].ctypes.data for k in self.SKIN_OUT]))
+        out.update(tri_first=self.tri_first, tri_count=self.tri_count)
+        return out
+
+    def apply(self, bones, info: bool = False):
+        """Skins the mesh and refits the scene (`rt_skin_apply`; blocks).  bones: a list of n_bones `Similarity3`, an
+        (n_bones, 8) float32 numpy array of rt_transform rows (`_abi.transform_row`), or a float32 torch tensor of that shape
+        on the scene's device (`rt_skin_apply_device` on torch.cuda.current_stream(): no bone crosses the bus).
+        `scene.flat` follows.  Returns None, or with info=True the rt_update_info of the call as a dict."""
+        lib = _lib.load()
+        inf = _abi.rt_update_info()
+        if isinstance(bones, (list, tuple, np.ndarray)):
+            if isinstance(bones, np.ndarray) and (bones.dtype != np.float32 or bones.shape != (self.n_bones, 8)):
+                raise ValueError(f"bones must be a float32 array of shape ({self.n_bones}, 8), got {bones.dtype} {bones.shape}")
+            rows = _abi.transform_rows(bones)
+            if rows.shape[0] != self.n_bones:
+                raise ValueError(f"{rows.shape[0]} transforms for {self.n_bones} bones")
+            _lib.check(lib.rt_skin_apply(self.scene.handle, self.handle, rows.ctypes.data, C.byref(inf)))
+        else:
+            import torch
+
+            want = torch.device("cuda", self.scene.device)
+            t = bones
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != want or tuple(t.shape) != (self.n_bones, 8):
+                raise ValueError(f"bones must be a float32 tensor of shape ({self.n_bones}, 8) on {want} (the scene's device)")
+            t = t.contiguous()
+            _lib.check(lib.rt_skin_apply_device(self.scene.handle, self.handle, C.c_void_p(t.data_ptr()), DeviceScene._stream_of(t), C.byref(inf)))
+        # the description the scene holds follows (the call has synchronised its stream)
+        g = self.geometry()
+        old = self.scene.flat
+        new = {k: np.array(getattr(old, k), copy=True) for k in FlatScene.__dataclass_fields__}
+        for k in _abi.TRIANGLE_GROUP:
+            new[k][self.tri_first:self.tri_first + self.tri_count] = g[k]
+        self.scene.flat = FlatScene(**new).contiguous()
+        return inf.as_dict() if info else None
+
+    def close(self):
+        if self._h is not None:
+            _lib.load().rt_skin_destroy(self._h)  # (waits for the skin's device work)
             self._h = None
 
     def __del__(self):

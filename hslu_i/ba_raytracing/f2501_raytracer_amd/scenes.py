@@ -30,18 +30,21 @@ def mesh_path(cfg: RenderConfig, model: Optional[str] = None) -> str:
     return os.path.join(_DATA_DIR, model + ".npz")
 
 
+def semesterbild_text_transform(cfg: RenderConfig) -> Similarity3:
+    """where semesterbild places its text mesh (src/main.rs:30-46): the transform a skin of that mesh takes as its one bone"""
+    SW, SH, SD, AVG = cfg.scene_width, cfg.scene_height, cfg.scene_depth, cfg.average_scene_dimension
+    return Similarity3.new(
+        Vec3.new(F(0.0135) * SW, F(0.145) * SH, F(0.885) * SD),
+        Rotor3.from_euler_angles(0.0, -0.015, 0.0),
+        F(1.226) * AVG,
+    )
+
+
 def semesterbild(cfg: RenderConfig, model: Optional[str] = None) -> Scene:
     SW, SH, SD, AVG = cfg.scene_width, cfg.scene_height, cfg.scene_depth, cfg.average_scene_dimension
     from .obj import load_obj_scene
 
-    scene = load_obj_scene(
-        mesh_path(cfg, model),
-        Similarity3.new(
-            Vec3.new(F(0.0135) * SW, F(0.145) * SH, F(0.885) * SD),
-            Rotor3.from_euler_angles(0.0, -0.015, 0.0),
-            F(1.226) * AVG,
-        ),
-    )
+    scene = load_obj_scene(mesh_path(cfg, model), semesterbild_text_transform(cfg))
 
     def sphere(cx, cy, cz, r, color, metallic, shininess, tp):
         scene.add_sphere(SphereData.with_material(

@@ -827,7 +827,8 @@ int rt_scene_update_device(rt_scene* scene, const rt_scene_delta* delta, void* h
  * part uses; on apply a pose whose counts differ from the scene's, a pose on another device than the scene, and what
  * rt_scene_update_device refuses in the delta; in the HOST form only, a non-finite transform member.  The device form
  * cannot look at the transforms: what non-finite geometry does is what rt_scene_update_device does with it.
- * Out of scope: lights are not posed (a caller moves them through rt_scene_update); hierarchies of parts; skinning. */
+ * Out of scope: lights are not posed (a caller moves them through rt_scene_update); hierarchies of parts.  A mesh that
+ * BENDS is an rt_skin (below). */
 typedef struct rt_transform {
   float translation[3];
   float rotor[4]; /* s, xy, xz, yz */
@@ -866,6 +867,81 @@ int rt_pose_read(rt_pose* pose, float* tri_v1, float* tri_e1, float* tri_e2, flo
 int rt_pose_model(const rt_pose_desc* desc, const rt_transform* transforms, float* tri_v1, float* tri_e1, float* tri_e2, float* tri_normal,
                   float* sphere_center, float* sphere_r_sq, float* sphere_r_inv);
 
+/* ---- skinned meshes: an indexed mesh deformed by linear blend skinning on the device, then refitted ---------------------------
+ *
+ * Reference: Scene::from_obj (src/scene/scene.rs:43-134, tobj with single_index: true) works on an INDEXED mesh in two
+ * steps: it transforms the unified vertices and rotates the per-vertex normals, then lerps the three normals per face.  An
+ * rt_skin holds such a mesh in rest pose on the device and does the same per frame, with up to four bones per vertex in
+ * place of the one transform: two kernels (csrc/rt_skin.hip) write the triangle arrays of an rt_scene_delta from 32 bytes
+ * per bone, and rt_scene_update_device takes them.  The mesh IS one range of canonical triangles of a scene,
+ * [tri_first, tri_first + tri_count): triangle tri_first + t is indices[t].
+ *
+ * A bone is an rt_transform, not normalised by the library; T(v) and rotate(n) are those of a pose (above).  Every operation
+ * is one correctly rounded fp32 operation, evaluated as written, left to right, never fused (except the two fma of the
+ * face normal); a - b is a + (-b):
+ *   vertex i:    influences (bone[i][k], weight[i][k]), k = 0..3, in that order; a weight of +0 or -0 is skipped;
+ *                the first influence kept sets   acc = w T_b(v)          (three multiplies)
+ *                every later one adds            acc = acc + w T_b(v)    (per component one multiply, one add)
+ *                normals: the same with rotate_b(n).  No influence kept: the rest position and the rest normal.
+ *                Weights are NOT normalised and no sum is required: one influence of weight 1 gives T_b(v) exactly, so a
+ *                mesh skinned to one bone is the mesh from_obj would have loaded with that transform, normals included
+ *                (a pose, which rotates the lerped normal, deviates there by a few 2^-24).
+ *   triangle t:  indices (i0, i1, i2);  v1 = V[i0];  e1 = V[i1] - V[i0];  e2 = V[i2] - V[i0]
+ *                with vertex normals:     n = (N[i0] 0.5 + N[i1] 0.5) 0.5 + N[i2] 0.5, per component
+ *                without (normal NULL):   c = e1 x e2, cx = e1y e2z + (-e1z) e2y, ...;  d = fma(cx, cx, fma(cy, cy, cz cz));
+ *                                         r = 1 / sqrt(d);  n = c r.  A degenerate triangle gives a non-finite normal: what
+ *                                         such geometry does is what rt_scene_update_device does with it.
+ * The formulas are specified by a host model compiled from the same source as the kernels (csrc/rt_skin.h): rt_skin_model.
+ *
+ * rt_skin_create allocates everything: the rest arrays, the index, bone and weight tables, the skinned vertices, the four
+ * posed triangle arrays (initialised on the host with the rest mesh run through the triangle formula), room for n_bones
+ * staged transforms and a pinned stage.  The device forms allocate nothing.
+ * rt_skin_apply_device enqueues the vertex kernel and the triangle kernel on `hip_stream`, back to back, and calls
+ * rt_scene_update_device with the skin's own device arrays: everything about blocking, invalidation, refusals
+ * (RT_ERR_UNSUPPORTED on split-clipped trees included) and rt_update_info is that call's, unchanged.  rt_skin_apply stages
+ * the bones through the skin's buffer on the null stream and does the same.  rt_skin_geometry_device is the kernels alone.
+ * One apply per skin at a time; a skin's work goes on one stream or is ordered by the caller.
+ *
+ * Refused with RT_ERR_INVALID_ARG (+ rt_last_error, naming the field) before any HIP call: a NULL pointer (normal may be
+ * NULL) or wrong abi_version; n_vertices, tri_count or n_bones 0; n_bones > 65536; tri_first + tri_count > n_triangles; an
+ * index >= n_vertices; a bone index >= n_bones in any of the four slots, zero weight or not; a non-finite weight; on apply
+ * a NULL scene, skin or bones, a skin whose n_triangles differs from the scene's, a skin on another device than the scene,
+ * a progressive render that owns the scene, and what rt_scene_update_device refuses in the delta; in the HOST form only, a
+ * non-finite bone member.
+ * Out of scope: bone hierarchies (bones are final transforms relative to the rest pose: the caller composes parent chains
+ * and inverse binds); morph targets; more than four influences; meshes with normals on some corners only; several skins
+ * batched into one update (each apply is one update; the ranges of different skins must not overlap, which is the caller's
+ * to ensure); lights and spheres. */
+typedef struct rt_skin_desc {
+  uint32_t abi_version;           /* RT_ABI_VERSION */
+  uint32_t n_vertices;            /* >= 1 */
+  uint32_t n_bones;               /* 1 .. 65536 */
+  uint32_t tri_first, tri_count;  /* the canonical triangles this mesh IS; tri_count >= 1 */
+  uint32_t n_triangles;           /* of the scene the skin is for */
+  const float* position;          /* [n_vertices][3] rest */
+  const float* normal;            /* [n_vertices][3] rest, or NULL: face normals from the skinned edges */
+  const uint32_t* indices;        /* [tri_count][3] */
+  const uint16_t* bone;           /* [n_vertices][4] */
+  const float* weight;            /* [n_vertices][4] */
+} rt_skin_desc;
+typedef struct rt_skin rt_skin;
+
+int rt_skin_create(const rt_skin_desc* desc, int device, rt_skin** out);
+void rt_skin_destroy(rt_skin* skin);
+/* the kernels alone: bones_dev [n_bones] on the skin's device; enqueued on `hip_stream` */
+int rt_skin_geometry_device(rt_skin* skin, const rt_transform* bones_dev, void* hip_stream);
+/* kernels + rt_scene_update_device on `hip_stream`; blocks as that call does; `info` may be NULL */
+int rt_skin_apply_device(rt_scene* scene, rt_skin* skin, const rt_transform* bones_dev, void* hip_stream, rt_update_info* info);
+/* host bones [n_bones]; blocks */
+int rt_skin_apply(rt_scene* scene, rt_skin* skin, const rt_transform* bones_host, rt_update_info* info);
+/* waits for the skin's device work; the arrays as the last kernels left them (before any kernel: the rest mesh): skinned
+ * vertices [n_vertices][3], triangle arrays [tri_count][3]; every output nullable; `normal` is not written for a mesh
+ * without vertex normals */
+int rt_skin_read(rt_skin* skin, float* position, float* normal, float* tri_v1, float* tri_e1, float* tri_e2, float* tri_normal);
+/* The host model (no device needed): the same layout as rt_skin_read; every output nullable.  Bones are not checked. */
+int rt_skin_model(const rt_skin_desc* desc, const rt_transform* bones, float* position, float* normal, float* tri_v1, float* tri_e1,
+                  float* tri_e2, float* tri_normal);
+
 /* ---- SAH report: how good is the tree an update left behind? -----------------------------------------------------------------
  *
  * No reference counterpart.  A refit keeps the topology of creation, so a tree that is deformed without bound decays; this
@@ -880,7 +956,8 @@ int rt_pose_model(const rt_pose_desc* desc, const rt_transform* transforms, floa
  *
  * The call BLOCKS and runs on a stream of its own (csrc/rt_sah.hip: one thread per node, one atomic add per sum and
  * workgroup).  It only reads the node array, as a query does: it may run while frames render.  It must not overlap an
- * rt_scene_update* / rt_pose_apply* of the same scene; both block, so this is a rule about the caller's threads only.
+ * rt_scene_update* / rt_pose_apply* / rt_skin_apply* of the same scene; all block, so this is a rule about the caller's
+ * threads only.
  * Out of scope: an automatic rebuild -- the threshold at which rebuilding (rt_scene_rebuild) pays has not been measured. */
 typedef struct rt_bvh_quality {
   double sah_created, sah_now;
@@ -892,7 +969,7 @@ int rt_scene_bvh_quality(rt_scene* scene, rt_bvh_quality* out);
 
 /* ---- BVH rebuild: a new tree for an existing handle, on the device, from the geometry the handle holds right now --------------
  *
- * No reference counterpart.  A refit (rt_scene_update*, rt_pose_apply*) keeps the topology of creation, so a scene that keeps
+ * No reference counterpart.  A refit (rt_scene_update*, rt_pose_apply*, rt_skin_apply*) keeps the topology of creation, so a scene that keeps
  * deforming gets slower; rt_scene_bvh_quality says by how much.  A rebuild replaces the tree without a host round trip: its
  * input is the leaf-slot intersection records of the scene as it stands, nothing comes from the caller.
  *
@@ -910,8 +987,8 @@ int rt_scene_bvh_quality(rt_scene* scene, rt_bvh_quality* out);
  * distances are the same bits; colours agree within the rounding of sums taken in another leaf order.  rt_scene_bvh_info
  * and rt_scene_memory_info describe the new tree; rt_scene_bvh_quality.sah_created stays the value of creation, sah_now is
  * the rebuilt tree's.  Receiver tables, tile costs and queue estimates are invalidated as a geometry update invalidates
- * them (the cell lists hold leaf slots).  rt_pose, rt_ray_order and rt_view handles stay valid: they speak in canonical
- * indices.  Later rt_scene_update* / rt_pose_apply* calls refit the new tree.
+ * them (the cell lists hold leaf slots).  rt_pose, rt_skin, rt_ray_order and rt_view handles stay valid: they speak in
+ * canonical indices.  Later rt_scene_update* / rt_pose_apply* / rt_skin_apply* calls refit the new tree.
  *
  * Both forms BLOCK: at entry they wait for every frame of this scene still in flight, at exit they synchronise their stream.
  * Ray queries the caller still has in flight on streams of its own are NOT waited for: finish them first.  While the call
