@@ -154,8 +154,8 @@ RT_HD static inline uint32_t rt_key_of(const RtKeyFrame& f, const float* o, cons
 // ---- the device-free half (rt_ray_order.cpp) --------------------------------------------------------------------------------
 // RT_OK, or RT_ERR_INVALID_ARG with a message: `perm` is not a permutation of [0, n) (rt_ray_order_set)
 int rt_check_permutation(const uint32_t* perm, uint32_t n);
-// The host model of rt_ray_order_build: keys[i] = the key of ray i, perm = the rays sorted by key, STABLY (the device leaves
-// rays of equal key in any order).  Every output nullable.
+// The host model of rt_ray_order_build: keys[i] = the key of ray i, perm = the rays sorted by key, STABLY (as the device's
+// sort: each of its passes is stable, so rays of equal key stay in index order there too).  Every output nullable.
 int rt_ray_order_model(const float* origin, const float* direction, uint32_t n, uint32_t origin_bits, uint32_t* keys, uint32_t* perm,
                        rt_ray_order_info* info);
 

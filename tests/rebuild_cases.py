@@ -28,6 +28,16 @@ def copies(n=9):
                    mats=[MAT_DIFFUSE], lights=[LIGHT]).contiguous()
 
 
+def clusters(n=9000, distinct=37, seed=5):
+    """n triangles drawn from `distinct` different ones in a seeded interleaved order: runs of about n / distinct equal keys that
+    lie across every boundary of the sort (wavefront, round of 256, tile of 4096), with distinct keys between them"""
+    base = soup(distinct)
+    pick = np.random.default_rng(seed).integers(0, distinct, n)
+    pick[:distinct] = np.arange(distinct)  # (every one of them appears)
+    return flat_of(v1=base.tri_v1[pick], e1=base.tri_e1[pick], e2=base.tri_e2[pick], nrm=base.tri_normal[pick], tm=[0] * n,
+                   mats=[MAT_DIFFUSE], lights=[LIGHT]).contiguous()
+
+
 def nan_vertex(n=20, victim=7):
     """one triangle whose first vertex has a NaN x among n: its centre is not finite on that axis"""
     f = soup(n)
@@ -70,6 +80,8 @@ def shuffled(flat, seed=9):
 CASES = {name: fn for name, fn in SCENES.items() if name != "empty"}
 CASES.update({"max_leaf": lambda: soup(MAX_LEAF), "max_leaf_plus_1": lambda: soup(MAX_LEAF + 1), "copies": copies, "nan_vertex": nan_vertex,
               "strip": strip, "heightfield": heightfield})
+# ties at scale: equal keys across a wavefront, a round and a tile of the sort, where only the canonical index orders them
+CASES.update({"copies_65": lambda: copies(65), "copies_257": lambda: copies(257), "copies_4097": lambda: copies(4097), "clusters": clusters})
 
 
 @functools.lru_cache(maxsize=None)

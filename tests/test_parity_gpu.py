@@ -1394,6 +1394,30 @@ def test_frame_as_two_chains_equals_frame_as_one_chain():
     assert hip.hipFree(fp) == 0
 
 
+_sort_bits_frame = []  # the default render of the test below, once
+
+
+@pytest.mark.parametrize("sort_bits", [12, 24])
+def test_sort_bits_at_their_edges_render_the_same_frame(sort_bits):
+    """rt_tuning.sort_bits at both ends of its range: one tile of buckets for the counting sort of a level's hit points
+    (every ray of a bucket ordered by its rank alone) and 4096 tiles (16 per thread of rt_sort_bases_kernel).  The order in
+    which a level is shaded changes; packed pixels, float planes and ray counters are those of the default render, bit for bit."""
+    seed = 7
+    cfg = RenderConfig.from_features(["realistic", "soft_shadows"], width_override=160, height_override=128, n_cloud_sets=16,
+                                     depth_override=3, cloud_seed=seed)
+    flat = random_scene(seed, n_spheres=13, n_tris=1000, n_lights=3, cfg=cfg)
+    win = (40, 30, 72, 56)
+    if not _sort_bits_frame:
+        _sort_bits_frame.append(gpu_render(cfg, flat, win))
+    ref, pref, sref = _sort_bits_frame[0]
+    assert sref["rays_reflection"] > 0 and sref["rays_refraction"] > 0, "the frame needs secondary levels to sort"
+    a, p, s = gpu_render(cfg, flat, win, sort_bits=sort_bits)
+    assert np.array_equal(a, ref), f"{int((a != ref).sum())} packed pixels differ"
+    assert np.array_equal(p["rgb"].view(np.uint32), pref["rgb"].view(np.uint32)) and np.array_equal(p["hit_id"], pref["hit_id"])
+    for k in ("rays_primary", "rays_reflection", "rays_refraction", "rays_shadow", "pixels_written"):
+        assert s[k] == sref[k], (k, s[k], sref[k])
+
+
 def test_two_frames_with_secondary_rays_in_flight():
     """Two frames with reflections / refractions in flight on two streams: each owns a workspace set (ray queues, sort
     workspace, hard-pair queue, level counters, accumulator), so the levels of one fill the compute units the drains of the

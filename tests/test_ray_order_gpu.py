@@ -1,7 +1,8 @@
 """Ray orders on the GPU (rt_ray_order*, rt_trace_rays_ordered*).  An order changes which 64 rays share a wavefront and
 nothing else, so every ordered call is held to the bits of the unordered call -- planes, argb, counters -- for every kind
 of order; and not only to itself: ordered batches go through the oracle-based reference of the radiance tests as well.
-The order a build produces is held to the host model (tests/ray_order_cases.py) bit for bit in its keys.
+The order a build produces is held to the host model (tests/ray_order_cases.py) bit for bit: its keys and, both sorts being
+stable, its permutation.
 
 Every test is one bounded piece of work in this process; the one test that needs torch runs in a child with a time limit
 of its own, nothing is retried, and no child is started after one has ended abnormally."""
@@ -170,7 +171,7 @@ def _against_model(probe, ds, o, d, origin_bits=0, what=""):
     order.close()
     mkeys, mperm, minfo = roc.model(probe, o, d, origin_bits=origin_bits)
     n_key = int((keys != mkeys).sum())
-    print(f"{what}: {n} rays, {info}; key diffs {n_key}; order equal to the stable model's: {bool(np.array_equal(perm, mperm))}")
+    print(f"{what}: {n} rays, {info}; key diffs {n_key}")
     assert n_key == 0, np.flatnonzero(keys != mkeys)[:10]
     for k, v in minfo.items():
         assert info[k] == v, (k, info[k], v)
@@ -179,6 +180,8 @@ def _against_model(probe, ds, o, d, origin_bits=0, what=""):
     sk = keys[perm]
     assert np.all(sk[1:] >= sk[:-1]), "keys[perm] decreases"
     assert np.array_equal(sk, mkeys[mperm])
+    # each pass of the device's sort is stable and the model is std::stable_sort: rays of equal key stay in index order on both sides
+    assert np.array_equal(perm, mperm), f"not the stable model's order, first at {np.flatnonzero(perm != mperm)[:5]}"
     return perm, mperm
 
 
@@ -200,8 +203,9 @@ def test_device_order_equals_the_host_model(probe):
     hp_p = roc.half_perimeter(perm, W)
     print(f"mean half-perimeter of the device's 64-ray runs: reference camera {hp:.2f}, pinhole {hp_p:.2f} (row-major 65.0)")
     assert hp <= 65.0 / 2 and hp_p <= 65.0 * 2 / 3
-    # identical rays: one key; the order is a permutation whatever it is
-    _against_model(probe, ds, np.tile(o[:1], (5000, 1)), np.tile(d[:1], (5000, 1)), what="identical rays")
+    # identical rays: one key; the stable order of equal keys is the identity, across wavefronts, rounds and a tile boundary
+    perm, _ = _against_model(probe, ds, np.tile(o[:1], (5000, 1)), np.tile(d[:1], (5000, 1)), what="identical rays")
+    assert np.array_equal(perm, np.arange(5000, dtype=np.uint32))
 
 
 def test_device_order_of_2_22_plus_17_random_rays(probe):

@@ -283,7 +283,10 @@ def test_cases_reach_the_paths_they_are_meant_for(probe):
             assert after.dev["n_nodes"] == nodes and after.dev["n_thr"] == 1
         else:
             assert after.dev["n_nodes"] >= 1 and after.dev["n_thr"] == 2 * after.dev["n_nodes"]
-    assert len(set(expected_keys(canonical_isect(*prepared(probe, "copies")[:2])))) == 1
+    for name in ("copies", "copies_65", "copies_257", "copies_4097"):
+        assert len(set(expected_keys(canonical_isect(*prepared(probe, name)[:2])))) == 1
+    runs = np.bincount(np.unique(expected_keys(canonical_isect(*prepared(probe, "clusters")[:2])), return_inverse=True)[1])
+    assert len(runs) == 37 and runs.min() > 64 and rc.flat_case("clusters").n_triangles == 9000 > 2 * 4096, "37 runs of equal keys, each longer than a wavefront"
     before, plan_before, flat = prepared(probe, "nan_vertex")
     keys = expected_keys(canonical_isect(before, plan_before))
     x_cell = sum(((keys >> (3 * b + 2)) & 1) << b for b in range(10))
