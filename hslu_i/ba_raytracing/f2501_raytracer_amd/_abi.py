@@ -232,6 +232,26 @@ class rt_rebuild_info(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+RT_REBUILD_LBVH, RT_REBUILD_PLOC = 0, 1
+RT_REBUILD_KEEP_BETTER = 0x1
+
+
+class rt_rebuild_desc(C.Structure):
+    _fields_ = [("method", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class rt_rebuild_report(C.Structure):
+    _fields_ = [("info", rt_rebuild_info), ("inner_q_before", C.c_uint64), ("leaf_q_before", C.c_uint64), ("inner_q_after", C.c_uint64),
+                ("leaf_q_after", C.c_uint64), ("sah_before", C.c_double), ("sah_after", C.c_double), ("swapped", C.c_uint32),
+                ("iterations", C.c_uint32)]
+
+    def as_dict(self):
+        """the fields of `info` and the report's own, flat"""
+        out = self.info.as_dict()
+        out.update({k: getattr(self, k) for k, _ in self._fields_ if k != "info"})
+        return out
+
+
 def transform_row(t):
     """Similarity3 -> the 8 floats of an rt_transform: translation, rotor s / xy / xz / yz, scale"""
     r = t.rotation

@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
-                   rt_bvh_quality, rt_pose_desc, rt_rebuild_info, rt_skin_desc, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_camera, rt_view_desc, rt_view_info)
+                   rt_bvh_quality, rt_pose_desc, rt_rebuild_desc, rt_rebuild_info, rt_rebuild_report, rt_skin_desc, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_camera, rt_view_desc, rt_view_info)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_HIP_LIB selects a diagnostic build of the same library (tools/, A/B timing); default: in-tree
@@ -24,7 +24,7 @@ EXPORTS = (
     "rt_view_read", "rt_view_rays_model", "rt_view_resolve_model",
     "rt_pose_create", "rt_pose_destroy", "rt_pose_geometry_device", "rt_pose_apply_device", "rt_pose_apply", "rt_pose_read", "rt_pose_model",
     "rt_skin_create", "rt_skin_destroy", "rt_skin_geometry_device", "rt_skin_apply_device", "rt_skin_apply", "rt_skin_read", "rt_skin_model",
-    "rt_scene_bvh_quality", "rt_scene_rebuild", "rt_scene_rebuild_device",
+    "rt_scene_bvh_quality", "rt_scene_rebuild", "rt_scene_rebuild_device", "rt_scene_rebuild_with", "rt_scene_rebuild_with_device",
 )
 
 _lib = None
@@ -176,6 +176,10 @@ def load():
     lib.rt_scene_rebuild.argtypes = [C.c_void_p, C.POINTER(rt_rebuild_info)]
     lib.rt_scene_rebuild_device.restype = C.c_int
     lib.rt_scene_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rt_rebuild_info)]
+    lib.rt_scene_rebuild_with.restype = C.c_int
+    lib.rt_scene_rebuild_with.argtypes = [C.c_void_p, C.POINTER(rt_rebuild_desc), C.POINTER(rt_rebuild_report)]
+    lib.rt_scene_rebuild_with_device.restype = C.c_int
+    lib.rt_scene_rebuild_with_device.argtypes = [C.c_void_p, C.POINTER(rt_rebuild_desc), C.c_void_p, C.POINTER(rt_rebuild_report)]
     _lib = lib
     return lib
 

@@ -274,6 +274,7 @@ struct RtRebuildIn {
   const uint32_t* recv_cell;  // device: RtRefitPlan::recv_cell
   const uint32_t* tri_slot;   // device: RtRefitPlan::tri_slot
   uint32_t max_leaf, n_materials;
+  uint32_t method, radius;    // RT_REBUILD_LBVH (0; radius unused) or RT_REBUILD_PLOC with the radius as applied (1 .. 32)
 };
 struct RtRebuildOut {
   DevBuf blob, plan_dev;
@@ -284,6 +285,7 @@ struct RtRebuildOut {
   float bounds[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
   uint32_t receivers_disabled = 0;
   float device_ms = 0.f;
+  uint32_t iterations = 0;    // of the PLOC loop (0: the LBVH, or a single root)
 };
 int rt_rebuild_device(const RtRebuildIn& in, hipStream_t stream, RtRebuildOut* out);
 

@@ -147,9 +147,8 @@ RT_HD static inline bool rt_lbvh_climb(const RtLbvhNode* kn, const uint32_t* ran
 
 // the topology of kept node nd, number r, first threaded entry `start`: the node (NaN boxes until the refit), its two
 // threaded entries (skip, leaf) and the children they mirror
-RT_HD static inline void rt_lbvh_emit(const uint32_t* rank, uint32_t max_leaf, const RtLbvhNode& nd, uint32_t r, uint32_t start, RtNode* nodes,
-                                      RtThrNode* thr, uint32_t* thr_src) {
-  const RtLbvhChild c0 = rt_lbvh_child(rank, max_leaf, nd, 0), c1 = rt_lbvh_child(rank, max_leaf, nd, 1);
+RT_HD static inline void rt_lbvh_emit_pair(const RtLbvhChild& c0, const RtLbvhChild& c1, uint32_t r, uint32_t start, RtNode* nodes, RtThrNode* thr,
+                                           uint32_t* thr_src) {
   RtNode o;
   for (int a = 0; a < 3; a++) o.lo0[a] = o.hi0[a] = o.lo1[a] = o.hi1[a] = NAN;
   o.c0 = c0.c, o.n0 = c0.n, o.c1 = c1.c, o.n1 = c1.n;
@@ -161,6 +160,10 @@ RT_HD static inline void rt_lbvh_emit(const uint32_t* rank, uint32_t max_leaf, c
   thr[start] = t, thr_src[start] = 2u * r;
   t.skip = second + 1u + 2u * c1.kept, t.leaf = c1.n ? ((c1.n << 24) | c1.c) : 0u;
   thr[second] = t, thr_src[second] = 2u * r + 1u;
+}
+RT_HD static inline void rt_lbvh_emit(const uint32_t* rank, uint32_t max_leaf, const RtLbvhNode& nd, uint32_t r, uint32_t start, RtNode* nodes,
+                                      RtThrNode* thr, uint32_t* thr_src) {
+  rt_lbvh_emit_pair(rt_lbvh_child(rank, max_leaf, nd, 0), rt_lbvh_child(rank, max_leaf, nd, 1), r, start, nodes, thr, thr_src);
 }
 
 // 1 <= n <= max_leaf: one root, child 0 the leaf (0, n), child 1 absent
@@ -214,6 +217,8 @@ struct RtRebuildWs {
 int rt_launch_sort_keys(const RtOrderWs& w, uint32_t n, void* stream);
 // (rt_order.hip) exclusive prefix over `total` counts (a multiple of 8, at most RT_ORDER_SCAN_BLOCKS * 2048), in place
 int rt_launch_exclusive_scan(uint32_t* counts, uint32_t total, uint32_t* sums, void* stream);
+// The first half of phase 1: frame, keys and the sort (w.sort.key_b / w.sort.idx_b).  rt_launch_rebuild_topology runs it itself.
+int rt_launch_rebuild_order(const RtDevScene& sc, const char* base, const uint32_t* tri_slot, const RtRebuildWs& w, void* stream);
 // Phase 1: keys, order, hierarchy, and w.result up to the histogram.  sc / base / tri_slot: the scene as it stands.
 int rt_launch_rebuild_topology(const RtDevScene& sc, const char* base, const uint32_t* tri_slot, const RtRebuildWs& w, uint32_t max_leaf, void* stream);
 // Phase 2: the slot records, ids, nodes, threaded entries and plan parts of the new blob (zeroed, its canonical sections

@@ -1,13 +1,15 @@
-// rt_rebuild.cpp -- rt_scene_rebuild / rt_scene_rebuild_device: the stateful half of a device-side BVH rebuild.  What a
-// rebuild computes is in rt_lbvh.h and rt_refit.h (host model: rt_rebuild_packed, kernels: rt_rebuild.hip, rt_order.hip,
-// rt_update.hip); here: the scratch, the one read-back between the two phases, the new blob and plan, and the swap.
+// rt_rebuild.cpp -- rt_scene_rebuild[_with][_device]: the stateful half of a device-side BVH rebuild.  What a rebuild
+// computes is in rt_lbvh.h, rt_ploc.h and rt_refit.h (host models: rt_rebuild_packed, rt_rebuild_ploc_packed; kernels:
+// rt_rebuild.hip, rt_ploc.hip, rt_order.hip, rt_update.hip); here: the scratch, the read-back between the two phases, the
+// new blob and plan, the SAH comparison of RT_REBUILD_KEEP_BETTER, and the swap.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cstring>
 
 #include "rt_host.h"
-#include "rt_lbvh.h"
+#include "rt_ploc.h"
+#include "rt_sah.h"
 
 int rt_rebuild_device(const RtRebuildIn& in, hipStream_t stream, RtRebuildOut* out) {
   const uint32_t n = in.dev.n_triangles, max_leaf = in.max_leaf;
@@ -19,22 +21,40 @@ int rt_rebuild_device(const RtRebuildIn& in, hipStream_t stream, RtRebuildOut* o
   const uint32_t n_tiles = (n + RT_ORDER_TILE - 1u) / RT_ORDER_TILE, total = (n + 7u) / 8u * 8u;
   const size_t per = rt_pad256((size_t)n * 4), hist = rt_pad256((size_t)256u * n_tiles * 4), sums = rt_pad256(RT_ORDER_SCAN_BLOCKS * 4);
   const size_t kn = rt_pad256((size_t)n * sizeof(RtLbvhNode)), rank = rt_pad256((size_t)total * 4), res = rt_pad256(RT_LBVH_RES_WORDS * 4);
-  int rc = b.ws.ensure(7 * per + hist + 2 * sums + 256 + kn + rank + res);
+  const bool ploc = in.method == RT_REBUILD_PLOC && n > max_leaf;  // (n <= max_leaf: the single root of either method)
+  const size_t ids = 2 * (size_t)n - 1u, nodes = rt_pad256(ids * sizeof(RtPlocNode)), places = rt_pad256(ids * sizeof(RtPlocPlace));
+  int rc = b.ws.ensure(5 * per + hist + sums + 256 + res + (ploc ? nodes + places + 3 * per + rank + sums + 256 : 2 * per + sums + kn + rank));
   if (rc != RT_OK) return rc;
   RtRebuildWs w{};
+  RtPlocWs pw{};
   char* p = (char*)b.ws.p;
   auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
   w.sort.keys = (uint32_t*)take(per), w.sort.key_a = (uint32_t*)take(per), w.sort.key_b = (uint32_t*)take(per);
   w.sort.idx_a = (uint32_t*)take(per), w.sort.idx_b = (uint32_t*)take(per);
-  w.depth = (uint32_t*)take(per), w.start = (uint32_t*)take(per);
-  w.sort.hist = (uint32_t*)take(hist), w.sort.sums = (uint32_t*)take(sums), w.scan_sums = (uint32_t*)take(sums);
-  w.frame = (float*)take(256), w.kn = (RtLbvhNode*)take(kn), w.rank = (uint32_t*)take(rank), w.result = (uint32_t*)take(res);
+  w.sort.hist = (uint32_t*)take(hist), w.sort.sums = (uint32_t*)take(sums);
+  w.frame = (float*)take(256), w.result = (uint32_t*)take(res);
+  if (ploc) {
+    pw.node = (RtPlocNode*)take(nodes), pw.place = (RtPlocPlace*)take(places);
+    pw.cid[0] = (uint32_t*)take(per), pw.cid[1] = (uint32_t*)take(per), pw.nn = (uint32_t*)take(per);
+    pw.flags = (uint32_t*)take(rank), pw.scan_sums = (uint32_t*)take(sums), pw.state = (RtPlocState*)take(256);
+  } else {
+    w.depth = (uint32_t*)take(per), w.start = (uint32_t*)take(per), w.scan_sums = (uint32_t*)take(sums);
+    w.kn = (RtLbvhNode*)take(kn), w.rank = (uint32_t*)take(rank);
+  }
   EventPair ev;
   HIP_TRY(hipEventCreate(&ev.e0));
   HIP_TRY(hipEventCreate(&ev.e1));
   HIP_TRY(hipEventRecord(ev.e0, stream));
   // ---- phase 1: the topology, and the few words the new blob is laid out with
-  hipError_t e = (hipError_t)rt_launch_rebuild_topology(in.dev, in.dev.base, in.tri_slot, w, max_leaf, stream);
+  hipError_t e;
+  if (ploc) {
+    e = (hipError_t)rt_launch_rebuild_order(in.dev, in.dev.base, in.tri_slot, w, stream);
+    if (e == hipSuccess) e = (hipError_t)rt_launch_ploc_topology(in.dev, in.dev.base, in.tri_slot, w, pw, max_leaf, in.radius, stream, &out->iterations);
+    if (e == hipSuccess && out->iterations > RT_PLOC_MAX_ITERATIONS)
+      return fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: PLOC did not finish within %u iterations", RT_PLOC_MAX_ITERATIONS);
+  } else {
+    e = (hipError_t)rt_launch_rebuild_topology(in.dev, in.dev.base, in.tri_slot, w, max_leaf, stream);
+  }
   if (e != hipSuccess) return fail(RT_ERR_HIP, "rebuild launch failed: %s", hipGetErrorString(e));
   uint32_t result[RT_LBVH_RES_WORDS];
   HIP_TRY(hipMemcpyAsync(result, w.result, sizeof(result), hipMemcpyDeviceToHost, stream));
@@ -72,7 +92,10 @@ int rt_rebuild_device(const RtRebuildIn& in, hipStream_t stream, RtRebuildOut* o
   uint32_t* group_nodes = (uint32_t*)(plan + out->plan_off[0]);
   uint32_t* thr_src = (uint32_t*)(plan + out->plan_off[1]);
   uint32_t* tri_slot = (uint32_t*)(plan + out->plan_off[3]);
-  e = (hipError_t)rt_launch_rebuild_fill(in.dev, in.dev.base, in.tri_slot, sc, base, group_nodes, thr_src, tri_slot, w, max_leaf, stream);
+  if (ploc)
+    e = (hipError_t)rt_launch_ploc_fill(in.dev, in.dev.base, in.tri_slot, sc, base, group_nodes, thr_src, tri_slot, w, pw, max_leaf, stream);
+  else
+    e = (hipError_t)rt_launch_rebuild_fill(in.dev, in.dev.base, in.tri_slot, sc, base, group_nodes, thr_src, tri_slot, w, max_leaf, stream);
   if (e != hipSuccess) return fail(RT_ERR_HIP, "rebuild launch failed: %s", hipGetErrorString(e));
   // ---- the boxes: the refit of this topology
   RtUpdateArgs u{};
@@ -103,7 +126,24 @@ int rt_rebuild_device(const RtRebuildIn& in, hipStream_t stream, RtRebuildOut* o
 
 namespace {
 
-int rebuild_impl(rt_scene* s, hipStream_t stream, bool own_stream, rt_rebuild_info* info) {
+// what rt_scene_rebuild_with* refuse of a descriptor, before the scene is looked at and before any HIP call; *radius: as applied
+int check_desc(const rt_rebuild_desc* d, uint32_t* radius) {
+  if (!d) return fail(RT_ERR_INVALID_ARG, "rt_scene_rebuild_with: null rt_rebuild_desc");
+  if (d->method != RT_REBUILD_LBVH && d->method != RT_REBUILD_PLOC) return fail(RT_ERR_INVALID_ARG, "rt_rebuild_desc.method = %u: unknown method", d->method);
+  if (d->method == RT_REBUILD_LBVH && d->radius) return fail(RT_ERR_INVALID_ARG, "rt_rebuild_desc.radius = %u: the LBVH takes no radius", d->radius);
+  *radius = 0u;
+  if (d->method == RT_REBUILD_PLOC) {
+    const int rc = rt_check_ploc_radius(d->radius, radius);
+    if (rc != RT_OK) return rc;
+  }
+  if (d->flags & ~RT_REBUILD_KEEP_BETTER) return fail(RT_ERR_INVALID_ARG, "rt_rebuild_desc.flags = 0x%x: unknown bits", d->flags);
+  if (d->reserved) return fail(RT_ERR_INVALID_ARG, "rt_rebuild_desc.reserved must be 0");
+  return RT_OK;
+}
+
+// desc == nullptr: rt_scene_rebuild[_device], the LBVH and no SAH report
+int rebuild_impl(rt_scene* s, const rt_rebuild_desc* desc, uint32_t radius, hipStream_t stream, bool own_stream, rt_rebuild_info* info,
+                 rt_rebuild_report* report) {
   const auto t0 = std::chrono::steady_clock::now();
   if (!s) return fail(RT_ERR_INVALID_ARG, "rt_scene_rebuild: null scene");
   if (s->progress_active) return fail(RT_ERR_INVALID_ARG, "a progressive render owns this scene until rt_render_end");
@@ -127,38 +167,81 @@ int rebuild_impl(rt_scene* s, hipStream_t stream, bool own_stream, rt_rebuild_in
   in.recv_cell = (const uint32_t*)((const char*)s->plan_dev.p + s->plan_off[2]);
   in.tri_slot = (const uint32_t*)((const char*)s->plan_dev.p + s->plan_off[3]);
   in.max_leaf = s->max_leaf, in.n_materials = (uint32_t)s->plan.mat_class.size();
+  in.method = desc ? desc->method : RT_REBUILD_LBVH, in.radius = radius;
   RtRebuildOut o;
   rc = rt_rebuild_device(in, stream, &o);
   if (rc != RT_OK) return rc;  // (the handle is as it was)
-  // ---- the swap: nothing below can fail
-  s->blob.release(), s->plan_dev.release();
-  s->blob = o.blob, s->plan_dev = o.plan_dev;
-  memcpy(s->plan_off, o.plan_off, sizeof(s->plan_off));
-  s->dev = o.dev;
-  s->plan.height_nodes.swap(o.height_nodes), s->plan.thr_src.swap(o.thr_src), s->plan.tri_slot.swap(o.tri_slot);
-  s->plan.height_offset = o.shape.group_offset;
-  s->plan.receivers_disabled = o.receivers_disabled;
-  rt_rebuild_info_of(o.shape, s->dev.n_triangles, &s->info, &s->bytes_bvh);
-  memcpy(s->aabb_lo, o.bounds, 12), memcpy(s->aabb_hi, o.bounds + 3, 12);
-  // what the scene has cached about its old tree: as a geometry update (the cell lists hold leaf slots)
-  s->stream_verified = false, s->est_valid = false, s->key_gen++;
-  s->flags_key[0] = -1.f, s->cell_lists_built = false, s->cost_valid = false;
+  struct Candidate {  // freed on every return path before the swap
+    RtRebuildOut* o;
+    ~Candidate() {
+      if (o) o->blob.release(), o->plan_dev.release();
+    }
+  } cand{&o};
+  bool swap = true;
+  if (desc) {  // ---- the SAH sums of the tree in place and of the candidate, from the kernel of rt_scene_bvh_quality
+    unsigned long long* dev = (unsigned long long*)s->sah_dev.p;  // (256 bytes: two reports of three words)
+    hipError_t e = (hipError_t)rt_launch_sah((const RtNode*)((const char*)s->blob.p + s->dev.off_nodes), s->dev.n_nodes, dev, stream);
+    if (e == hipSuccess) e = (hipError_t)rt_launch_sah((const RtNode*)((const char*)o.blob.p + o.dev.off_nodes), o.dev.n_nodes, dev + 4, stream);
+    if (e != hipSuccess) return fail(RT_ERR_HIP, "SAH report launch failed: %s", hipGetErrorString(e));
+    unsigned long long host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const double cost = (double)s->sah_tri_cost;
+    const double before = ((double)host[0] + cost * (double)host[1]) / RT_SAH_ONE, after = ((double)host[4] + cost * (double)host[5]) / RT_SAH_ONE;
+    swap = !(desc->flags & RT_REBUILD_KEEP_BETTER) || after < before;
+    if (report) {
+      report->inner_q_before = host[0], report->leaf_q_before = host[1], report->inner_q_after = host[4], report->leaf_q_after = host[5];
+      report->sah_before = before, report->sah_after = after;
+      report->swapped = swap ? 1u : 0u, report->iterations = o.iterations;
+    }
+  }
+  if (swap) {  // ---- nothing below can fail
+    cand.o = nullptr;
+    s->blob.release(), s->plan_dev.release();
+    s->blob = o.blob, s->plan_dev = o.plan_dev;
+    memcpy(s->plan_off, o.plan_off, sizeof(s->plan_off));
+    s->dev = o.dev;
+    s->plan.height_nodes.swap(o.height_nodes), s->plan.thr_src.swap(o.thr_src), s->plan.tri_slot.swap(o.tri_slot);
+    s->plan.height_offset = o.shape.group_offset;
+    s->plan.receivers_disabled = o.receivers_disabled;
+    rt_rebuild_info_of(o.shape, s->dev.n_triangles, &s->info, &s->bytes_bvh);
+    memcpy(s->aabb_lo, o.bounds, 12), memcpy(s->aabb_hi, o.bounds + 3, 12);
+    // what the scene has cached about its old tree: as a geometry update (the cell lists hold leaf slots)
+    s->stream_verified = false, s->est_valid = false, s->key_gen++;
+    s->flags_key[0] = -1.f, s->cell_lists_built = false, s->cost_valid = false;
+  }
   if (info) {
     info->device_ms = o.device_ms;
     info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     info->n_nodes = s->info.n_nodes, info->n_leaves = s->info.n_leaves, info->max_depth = s->info.max_depth, info->max_leaf_size = s->info.max_leaf_size;
-    info->tables_invalidated = RT_UPDATE_INVALIDATES_RECEIVER_TABLES | RT_UPDATE_INVALIDATES_TILE_COSTS | RT_UPDATE_INVALIDATES_QUEUE_SIZES;
+    info->tables_invalidated = swap ? RT_UPDATE_INVALIDATES_RECEIVER_TABLES | RT_UPDATE_INVALIDATES_TILE_COSTS | RT_UPDATE_INVALIDATES_QUEUE_SIZES : 0u;
     info->reserved = 0;
   }
   return RT_OK;
+}
+
+int rebuild_with(rt_scene* s, const rt_rebuild_desc* d, hipStream_t stream, bool own_stream, rt_rebuild_report* report) {
+  uint32_t radius = 0u;
+  const int rc = check_desc(d, &radius);
+  if (rc != RT_OK) return rc;
+  if (report) *report = rt_rebuild_report{};
+  return rebuild_impl(s, d, radius, stream, own_stream, report ? &report->info : nullptr, report);
 }
 
 }  // namespace
 
 extern "C" {
 
-int rt_scene_rebuild(rt_scene* s, rt_rebuild_info* info) { return rebuild_impl(s, nullptr, true, info); }
+int rt_scene_rebuild(rt_scene* s, rt_rebuild_info* info) { return rebuild_impl(s, nullptr, 0u, nullptr, true, info, nullptr); }
 
-int rt_scene_rebuild_device(rt_scene* s, void* hip_stream, rt_rebuild_info* info) { return rebuild_impl(s, (hipStream_t)hip_stream, false, info); }
+int rt_scene_rebuild_device(rt_scene* s, void* hip_stream, rt_rebuild_info* info) {
+  return rebuild_impl(s, nullptr, 0u, (hipStream_t)hip_stream, false, info, nullptr);
+}
+
+int rt_scene_rebuild_with(rt_scene* s, const rt_rebuild_desc* d, rt_rebuild_report* report) { return rebuild_with(s, d, nullptr, true, report); }
+
+int rt_scene_rebuild_with_device(rt_scene* s, const rt_rebuild_desc* d, void* hip_stream, rt_rebuild_report* report) {
+  return rebuild_with(s, d, (hipStream_t)hip_stream, false, report);
+}
 
 }  // extern "C"

@@ -121,12 +121,18 @@ static inline uint32_t wgs(uint32_t n) { return (n + RT_RB_WG - 1u) / RT_RB_WG; 
     if (e_ != hipSuccess) return (int)e_;                                       \
   } while (0)
 
+int rt_launch_rebuild_order(const RtDevScene& sc, const char* base, const uint32_t* tri_slot, const RtRebuildWs& w, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const uint32_t n = sc.n_triangles;
+  RT_RB_LAUNCH(rt_lbvh_frame_kernel, 1u, RT_RB_FRAME_WG, sc, base, tri_slot, w.frame);
+  RT_RB_LAUNCH(rt_lbvh_keys_kernel, wgs(n), RT_RB_WG, sc, base, tri_slot, (const float*)w.frame, w.sort.keys);
+  return rt_launch_sort_keys(w.sort, n, stream_);
+}
+
 int rt_launch_rebuild_topology(const RtDevScene& sc, const char* base, const uint32_t* tri_slot, const RtRebuildWs& w, uint32_t max_leaf, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const uint32_t n = sc.n_triangles, total = (n + 7u) / 8u * 8u;
-  RT_RB_LAUNCH(rt_lbvh_frame_kernel, 1u, RT_RB_FRAME_WG, sc, base, tri_slot, w.frame);
-  RT_RB_LAUNCH(rt_lbvh_keys_kernel, wgs(n), RT_RB_WG, sc, base, tri_slot, (const float*)w.frame, w.sort.keys);
-  int e = rt_launch_sort_keys(w.sort, n, stream_);
+  int e = rt_launch_rebuild_order(sc, base, tri_slot, w, stream_);
   if (e != (int)hipSuccess) return e;
   // (the grid covers the flags and the result words, whichever are more)
   RT_RB_LAUNCH(rt_lbvh_karras_kernel, wgs(total > RT_LBVH_RES_WORDS ? total : RT_LBVH_RES_WORDS), RT_RB_WG, (const uint32_t*)w.sort.key_b,

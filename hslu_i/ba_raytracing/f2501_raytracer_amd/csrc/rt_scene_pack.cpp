@@ -12,6 +12,7 @@
 
 #include "rt_lbvh.h"
 #include "rt_refit.h"
+#include "rt_ploc.h"
 #include "rt_sah.h"
 #include "rt_scene_pack.h"
 
@@ -534,7 +535,64 @@ int rt_rebuild_shape(uint32_t n_triangles, uint32_t max_leaf, const uint32_t* re
   return RT_OK;
 }
 
-int rt_rebuild_packed(RtPackedScene* pk, uint32_t max_leaf) {
+namespace {
+
+// the PLOC loop of rt_ploc.h over n > max_leaf sorted triangles: the nodes, and a place for every kept node and every leaf
+struct PlocTree {
+  std::vector<RtPlocNode> node;
+  std::vector<RtPlocPlace> place;
+  uint32_t iterations = 0;
+};
+int ploc_tree(const RtDevScene& old, const char* old_base, const uint32_t* old_tri_slot, const std::vector<uint32_t>& idx, uint32_t max_leaf,
+              uint32_t radius, std::vector<uint32_t>* result, PlocTree* out) {
+  const uint32_t n = (uint32_t)idx.size(), n_ids = 2u * n - 1u;
+  std::vector<RtPlocNode>& node = out->node;
+  node.assign(n_ids, RtPlocNode());
+  for (uint32_t x = n; x < n_ids; x++) node[x].parent = RT_LBVH_NONE;
+  std::vector<uint32_t> cid[2] = {std::vector<uint32_t>(n), std::vector<uint32_t>(n)}, nn(n), scan(n);
+  for (uint32_t s = 0; s < n; s++) rt_ploc_leaf(old, old_base, old_tri_slot[idx[s]], &node[s]), cid[0][s] = s;
+  RtPlocState state[2] = {{n, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+  std::vector<float> box;
+  uint32_t it = 0;
+  for (; state[it & 1u].m > 1u; it++) {
+    if (it >= RT_PLOC_MAX_ITERATIONS)
+      return rt_fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: PLOC did not finish within %u iterations (%u clusters left)", RT_PLOC_MAX_ITERATIONS,
+                     state[it & 1u].m);
+    const RtPlocState st = state[it & 1u];
+    const std::vector<uint32_t>& in = cid[it & 1u];
+    const uint32_t m = st.m;
+    box.resize(6 * (size_t)m);
+    for (uint32_t p = 0; p < m; p++)
+      for (int a = 0; a < 3; a++) box[(size_t)a * m + p] = node[in[p]].lo[a], box[(size_t)(3 + a) * m + p] = node[in[p]].hi[a];
+    for (uint32_t i = 0; i < m; i++) nn[i] = rt_ploc_nearest(box.data(), m, 0u, m, radius, i);
+    uint32_t run = 0;
+    for (uint32_t i = 0; i < m; i++) scan[i] = run, run += rt_ploc_survives(nn.data(), m, i) ? 1u : 0u;
+    for (uint32_t i = 0; i < m; i++)
+      rt_ploc_merge(node.data(), n, in.data(), nn.data(), scan.data(), st, max_leaf, i, cid[(it + 1u) & 1u].data(), &state[(it + 1u) & 1u]);
+  }
+  out->iterations = state[it & 1u].iterations;
+  // the climb, and the counts of phase 1
+  std::vector<uint32_t>& res = *result;
+  out->place.assign(n_ids, RtPlocPlace());
+  res[RT_LBVH_RES_NODES] = node[n_ids - 1u].kept;
+  for (uint32_t x = 0; x < n_ids; x++) {
+    const bool kept = rt_ploc_keeps(node[x], max_leaf);
+    if (!kept && x >= n) continue;
+    RtPlocPlace& p = out->place[x];
+    rt_ploc_climb(node.data(), x, kept ? RT_PLOC_CLIMB_KEPT : RT_PLOC_CLIMB_LEAF, &p);
+    if (!kept) continue;
+    res[RT_LBVH_RES_DEPTH] = std::max(res[RT_LBVH_RES_DEPTH], p.depth);
+    res[RT_LBVH_RES_HIST + (p.depth - 1u)]++;
+    for (int k = 0; k < 2; k++) {
+      const RtLbvhChild ch = rt_ploc_child(node.data(), max_leaf, x, p, k);
+      if (ch.n) res[RT_LBVH_RES_LEAVES]++, res[RT_LBVH_RES_LARGEST] = std::max(res[RT_LBVH_RES_LARGEST], ch.n);
+    }
+  }
+  return RT_OK;
+}
+
+// what rt_rebuild_packed and rt_rebuild_ploc_packed share: keys, layout, gather, refit, info.  radius 0: the LBVH.
+int rebuild_packed(RtPackedScene* pk, uint32_t max_leaf, uint32_t radius, uint32_t* iterations) {
   if (!pk) return rt_fail(RT_ERR_INVALID_ARG, "null argument");
   int rc = rt_check_rebuild(pk->dev);
   if (rc != RT_OK) return rc;
@@ -558,7 +616,12 @@ int rt_rebuild_packed(RtPackedScene* pk, uint32_t max_leaf) {
   // hierarchy
   std::vector<RtLbvhNode> kn(n);
   std::vector<uint32_t> rank(n, 0u), depth(n, 0u), start(n, 0u), result(RT_LBVH_RES_WORDS, 0u);
-  if (n > max_leaf) {
+  const bool ploc = radius != 0u && n > max_leaf;  // (n <= max_leaf: the single root of either method)
+  PlocTree tree;
+  if (ploc) {
+    rc = ploc_tree(old, old_base, old_tri_slot, idx, max_leaf, radius, &result, &tree);
+    if (rc != RT_OK) return rc;
+  } else if (n > max_leaf) {
     for (uint32_t i = 0; i + 1u < n; i++) {
       RtLbvhNode nd;
       rt_lbvh_karras(key.data(), idx.data(), n, i, &nd);
@@ -598,8 +661,19 @@ int rt_rebuild_packed(RtPackedScene* pk, uint32_t max_leaf) {
   o.plan = pk->plan;
   RtRefitPlan& pl = o.plan;
   pl.height_nodes.assign(sh.n_nodes, 0u), pl.height_offset = sh.group_offset, pl.thr_src.assign(sh.n_thr, 0u);
-  for (uint32_t s = 0; s < n; s++) rt_lbvh_gather(old, old_base, old_tri_slot, o.dev, base, pl.tri_slot.data(), s, idx[s]);
-  if (n <= max_leaf) {
+  for (uint32_t s = 0; s < n; s++) rt_lbvh_gather(old, old_base, old_tri_slot, o.dev, base, pl.tri_slot.data(), ploc ? tree.place[s].first : s, idx[s]);
+  if (ploc) {
+    std::vector<uint32_t> cursor(RT_LBVH_DEPTH_BINS + 1u, 0u), by_number(sh.n_nodes, 0u);
+    for (uint32_t g = 0; g + 1u < sh.group_offset.size(); g++) cursor[sh.max_depth - 2u - g] = sh.group_offset[g];  // (depth k + 1 at k)
+    for (uint32_t x = n; x < 2u * n - 1u; x++)
+      if (rt_ploc_keeps(tree.node[x], max_leaf)) by_number[tree.place[x].number] = x;
+    for (uint32_t x : by_number) {  // (ascending node number inside a group)
+      const RtPlocPlace& p = tree.place[x];
+      rt_lbvh_emit_pair(rt_ploc_child(tree.node.data(), max_leaf, x, p, 0), rt_ploc_child(tree.node.data(), max_leaf, x, p, 1), p.number, p.start,
+                        (RtNode*)(base + o.dev.off_nodes), (RtThrNode*)(base + o.dev.off_nodes_thr), pl.thr_src.data());
+      pl.height_nodes[cursor[p.depth - 1u]++] = p.number;
+    }
+  } else if (n <= max_leaf) {
     rt_lbvh_single_root(n, (RtNode*)(base + o.dev.off_nodes), (RtThrNode*)(base + o.dev.off_nodes_thr), pl.thr_src.data(), pl.height_nodes.data());
   } else {
     std::vector<uint32_t> cursor(RT_LBVH_DEPTH_BINS + 1u, 0u);
@@ -628,7 +702,24 @@ int rt_rebuild_packed(RtPackedScene* pk, uint32_t max_leaf) {
   o.info = pk->info;
   rt_rebuild_info_of(sh, n, &o.info, &o.bytes_bvh);
   *pk = std::move(o);
+  if (iterations) *iterations = tree.iterations;
   return RT_OK;
+}
+
+}  // namespace
+
+int rt_rebuild_packed(RtPackedScene* pk, uint32_t max_leaf) { return rebuild_packed(pk, max_leaf, 0u, nullptr); }
+
+int rt_check_ploc_radius(uint32_t radius, uint32_t* applied) {
+  if (radius > RT_PLOC_MAX_RADIUS) return rt_fail(RT_ERR_INVALID_ARG, "rt_rebuild_desc.radius = %u: at most %u", radius, RT_PLOC_MAX_RADIUS);
+  *applied = radius ? radius : RT_PLOC_DEFAULT_RADIUS;
+  return RT_OK;
+}
+
+int rt_rebuild_ploc_packed(RtPackedScene* pk, uint32_t max_leaf, uint32_t radius, uint32_t* iterations) {
+  int rc = rt_check_ploc_radius(radius, &radius);
+  if (rc != RT_OK) return rc;
+  return rebuild_packed(pk, max_leaf, radius, iterations);
 }
 
 void rt_rebuild_info_of(const RtRebuildShape& sh, uint32_t n_triangles, rt_bvh_info* info, size_t* bytes_bvh) {

@@ -87,6 +87,11 @@ void rt_rebuild_info_of(const RtRebuildShape& sh, uint32_t n_triangles, rt_bvh_i
 // same functions the kernels are made of: the specification of rt_scene_rebuild, checked on the CPU.  max_leaf as
 // rt_bvh_tuning.max_leaf (0 = default).  Any refusal leaves `pk` untouched.
 int rt_rebuild_packed(RtPackedScene* pk, uint32_t max_leaf);
+// The same with the tree of rt_ploc.h: the specification of rt_scene_rebuild_with(RT_REBUILD_PLOC).  radius as
+// rt_rebuild_desc.radius (0 = 8, at most 32: rt_check_ploc_radius); *iterations (may be null): the iterations of the loop,
+// 0 for the single root of n_triangles <= max_leaf.  Also refuses a loop of more than RT_PLOC_MAX_ITERATIONS iterations.
+int rt_check_ploc_radius(uint32_t radius, uint32_t* applied);
+int rt_rebuild_ploc_packed(RtPackedScene* pk, uint32_t max_leaf, uint32_t radius, uint32_t* iterations = nullptr);
 
 // ---- SAH report ------------------------------------------------------------------------------------------------------------
 // The two integer sums of rt_sah.h over the tree of a packed scene as it stands: sums[0] = inner_q, sums[1] = leaf_q, and

@@ -270,15 +270,29 @@ class DeviceScene:
         _lib.check(_lib.load().rt_scene_bvh_quality(self.handle, C.byref(q)))
         return q.as_dict()
 
-    def rebuild(self, info: bool = False):
+    def rebuild(self, info: bool = False, method: str = "lbvh", radius: Optional[int] = None, keep_better: bool = False):
         """`rt_scene_rebuild`: a new tree for this scene, built on the device from the geometry it holds right now -- the
         repair for a tree that `update` / `DevicePose.apply` / `DeviceSkin.apply` have refitted until it decayed (`bvh_quality`).  The tree is an
         LBVH with the leaf size of creation; renders and queries behave as on a DeviceScene created from the current
         description.  Blocks; runs on a stream of its own; waits for the scene's frames in flight.  The description this
-        scene holds (`flat`) is unchanged.  Returns None, or with info=True the rt_rebuild_info of the call as a dict."""
-        inf = _abi.rt_rebuild_info()
-        _lib.check(_lib.load().rt_scene_rebuild(self.handle, C.byref(inf)))
-        return inf.as_dict() if info else None
+        scene holds (`flat`) is unchanged.  Returns None, or with info=True the rt_rebuild_info of the call as a dict.
+
+        Any other argument goes through `rt_scene_rebuild_with`: method="ploc" clusters by surface area inside a window of
+        `radius` positions of the Morton order (None: 8; 1 .. 32) -- a tighter tree that takes longer to build; keep_better=True
+        builds the candidate, compares its SAH with the tree's in place and swaps only if it is lower.  With info=True these
+        calls return the rt_rebuild_report as a dict: the info fields (of the tree in place), the SAH sums before / after,
+        `swapped` and `iterations`."""
+        if method == "lbvh" and radius is None and not keep_better:
+            inf = _abi.rt_rebuild_info()
+            _lib.check(_lib.load().rt_scene_rebuild(self.handle, C.byref(inf)))
+            return inf.as_dict() if info else None
+        methods = {"lbvh": _abi.RT_REBUILD_LBVH, "ploc": _abi.RT_REBUILD_PLOC}
+        if method not in methods:
+            raise ValueError(f"rebuild: method {method!r} is not one of {sorted(methods)}")
+        desc = _abi.rt_rebuild_desc(methods[method], int(radius or 0), _abi.RT_REBUILD_KEEP_BETTER if keep_better else 0, 0)
+        rep = _abi.rt_rebuild_report()
+        _lib.check(_lib.load().rt_scene_rebuild_with(self.handle, C.byref(desc), C.byref(rep)))
+        return rep.as_dict() if info else None
 
     def update(self, flat, info: bool = False, tri_first: int = 0):
         """New values for the objects this scene already has, in place (`rt_scene_update`): the BVH is refitted on the

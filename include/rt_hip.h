@@ -1001,9 +1001,10 @@ int rt_scene_bvh_quality(rt_scene* scene, rt_bvh_quality* out);
  * RT_ERR_UNSUPPORTED: a split-clipped tree (n_references > n_triangles: a clipped reference has no record to rebuild
  * from), also before any HIP call; more than 2^23 - 8 triangles; a rebuilt tree deeper than the traversal stack (max_depth
  * + 2 > 64, the rule of rt_scene_create -- a guard only: a radix tree over 30 key bits and 23 index bits is at most 53 deep).
- * Multi-GPU: the caller rebuilds each per_gpu[i].  Out of scope: an automatic trigger (profiles/rebuild.md has the numbers of
- * tools/rebuild_bench.py on one scene: not enough to pick a threshold, and a rebuild can lose); asynchronous rebuilds;
- * rebuilding with another max_leaf than the one of creation. */
+ * Multi-GPU: the caller rebuilds each per_gpu[i].  A rebuild can lose (profiles/rebuild.md): use rt_scene_rebuild_with and
+ * RT_REBUILD_KEEP_BETTER, which compares before it swaps.  Out of scope: an automatic trigger (the numbers of
+ * tools/rebuild_bench.py on one scene are not enough to pick a threshold); asynchronous rebuilds; rebuilding with another
+ * max_leaf than the one of creation. */
 typedef struct rt_rebuild_info {
   double device_ms, total_ms;
   uint32_t n_nodes, n_leaves, max_depth, max_leaf_size; /* of the new tree, as rt_bvh_info */
@@ -1014,6 +1015,54 @@ typedef struct rt_rebuild_info {
 int rt_scene_rebuild(rt_scene* scene, rt_rebuild_info* info);
 /* the kernels run on `hip_stream` */
 int rt_scene_rebuild_device(rt_scene* scene, void* hip_stream, rt_rebuild_info* info);
+
+/* ---- BVH rebuild, the method chosen: an LBVH as above, or PLOC, which clusters by surface area ------------------------------
+ *
+ * rt_scene_rebuild_with* are rt_scene_rebuild* with a descriptor and a report.  RT_REBUILD_LBVH builds the tree rt_scene_rebuild
+ * builds, byte for byte.  RT_REBUILD_PLOC (csrc/rt_ploc.h; Meister & Bittner 2018, parallel locally-ordered clustering)
+ * starts from the same Morton order, but builds the hierarchy bottom-up: every cluster looks at the `radius` clusters on
+ * either side of it in that order for the one whose common box with it has the smallest surface area, pairs that chose each
+ * other merge, and the loop runs until one cluster is left -- tens of iterations of a few short launches, against the
+ * LBVH's single pass.  Ties are broken by (position xor position), which is symmetric: the closest pair of all is always
+ * mutual, and n identical triangles halve per iteration.  The collapse into leaves of at most max_leaf triangles, the boxes,
+ * the copies, the bounds and the receiver records are the LBVH's.  A host model compiled from the same sources specifies
+ * every byte (rt_rebuild_ploc_packed, csrc/rt_scene_pack.cpp).  The tree costs less SAH than the LBVH's on meshes and
+ * terrains and comes close to the tree of rt_scene_create (profiles/rebuild.md has the figures); it costs more time to
+ * build, and on a one-dimensional strip of triangles it is the looser of the two.
+ *
+ * A rebuild can LOSE: on a scene of a few wall-sized triangles either tree is worse than the refitted tree of creation.
+ * RT_REBUILD_KEEP_BETTER makes the call compare before it swaps: the candidate tree is built, the SAH sums of both trees
+ * are taken on the device (the kernel and the integers of rt_scene_bvh_quality; both trees bound the same padded triangle
+ * boxes, so the two costs share their root area), and a candidate whose SAH is not LOWER is freed: report.swapped = 0,
+ * report.info.tables_invalidated = 0, and the handle is exactly as it was, cached receiver tables and queue sizes included.
+ * The report is filled either way; `info` describes the tree in place when the call returns, the *_after sums the candidate.
+ * An automatic trigger -- when to call this at all -- stays out of scope.
+ *
+ * Scratch while the call runs, next to the second blob: 48 bytes per triangle for the LBVH, about 160 for PLOC (the sort's
+ * 20, a 48-byte node and a 16-byte place for each of the 2n - 1 clusters ever made, 16 for the loop's arrays).
+ *
+ * RT_ERR_INVALID_ARG, checked on the descriptor before the scene is looked at and before any HIP call (the message names
+ * the field): NULL desc, an unknown method, a radius above 32, a radius given for the LBVH, unknown flag bits, reserved != 0.
+ * Then everything rt_scene_rebuild refuses.  RT_ERR_UNSUPPORTED, the handle untouched: a PLOC loop of more than 256
+ * iterations (a guard: the scenes measured take 6 to 52) and a tree deeper than the traversal stack (max_depth + 2 > 64;
+ * PLOC has no depth guarantee, so with it this guard can fire).  `report` may be NULL. */
+#define RT_REBUILD_LBVH 0u
+#define RT_REBUILD_PLOC 1u
+#define RT_REBUILD_KEEP_BETTER 0x1u /* swap only if the candidate's SAH is lower than the tree's in place */
+typedef struct rt_rebuild_desc {
+  uint32_t method;   /* RT_REBUILD_LBVH / RT_REBUILD_PLOC */
+  uint32_t radius;   /* PLOC: 0 = 8, else 1..32; LBVH: must be 0 */
+  uint32_t flags;    /* RT_REBUILD_KEEP_BETTER */
+  uint32_t reserved; /* 0 */
+} rt_rebuild_desc;
+typedef struct rt_rebuild_report {
+  rt_rebuild_info info; /* of the tree in place when the call returns */
+  uint64_t inner_q_before, leaf_q_before, inner_q_after, leaf_q_after; /* rt_bvh_quality's sums; "after" = the candidate's */
+  double sah_before, sah_after;
+  uint32_t swapped, iterations; /* iterations: of the PLOC loop, 0 for the LBVH */
+} rt_rebuild_report;
+int rt_scene_rebuild_with(rt_scene* scene, const rt_rebuild_desc* desc, rt_rebuild_report* report);
+int rt_scene_rebuild_with_device(rt_scene* scene, const rt_rebuild_desc* desc, void* hip_stream, rt_rebuild_report* report);
 
 /* ---- multi-GPU: tile-partitioned frame + ONE gather of the packed pixels to rank 0 (RCCL over xGMI) ---------
  *
