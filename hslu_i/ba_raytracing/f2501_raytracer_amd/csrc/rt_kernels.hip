@@ -536,8 +536,69 @@ __device__ __forceinline__ V3 shadow_filter(const Shadow& S) {
   return mk(1.0f - (float)S.fr * RT_FILT_INV_SCALE, 1.0f - (float)S.fg * RT_FILT_INV_SCALE, 1.0f - (float)S.fb * RT_FILT_INV_SCALE);
 }
 
+// What a TRANSMISSIVE occluder contributes to a shadow ray, as far as it depends on the material row alone (wave-uniform):
+// the three filter decrements, and of io = opacity * (1 - fresnel_reflectance_air_red) everything that holds neither the
+// normal nor the ray.  Two kinds of material:
+//  * REFLECTIVE (metallic > 0): the reflectance is `tir ? ra : fres` with tir = true and ra = metallic in every lane, so
+//    io = opacity * (1 - metallic) and the decrement itself are wave-uniform: `x` holds the decrement.
+//  * otherwise ra = 1 and the lanes differ: `x` holds the opacity's bits, eta2_out / eta2_in the two values eta_t * eta_t can
+//    take, f0x the base reflectance.
+// Each value is what the unsplit expression computes at that place of its tree -- the same single-precision operation on
+// the same operands -- so the per-lane remainder (occluder_decrement) rounds exactly as the unsplit form does.
+// `x` needs no flag: a decrement is at most RT_SH_ONE = 2^28, and a transmissive material has |opacity| > RT_EPS (or NaN),
+// whose bits read as an integer lie far above 2^28 (2^28 is the float 2^-95).
+struct OccConst {
+  uint32_t ar, ag, ab;      // absorption per channel, 2^-24 units
+  uint32_t x;               // <= RT_SH_ONE: the opacity decrement 1 - io, 2^-28 units; else the bits of the opacity
+  float eta2_out, eta2_in;  // eta_t * eta_t for a ray that leaves (ior) / enters (1 / ior) the material
+  float f0x;                // base reflectance, red
+};
+__device__ __forceinline__ OccConst occluder_constants(const Mat& m) {
+  OccConst k;
+  const V3 ab = absorption(m);
+  k.ar = (uint32_t)__float2uint_rn(ab.x * RT_FILT_SCALE);
+  k.ag = (uint32_t)__float2uint_rn(ab.y * RT_FILT_SCALE);
+  k.ab = (uint32_t)__float2uint_rn(ab.z * RT_FILT_SCALE);
+  const float omt = 1.0f - m.metallic;
+  const float io = m.opacity * omt;  // (reflective: 1 - ra = 1 - metallic)
+  k.x = m.metallic > 0.0f ? (uint32_t)__float2uint_rn(clampf(1.0f - io, 0.0f, 1.0f) * RT_SH_SCALE) : __float_as_uint(m.opacity);
+  k.eta2_out = m.ior * m.ior;
+  k.eta2_in = m.inv_ior * m.inv_ior;
+  k.f0x = m.f0_air * omt + m.color.x * m.metallic;
+  return k;
+}
+// the opacity decrement of a transmissive occluder that is not reflective, per lane: fresnel_reflectance_air_red with
+// reflective = false, ra = 1 and the material's part taken from k
+__device__ __forceinline__ uint32_t occluder_decrement(const OccConst& k, V3 n, V3 d) {
+  const float n_dot_v = dot(n, -d);
+  const float cos_theta = fabsf(n_dot_v);
+  const bool inside = n_dot_v < 0.0f;
+  const float sin2_t = (inside ? k.eta2_out : k.eta2_in) * (1.0f - cos_theta * cos_theta);
+  const bool tir = inside && sin2_t > 1.0f;
+  const float c1 = 1.0f - cos_theta;
+  const float c2 = c1 * c1;
+  const float c5 = c1 * (c2 * c2);
+  const float fres = k.f0x + (1.0f - k.f0x) * c5;
+  const float io = __uint_as_float(k.x) * (1.0f - (tir ? 1.0f : fres));
+  return (uint32_t)__float2uint_rn(clampf(1.0f - io, 0.0f, 1.0f) * RT_SH_SCALE);
+}
+// the per-lane remainder: the sums of the lanes in `h`
+__device__ __forceinline__ void shadow_add(Shadow& S, const OccConst& k, V3 n, V3 d, lanemask h) {
+  const bool on = lane_of(h);
+  uint32_t di = k.x;
+  if (k.x > RT_SH_ONE) di = occluder_decrement(k, n, d);  // (wave-uniform test)
+  const uint32_t nd = min(S.dec + di, RT_SH_ONE);
+  S.dec = on ? nd : S.dec;
+  S.fr = on ? S.fr + k.ar : S.fr;
+  S.fg = on ? S.fg + k.ag : S.fg;
+  S.fb = on ? S.fb + k.ab : S.fb;
+}
+
 // one transmissive / opaque occluder on a shadow ray, raytracer.rs:53-92, applied to the lanes in `h`
 // (predicated, outside divergent control flow, so that S.occ stays a wave-uniform mask; m is wave-uniform)
+// The UNSPLIT form, for the kernels that keep no memo: occluder_constants + shadow_add above restate it piece by piece
+// (written out here, not composed of them: composed, hipcc allocates the generic kernels' registers differently --
+// rt_primary_kernel 20 -> 22 spilled SGPRs -- for the same arithmetic).
 __device__ __forceinline__ void shadow_accumulate(Shadow& S, const Mat& m, V3 n, V3 d, lanemask h) {
   if (!m.transmissive) {
     S.occ |= h;  // io = 0: the decrement is 1
@@ -554,6 +615,39 @@ __device__ __forceinline__ void shadow_accumulate(Shadow& S, const Mat& m, V3 n,
   S.fr = on ? S.fr + ar : S.fr;
   S.fg = on ? S.fg + ag : S.fg;
   S.fb = on ? S.fb + abl : S.fb;
+}
+
+// The constants of the transmissive occluder that a (wavefront, light) met last, in eight scalar registers.  The sample
+// rays of one light cross the same few panes again and again; a scalar compare of the material row then replaces the
+// row's three loads and the vector instructions of occluder_constants (gfx950 has no scalar float ALU: uniform or not,
+// they issue on the VALU).  The memo lives from a light's first transmissive hit to the end of its sample loop, never
+// across lights.
+#define RT_OCC_NO_ROW 0xFFFFFFFFu
+struct OccMemo {
+  uint32_t row;  // material row the constants belong to; RT_OCC_NO_ROW: none yet
+  OccConst k;
+};
+__device__ __forceinline__ uint32_t uniform_u(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ float uniform_f(float v) { return __uint_as_float(uniform_u(__float_as_uint(v))); }
+// one occluder of material `row` (wave-uniform) on the lanes in `h`, through the memo
+template <bool CULL>
+__device__ __forceinline__ void shadow_accumulate_memo(const RtDevScene& sc, Shadow& S, OccMemo& M, uint32_t row, V3 n, V3 d, lanemask h,
+                                                       uint32_t& n_exec, uint32_t& n_miss) {
+  if (row != M.row) {
+    const Mat m = load_mat_u(sc, row);
+    if (!m.transmissive) {
+      if (CULL) h &= wave_ballot(dot(d, n) < 0.75f);
+      S.occ |= h;  // io = 0: the decrement is 1
+      return;
+    }
+    const OccConst k = occluder_constants(m);
+    M.row = row;
+    M.k.ar = uniform_u(k.ar), M.k.ag = uniform_u(k.ag), M.k.ab = uniform_u(k.ab), M.k.x = uniform_u(k.x);
+    M.k.eta2_out = uniform_f(k.eta2_out), M.k.eta2_in = uniform_f(k.eta2_in), M.k.f0x = uniform_f(k.f0x);
+    WSTAT(n_miss++);
+  }
+  WSTAT(n_exec++);
+  shadow_add(S, M.k, n, d, h);
 }
 
 // same for an occluder whose material differs from lane to lane (per-lane walk: rt_hard_kernel, the any-hit query); -> the
@@ -577,6 +671,9 @@ __device__ __forceinline__ lanemask shadow_accumulate_lane(Shadow& S, const Mat&
 struct WaveCtx {
   // wave-level work counters (uniform)
   uint32_t n_nodes, n_tris, s_nodes, s_tris, s_passes, n_exact, s_exact;  // one ray per wavefront: 32 bits are plenty
+  // transmissive occluders accumulated by shadow_ray, and how many of them had another material row than the one before
+  // in the same (wavefront, light): reported by the STATS=2 build in place of n_nodes / n_tris
+  uint32_t o_exec, o_miss;
 #if RT_PROFILE
   unsigned long long t_mark;
   unsigned long long prof[7];  // 0 nearest hit, 1 candidate collection, 2 sample set-up, 3 spheres, 4 triangles, 5 lighting, 6 whole ray
@@ -599,6 +696,7 @@ struct CfgGeneric {
   static constexpr bool POW2_SETS = false;   // true: n_cloud_sets is a power of two
   static constexpr bool FEW_SPHERES = false; // true: n_spheres < 32
   static constexpr bool FAR_ORIGINS = false; // true: rays may start far outside the scene (CfgRays)
+  static constexpr bool OCC_MEMO = false;    // true: shadow_ray keeps the last transmissive occluder's constants (OccMemo)
 };
 template <uint32_t N_, int TABLES_>
 struct CfgSoft {
@@ -608,6 +706,8 @@ struct CfgSoft {
   static constexpr bool POW2_SETS = true;
   static constexpr bool FEW_SPHERES = true;
   static constexpr bool FAR_ORIGINS = false;
+  // (the flags-only kernels keep no memo: its eight registers cost them a spilled SGPR, two VGPRs and 4 B of scratch)
+  static constexpr bool OCC_MEMO = TABLES_ == CFG_TABLES_LISTS;
 };
 // Rays the CALLER supplies (rt_rays.h).  The receiver tables stand for hit points that lie ON their surface to within the
 // rounding of p = o + t d for a ray that starts in or near the scene (collect_light_candidates, COLLECT_FLAGS: 4e-7 |p|).  A
@@ -1179,9 +1279,18 @@ __device__ __forceinline__ CandList collect_light_candidates(const RtDevScene& s
 // LIST: the caller has checked (once per light, not once per sample) that a shared candidate list exists
 template <bool CULL, bool LIST, class C = CfgGeneric>
 __device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevParams& P, WaveCtx& W,
-                                             lanemask grp, V3 o, V3 d_raw, float tmax, const CandList& cand) {
+                                             lanemask grp, V3 o, V3 d_raw, float tmax, const CandList& cand, OccMemo& memo) {
   Shadow S;
   shadow_init(S);
+  // (STATS builds: the transmissive occluders and their changes of material row, counted where no memo is kept too)
+  auto count_occluder = [&](const Mat& m, uint32_t row) {
+    if (m.transmissive) {
+      WSTAT(W.o_exec++);
+      WSTAT(W.o_miss += row != memo.row ? 1u : 0u);
+      WSTAT(memo.row = row);
+    }
+  };
+  (void)count_occluder;
   V3 d = normalize_unit(d_raw, grp);  // Ray::new_with_mask re-normalises, ray.rs:52-57 (d_raw is unit up to rounding)
 #if RT_PROFILE
   RT_OPAQUE(d.x);
@@ -1200,9 +1309,14 @@ __device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevPa
       // of IEEE sqrt + division.  With backface culling the normal decides a hit and stays exact.
       V3 p = fma_s(d, t, o);
       V3 n = CULL ? normalize(p - mk(s.x, s.y, s.z)) : fast_normalize(p - mk(s.x, s.y, s.z));
-      Mat m = load_mat_u(sc, sload<uint32_t>(sc, sc.off_sphere_mat + i * 4u));
-      if (CULL && !m.transmissive) h &= wave_ballot(dot(d, n) < 0.75f);
-      shadow_accumulate(S, m, n, d, h);
+      if (C::OCC_MEMO) {
+        shadow_accumulate_memo<CULL>(sc, S, memo, sload<uint32_t>(sc, sc.off_sphere_mat + i * 4u), n, d, h, W.o_exec, W.o_miss);
+      } else {
+        Mat m = load_mat_u(sc, sload<uint32_t>(sc, sc.off_sphere_mat + i * 4u));
+        if (CULL && !m.transmissive) h &= wave_ballot(dot(d, n) < 0.75f);
+        WSTAT(count_occluder(m, sload<uint32_t>(sc, sc.off_sphere_mat + i * 4u)));
+        shadow_accumulate(S, m, n, d, h);
+      }
     }
   };
   // spheres 0..31 through the bits of the (wavefront, light) mask, in index order; any further ones unconditionally
@@ -1227,10 +1341,15 @@ __device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevPa
     h &= wave_ballot(t <= tmax);
     if (h) {
       float4 sh = sload<float4>(sc, sc.off_tri_shade + slot * 16u);
-      Mat m = load_mat_u(sc, __float_as_uint(sh.w));
-      V3 n = mk(sh.x, sh.y, sh.z);
-      if (CULL && !m.transmissive) h &= wave_ballot(dot(d, n) < 0.75f);
-      shadow_accumulate(S, m, n, d, h);
+      if (C::OCC_MEMO) {
+        shadow_accumulate_memo<CULL>(sc, S, memo, __float_as_uint(sh.w), mk(sh.x, sh.y, sh.z), d, h, W.o_exec, W.o_miss);
+      } else {
+        Mat m = load_mat_u(sc, __float_as_uint(sh.w));
+        V3 n = mk(sh.x, sh.y, sh.z);
+        if (CULL && !m.transmissive) h &= wave_ballot(dot(d, n) < 0.75f);
+        WSTAT(count_occluder(m, __float_as_uint(sh.w)));
+        shadow_accumulate(S, m, n, d, h);
+      }
     }
   };
 
@@ -1314,6 +1433,14 @@ __device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevPa
     }
   }
   return S;
+}
+// a shadow ray on its own: no memo to share with the other samples of its light
+template <bool CULL, bool LIST, class C = CfgGeneric>
+__device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevParams& P, WaveCtx& W,
+                                             lanemask grp, V3 o, V3 d_raw, float tmax, const CandList& cand) {
+  OccMemo memo;
+  memo.row = RT_OCC_NO_ROW;
+  return shadow_ray<CULL, LIST, C>(sc, P, W, grp, o, d_raw, tmax, cand, memo);
 }
 
 // surface data of a hit (SurfaceInteraction, surface_interaction.rs)
@@ -1409,6 +1536,7 @@ struct Wave {
 
 __device__ __forceinline__ void wave_init(Wave& w) {
   w.ctx.n_nodes = w.ctx.n_tris = w.ctx.s_nodes = w.ctx.s_tris = w.ctx.s_passes = w.ctx.n_exact = w.ctx.s_exact = 0;
+  w.ctx.o_exec = w.ctx.o_miss = 0;
   w.cnt_kind[0] = w.cnt_kind[1] = w.cnt_kind[2] = 0;
   w.cnt_shadow = w.cnt_pass = w.cnt_lanes = w.cnt_traced = 0;
 #if RT_PROFILE
@@ -1439,6 +1567,10 @@ __device__ __forceinline__ void wave_flush(const Wave& w, const RtDevParams& P, 
     const unsigned long long v[RT_N_COUNTERS] = {w.cnt_kind[0], w.cnt_kind[1], w.cnt_kind[2], w.cnt_shadow, written,
                                                  w.cnt_pass,    w.ctx.prof[6], w.ctx.prof[0],  w.ctx.prof[1], w.ctx.prof[2],
                                                  w.ctx.prof[3], w.ctx.s_passes, w.ctx.prof[4], w.ctx.prof[5], w.cnt_traced};
+#elif RT_WORK_STATS == 2
+    const unsigned long long v[RT_N_COUNTERS] = {w.cnt_kind[0], w.cnt_kind[1], w.cnt_kind[2], w.cnt_shadow, written,
+                                                 w.cnt_pass,    w.cnt_lanes,   w.ctx.o_exec,   w.ctx.o_miss, w.ctx.s_nodes,
+                                                 w.ctx.s_tris,  w.ctx.s_passes, w.ctx.n_exact, w.ctx.s_exact, w.cnt_traced};
 #else
     const unsigned long long v[RT_N_COUNTERS] = {w.cnt_kind[0], w.cnt_kind[1], w.cnt_kind[2], w.cnt_shadow, written,
                                                  w.cnt_pass,    w.cnt_lanes,   w.ctx.n_nodes,  w.ctx.n_tris, w.ctx.s_nodes,
@@ -1959,6 +2091,8 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       }
     } else {
       auto traced_samples = [&](auto list_tag) {
+        OccMemo memo;  // (this light's alone: empty at its first sample, gone after its last)
+        memo.row = RT_OCC_NO_ROW;
         for (uint32_t j = 0; j < N; j++) {
           const RtDevScene& sc = kernarg_scene();  // (per sample)
           const RtDevParams& P = kernarg_params();
@@ -1970,7 +2104,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
           const V3 ld = ltp * exact_rcp(mag(ltp));  // normalize(ltp): the shadow ray's geometry is exact
           const V3 so = sf.p + ld * epsv;
           const float tmax = mag(lp - so);
-          const Shadow S = shadow_ray<CULL, decltype(list_tag)::value, C>(sc, P, W, use_m, so, ld, tmax, cand);
+          const Shadow S = shadow_ray<CULL, decltype(list_tag)::value, C>(sc, P, W, use_m, so, ld, tmax, cand, memo);
           const lanemask reach_m = use_m & ~S.occ;
 #if RT_PROFILE == 3
           set_occ += (uint32_t)__popcll(use_m & S.occ);
@@ -3046,6 +3180,7 @@ __global__ __launch_bounds__(256) void rt_flags_kernel(RtDevScene sc, RtDevParam
   fb.r = __builtin_fmaf(r, 1.0001f, 4e-7f * (fabsf(pm.x) + fabsf(pm.y) + fabsf(pm.z)));
   WaveCtx W;
   W.n_nodes = W.n_tris = W.s_nodes = W.s_tris = W.s_passes = W.n_exact = W.s_exact = 0;
+  W.o_exec = W.o_miss = 0;
   uint32_t flags = 0u;
   for (uint32_t l = 0; l < sc.n_lights && l < 8u; l++) {
     const float4 L0 = sload<float4>(sc, sc.off_lights + l * 32u);

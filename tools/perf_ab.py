@@ -72,7 +72,12 @@ for spec in args or ["c3"]:
     sp = max(1, st.wave_shadow_passes)
     print(f"{'':28s} per wave-pass: nearest nodes {st.wave_nearest_nodes/max(1,st.wave_ray_passes):.1f} tris {st.wave_nearest_tris/max(1,st.wave_ray_passes):.1f} | "
           f"shadow passes {st.wave_shadow_passes} nodes {st.wave_shadow_nodes/sp:.1f} tris {st.wave_shadow_tris/sp:.1f} exact {st.wave_shadow_tris_exact/sp:.2f}")
-    if os.environ.get("RT_HIP_LIB", "").endswith("_prof4.so"):
+    if os.environ.get("RT_HIP_LIB", "").endswith("_stats2.so"):
+        # make STATS=2 build: nearest_nodes = transmissive occluders accumulated on shadow rays (wave-level executions),
+        # nearest_tris = those whose material row differs from the one before in the same (wavefront, light)
+        print(f"{'':28s} transmissive shadow occluders: {st.wave_nearest_nodes} executions, {st.wave_nearest_tris} with a new material row "
+              f"({100.0*st.wave_nearest_tris/max(1,st.wave_nearest_nodes):.2f} %); {st.wave_nearest_nodes/sp:.3f} per shadow pass")
+    elif os.environ.get("RT_HIP_LIB", "").endswith("_prof4.so"):
         # make PROFILE=4 build: lane occupancy per class of (wavefront, light) set.  Counter order (wave_flush, RT_PROFILE):
         # wave_ray_lanes = prof[6], nearest_nodes = prof[0], nearest_tris = prof[1], shadow_nodes = prof[2], shadow_tris = prof[3],
         # nearest_tris_exact = prof[4], shadow_tris_exact = prof[5]
