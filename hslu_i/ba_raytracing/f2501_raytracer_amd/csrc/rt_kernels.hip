@@ -1518,7 +1518,12 @@ __device__ __forceinline__ LightTerms light_sample_terms(V3 n, V3 view, V3 mmc_l
   }
   T.lf = FILTERED ? diff * cint * opac : diff * cint;
   T.sf = FILTERED ? cint * opac * specf : cint * specf;
-  T.lit = diff > 0.0f;
+  // D10: a sample that arrives with combined opacity 0 (S.dec == RT_SH_ONE) adds nothing, whatever its filter: a filter
+  // channel of 0 would make mLc * lf = inf * 0.  S.dec <= RT_SH_ONE = 2^28, so S.dec >> 28 is 1 exactly there, and the mask
+  // below is 0 there and all ones elsewhere: diff is tested as +0 instead.  (Written as `diff > 0 && S.dec != RT_SH_ONE` the
+  // second compare's lane mask costs rt_primary_kernel four more spilled SGPRs, 24 against its budget of 20; this form stays
+  // in the VALU: profiles/material_domain.md.)
+  T.lit = FILTERED ? __uint_as_float(__float_as_uint(diff) & ((S.dec >> 28) - 1u)) > 0.0f : diff > 0.0f;
   return T;
 }
 

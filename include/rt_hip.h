@@ -69,7 +69,14 @@ extern "C" {
 #define RT_TRAVERSAL_BVH 0u    /* BVH over the triangles (result-preserving w.r.t. the scan) */
 #define RT_TRAVERSAL_LINEAR 1u /* literal linear scan of all objects, raytracer.rs:48,180 */
 
-/* material row layout inside rt_scene_desc.materials (stride RT_MATERIAL_STRIDE floats) */
+/* material row layout inside rt_scene_desc.materials (stride RT_MATERIAL_STRIDE floats).
+ * Domain: colour channels and opacity in [0, 1].  No value is validated; outside the domain a result is finite or not as
+ * the arithmetic gives (an opacity above 1 never raises a shadow ray's opacity again: each hit's decrement is clamped to
+ * [0, 1] before it is summed).  Inside it a shadow ray's colour filter 1 - sum(absorption) can reach 0 only together with
+ * combined opacity 0, and a light sample that arrives with combined opacity 0 contributes nothing (the reference's
+ * colour / filter * opacity would be inf * 0 there); the ray queries still report the filter as it sums, 0 or below included.
+ * Capacity: the absorption a shadow ray collects must stay below 256 per channel (2^-24 fixed point in 32 bits; 255 white
+ * panes of opacity 1e-3 fit); beyond it the filter sum wraps. */
 #define RT_MATERIAL_STRIDE 9u
 #define RT_MAT_R 0
 #define RT_MAT_G 1

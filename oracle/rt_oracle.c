@@ -39,7 +39,10 @@
  *       horizontal max (raytracer_renderer.rs:458-491); identical for the named scenes;
  *   D4  the unseeded per-pixel Poisson light cloud and AA table are replaced by seeded tables
  *       passed in rt_params;
- *   D5  object order is fixed: spheres (insertion order) then triangles (insertion order).
+ *   D5  object order is fixed: spheres (insertion order) then triangles (insertion order);
+ *   D9  a shadow-ray hit's opacity decrement 1 - io is clamped to [0, 1] before it is subtracted;
+ *   D10 a light sample that arrives with combined opacity 0 contributes nothing (colour / filter * 0
+ *       is inf * 0 where the filter reaches 0).
  */
 #include <math.h>
 #include <pthread.h>
@@ -308,7 +311,9 @@ static shadow_t shadow_test(ctx_t* c, v3 from, v3 dir_raw, float tmax) {
       float trans_red = 1.0f - refl.x;
       io = m.opacity * trans_red;
     }
-    r.opacity = clampf(r.opacity - (1.0f - io), 0.0f, 1.0f);
+    /* D9: the decrement is clamped to [0, 1] itself (the same bits for every opacity in [0, 1]); a hit of opacity > 1 then
+     * cannot raise the opacity again, and the result does not depend on the order of the hits */
+    r.opacity = clampf(r.opacity - clampf(1.0f - io, 0.0f, 1.0f), 0.0f, 1.0f);
     if (!tr && fabsf(r.opacity - 0.0f) <= RT_EPS) r.occluded = 1;
     r.filter = vsub(r.filter, absorption(&m));
     if (r.occluded) break; /* :94-96, per lane */
@@ -343,6 +348,7 @@ static void lighting(ctx_t* c, const hit_t* h, const mat_t* m, v3 view, v3* out_
     float tmax = vmag(vsub(lp, so));
     shadow_t S = shadow_test(c, so, ld, tmax);
     if (S.occluded) continue;
+    if (S.opacity == 0.0f) continue; /* D10: nothing arrives; the reference goes on to colour / filter * 0 */
     /* contribution */
     float dist = vmag(ltp) + RT_EPS;
     float cosi = vdot(ltp, h->n) / dist;

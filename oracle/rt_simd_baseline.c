@@ -336,7 +336,8 @@ static shadow8_t shadow8(ctx8* c, v8 from, v8 dir_raw, f8 tmax, f8 active) {
       v8 refl = fresnel8(vsplat(m.r, m.g, m.b), S8(m.metallic), S8(m.ior), true8(), nrm, vneg8(d), S8(1.0f));
       io = mul8(S8(m.opacity), sub8(S8(1.0f), refl.x));
     }
-    f8 nop = clamp8(sub8(r.opacity, sub8(S8(1.0f), io)), S8(0.0f), S8(1.0f));
+    /* D9: the decrement is clamped to [0, 1] itself */
+    f8 nop = clamp8(sub8(r.opacity, clamp8(sub8(S8(1.0f), io), S8(0.0f), S8(1.0f))), S8(0.0f), S8(1.0f));
     r.opacity = sel8(h, nop, r.opacity);
     if (!m.transmissive) r.occluded = or8(r.occluded, and8(h, _mm256_cmp_ps(abs8(sub8(nop, S8(0.0f))), S8(RT_EPS), _CMP_LE_OQ)));
     float op = m.transmissive ? m.opacity : 1.0f;
@@ -383,7 +384,8 @@ static void lighting8(ctx8* c, const hit8* h, v8 view, f8 active, v8* out_direct
     v8 so = vadd8(h->p, vmul8(ld, epsv));
     f8 tmax = vmag8(vsub8(lp, so));
     shadow8_t S = shadow8(c, so, ld, tmax, active);
-    f8 reach = andn8(S.occluded, active);
+    /* D10: a lane whose sample arrives with combined opacity 0 adds nothing, like an occluded one */
+    f8 reach = andn8(or8(S.occluded, _mm256_cmp_ps(S.opacity, S8(0.0f), _CMP_EQ_OQ)), active);
     if (!any8(reach)) continue;
     f8 dist = add8(vmag8(ltp), S8(RT_EPS));
     f8 cosi = div8(vdot8(ltp, h->n), dist);

@@ -75,7 +75,7 @@ _W = {}
 
 
 def _init(kind, key, kw):
-    cfg, flat = syn_workload(key) if kind == "syn" else spec_workload(key)[:2]
+    cfg, flat = syn_workload(key) if kind == "syn" else key if kind == "scene" else spec_workload(key)[:2]
     _W["m"] = Model(flat, cfg, **kw)
 
 
@@ -127,7 +127,8 @@ def spec_intervals(name):
 
 
 def model_intervals(kind, key, pixels, **kw):
-    """float64 intervals of `pixels` ([(gx, gy)]) of a synthetic case (kind "syn") or an at-spec workload ("spec")"""
+    """float64 intervals of `pixels` ([(gx, gy)]) of a synthetic case (kind "syn"), an at-spec workload ("spec") or any
+    scene (kind "scene", key = (cfg, flat)); kw goes to the Model"""
     chunks = [pixels[i::n_procs() * 4] for i in range(n_procs() * 4)]
     with _pool(kind, key, kw) as p:
         res = [r for part in p.map(_eval, [c for c in chunks if c]) for r in part]
@@ -137,8 +138,18 @@ def model_intervals(kind, key, pixels, **kw):
 @functools.lru_cache(maxsize=None)
 def model_counts(key, **kw):
     """the synthetic case's full-frame ray counters and written pixels"""
+    return _counts("syn", key, kw)
+
+
+def scene_counts(cfg, flat, **kw):
+    """the same for any scene at the synthetic frame size"""
+    assert (cfg.width, cfg.height) == (SYN_W, SYN_H)
+    return _counts("scene", (cfg, flat), kw)
+
+
+def _counts(kind, key, kw):
     rows = list(range(SYN_H))
-    with _pool("syn", key, kw) as p:
+    with _pool(kind, key, kw) as p:
         parts = p.map(_count, [rows[i::n_procs()] for i in range(n_procs())])
     tot = {}
     for c in parts:
@@ -161,12 +172,19 @@ def check(res, width, rgb, hit_id, hit_t, t_rel=None):
         if int(hit_id[i]) != r["id"]:
             bad.append((r["px"], "hit id", int(hit_id[i]), r["id"]))
             continue
-        if t_rel is not None and r["id"] >= 0 and abs(float(hit_t[i]) - r["t"]) > t_rel * abs(r["t"]):
+        if t_rel is not None and r["id"] >= 0 and not abs(float(hit_t[i]) - r["t"]) <= t_rel * abs(r["t"]):
             bad.append((r["px"], "t", float(hit_t[i]), r["t"]))
             continue
         lo = np.zeros(3) if r["lo"] is None else r["lo"]
         hi = np.zeros(3) if r["hi"] is None else r["hi"]
         obs = np.asarray(rgb[i], np.float64)
+        # a non-finite value never passes: NaN > TOL is false, so it is rejected by name and not by the comparison
+        if not np.all(np.isfinite(obs)):
+            bad.append((r["px"], "non-finite rgb", obs.tolist()))
+            continue
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+            bad.append((r["px"], "non-finite model bound", lo.tolist(), hi.tolist()))
+            continue
         ex = float(np.maximum(lo - obs, obs - hi).max())
         worst = max(worst, ex)
         narrow += float((hi - lo).max()) < TOL

@@ -121,16 +121,20 @@ class Model:
     refractions.  `reflections` / `refractions` default to the config's features."""
 
     def __init__(self, flat, cfg, reflections=None, refractions=None, aa_offsets=None, cloud=None, cull=None,
-                 cull_threshold=0.75, cull_exempts_transmissive=True, cull_shadows=True):
+                 cull_threshold=0.75, cull_exempts_transmissive=True, cull_shadows=True, d10=True, shininess_clamp=True):
         """cull: back-face culling (sphere.rs:137-151, triangle.rs:154-168), None = the config's feature: an object is hit
         only if d . n < cull_threshold or its material is transmissive; the sphere's n is the normal at the chosen root, the
         triangle's its stored normal; shadow rays cull as every other ray does.  cull_threshold, cull_exempts_transmissive
-        and cull_shadows exist so that a test can mutate the model."""
+        and cull_shadows exist so that a test can mutate the model, and so do d10 (False: a light sample that arrives with
+        combined opacity 0 is shaded as the reference shades it, colour / filter * 0, DESIGN D10) and shininess_clamp (False:
+        the specular exponent is 512 * shininess without its floor of 1)."""
         self.f, self.cfg = flat, cfg
         self.cull = cfg.has("backface_culling") if cull is None else bool(cull)
         self.cull_threshold = float(cull_threshold)
         self.cull_exempts_transmissive = bool(cull_exempts_transmissive)
         self.cull_shadows = bool(cull_shadows)
+        self.d10 = bool(d10)
+        self.shininess_clamp = bool(shininess_clamp)
         self.refl = cfg.has("reflections") if reflections is None else bool(reflections)
         self.refr = cfg.has("refractions") if refractions is None else bool(refractions)
         self.eps_d = float(cfg.eps_distance)
@@ -327,18 +331,20 @@ class Model:
 
     def _chain(self, ids, valid, io, absorb):
         """has_any_intersection's walk in object order for a batch of rays -> occluded (R,), opacity (R,),
-        filter (R,3), opacity-decision near (R,)"""
+        filter (R,3), opacity-decision near (R,), unclamped sum of the opacity decrements (R,)"""
         R = valid.shape[0]
-        op, filt = np.ones(R), np.ones((R, 3))
+        op, filt, dsum = np.ones(R), np.ones((R, 3)), np.zeros(R)
         occ, near = np.zeros(R, bool), np.zeros(R, bool)
         for k in np.nonzero(valid.any(axis=0))[0]:
             on = valid[:, k] & ~occ
-            op = np.where(on, np.clip(op - (1 - io[:, k]), 0.0, 1.0), op)
+            dec = np.clip(1 - io[:, k], 0.0, 1.0)  # DESIGN D9: an opacity above 1 never raises the opacity again
+            op = np.where(on, np.clip(op - dec, 0.0, 1.0), op)
+            dsum = np.where(on, dsum + dec, dsum)
             if not self.obj_tr[ids[k]]:
                 near |= on & (np.abs(np.abs(op) - EPS) < M_OP)
                 occ |= on & (np.abs(op) <= EPS)
             filt = np.where(on[:, None], filt - absorb[:, k], filt)
-        return occ, op, filt, near
+        return occ, op, filt, near, dsum
 
     def _chain_terms(self, so, ld, ids, t, valid, near):
         """per (ray, object) terms of the chain: the opacity an object lets through (io) and what it absorbs"""
@@ -372,7 +378,7 @@ class Model:
         idx = self._candidates(so, LP)
         ids, t, valid, near = self.intersect(so, ld, idx, tmax, cull=self.cull and self.cull_shadows)
         io, absorb = self._chain_terms(so, ld, ids, t, valid, near)
-        occ, op, filt, opnear = self._chain(ids, valid, io, absorb)
+        occ, op, filt, opnear, dsum = self._chain(ids, valid, io, absorb)
         if opnear.any():
             self.amb("near |opacity| <= EPS decision")
         # contribution (light.rs calculate_contribution_at + calculate_lighting)
@@ -387,16 +393,24 @@ class Model:
         if shin > 0:
             rr = ld - 2 * ndl[:, None] * n
             rr = rr / np.sqrt(_dot(rr, rr))[:, None]
-            specf = np.maximum(_dot(rr, view), 0.0) ** max(shin * 512, 1.0)
+            specf = np.maximum(_dot(rr, view), 0.0) ** (max(shin * 512, 1.0) if self.shininess_clamp else shin * 512)
         else:
             specf = np.zeros(NL)
         lit = diff > 0
 
-        def contrib(r, occ_r, op_r, filt_r):
+        def contrib(r, occ_r, op_r, filt_r, dsum_r):
             if occ_r or not lit[r]:
                 return np.zeros(3), np.zeros(3)
-            Lc = ccol[r] / filt_r
-            dcol = mc * Lc * (diff[r] * cint[r] * op_r)
+            if self.d10:
+                # D10: a sample that arrives with combined opacity 0 contributes nothing.  Decrements that sum to 1 while a
+                # filter channel reaches 0 are a near decision: the limit of opacity / filter there is not 0
+                if abs(dsum_r - 1) < M_OP and (np.abs(filt_r) < M_OP).any():
+                    self.amb("near combined opacity 0 decision on a filter channel near 0")
+                if op_r == 0:
+                    return np.zeros(3), np.zeros(3)
+            with np.errstate(divide="ignore", invalid="ignore"):  # (a filter channel of 0: inf, and NaN without D10)
+                Lc = ccol[r] / filt_r
+                dcol = mc * Lc * (diff[r] * cint[r] * op_r)
             scol = LC[r] * (cint[r] * op_r * specf[r]) if shin > 0 else np.zeros(3)
             return dcol, scol
 
@@ -404,7 +418,7 @@ class Model:
         dlo, dhi, slo, shi = np.zeros(3), np.zeros(3), np.zeros(3), np.zeros(3)
         cos_near = (np.abs(cosi) < M_COS) | (np.abs(ndl) < M_COS)
         for r in range(NL):
-            dc, sc = contrib(r, occ[r], op[r], filt[r])
+            dc, sc = contrib(r, occ[r], op[r], filt[r], dsum[r])
             dn, sn = dn + dc, sn + sc
             outs = [(dc, sc)]
             flips = np.nonzero(near[r])[0]
@@ -416,10 +430,10 @@ class Model:
                 for j, k in enumerate(flips):
                     if mask >> j & 1:
                         vr[0, k] = not vr[0, k]
-                o2, p2, f2, n2 = self._chain(ids, vr, io[r:r + 1], absorb[r:r + 1])
+                o2, p2, f2, n2, d2 = self._chain(ids, vr, io[r:r + 1], absorb[r:r + 1])
                 if n2.any():
                     self.amb("near |opacity| <= EPS decision")
-                outs.append(contrib(r, o2[0], p2[0], f2[0]))
+                outs.append(contrib(r, o2[0], p2[0], f2[0], d2[0]))
             if cos_near[r]:
                 outs.append((np.zeros(3), np.zeros(3)))
             ds, ss = np.array([o[0] for o in outs]), np.array([o[1] for o in outs])
@@ -608,7 +622,7 @@ class Model:
             for j, k in enumerate(flips):
                 if mask >> j & 1:
                     vr[0, k] = not vr[0, k]
-            occ, op, filt, opnear = self._chain(ids, vr, io, absorb)
+            occ, op, filt, opnear, _ = self._chain(ids, vr, io, absorb)
             if opnear.any():
                 self.amb("near |opacity| <= EPS decision")
             outs.append((bool(vr.any()), bool(occ[0]), 0.0 if occ[0] else float(op[0]), filt[0]))
