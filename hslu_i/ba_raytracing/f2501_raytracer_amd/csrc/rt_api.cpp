@@ -102,10 +102,7 @@ int rt_scene_create(const rt_scene_desc* d, int device, rt_scene** out) {
   *out = nullptr;
   int rc = rt_check_scene_desc(d);
   if (rc != RT_OK) return rc;
-  int ndev = rt_device_count();
-  if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
-  HIP_TRY(hipSetDevice(device));
+  if ((rc = rt_open_device(device)) != RT_OK) return rc;
 
   rt_scene* s = new rt_scene();
   s->device = device;
@@ -1186,9 +1183,8 @@ int rt_render(rt_scene* s, const rt_params* p, uint32_t* argb, const rt_aux* aux
       ad.hit_t = (float*)s->aux_t.p;
     }
   }
-  EventPair ev, ev_setup;
-  HIP_TRY(hipEventCreate(&ev.e0));
-  HIP_TRY(hipEventCreate(&ev.e1));
+  EventPair ev, ev_setup;  // (ev_setup: e0 alone)
+  if ((rc = ev.create()) != RT_OK) return rc;
   HIP_TRY(hipEventCreate(&ev_setup.e0));
   HIP_TRY(hipEventRecord(ev_setup.e0, nullptr));  // what prepare enqueues (table uploads, rt_flags_kernel) is timed as setup_ms
   RtDevParams P;

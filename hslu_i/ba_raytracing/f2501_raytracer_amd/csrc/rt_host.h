@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_ray_key.h"     // (RtOrderWs)
 #include "rt_scene_pack.h"  // (rt_internal.h; rt_fail; the device-free scene packer and table builders)
 
 #define fail rt_fail
@@ -65,6 +66,11 @@ struct DevBuf {
 
 struct EventPair {  // destroyed on every return path
   hipEvent_t e0 = nullptr, e1 = nullptr;
+  int create() {
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    return RT_OK;
+  }
   ~EventPair() {
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
@@ -73,6 +79,84 @@ struct EventPair {  // destroyed on every return path
 
 // the alignment of every array inside a device allocation that holds several
 inline size_t rt_pad256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
+
+// The layout of one allocation that holds several arrays: list the parts, allocate total() bytes, bind().  Every part
+// starts on a multiple of 256 bytes and occupies rt_pad256(bytes), so a part of 0 bytes takes none.  add() returns the
+// part's offset; with a `slot` the part is remembered, and bind(base) stores base + offset into every slot -- the slots
+// must still be where they were.  bind() may be called again: on a host image first, on its device copy afterwards.
+// Arithmetic only: no HIP call, usable before a device is chosen.
+struct RtArena {
+  struct Part {
+    void** slot;
+    size_t off;
+  };
+  std::vector<Part> parts;
+  size_t used = 0;
+  template <class T = void>
+  size_t add(size_t bytes, T** slot = nullptr) {
+    const size_t off = used;
+    used += rt_pad256(bytes);
+    if (slot) parts.push_back({(void**)slot, off});
+    return off;
+  }
+  size_t total() const { return used; }
+  void bind(void* base) const {
+    for (const Part& p : parts) *p.slot = (char*)base + p.off;
+  }
+};
+
+// the device copy of a refit plan (rt_scene::plan_dev, RtRebuildOut::plan_dev): height_nodes, thr_src, recv_cell, tri_slot
+// of part_bytes[] bytes, then 256 bytes for the 8 words of results; fills off[5], returns the size of the allocation
+inline size_t rt_plan_layout(const size_t part_bytes[4], size_t off[5]) {
+  RtArena lay;
+  for (int k = 0; k < 4; k++) off[k] = lay.add(part_bytes[k]);
+  off[4] = lay.add(256);
+  return lay.total();
+}
+
+// the radix sort's arrays for `n` keys, the head of an RtOrderWs (the orders; the Morton sort of a rebuild): parts of `lay`
+inline void rt_sort_ws_add(RtArena& lay, size_t n, RtOrderWs* ws) {
+  const size_t n_tiles = (n + RT_ORDER_TILE - 1u) / RT_ORDER_TILE;
+  for (uint32_t** per : {&ws->keys, &ws->key_a, &ws->key_b, &ws->idx_a, &ws->idx_b}) lay.add(n * 4, per);
+  lay.add(256u * n_tiles * 4, &ws->hist), lay.add(RT_ORDER_SCAN_BLOCKS * 4, &ws->sums);
+}
+
+// Work enqueued for a handle that nobody has waited for yet: an event behind the last of it, and whether it was recorded.
+struct RtPending {
+  hipEvent_t ev = nullptr;
+  bool pending = false;
+  int create() {
+    HIP_TRY(hipEventCreate(&ev));
+    return RT_OK;
+  }
+  int mark(hipStream_t stream) {
+    HIP_TRY(hipEventRecord(ev, stream));
+    pending = true;
+    return RT_OK;
+  }
+  int wait() {
+    if (pending) {
+      HIP_TRY(hipEventSynchronize(ev));
+      pending = false;
+    }
+    return RT_OK;
+  }
+  void clear() { pending = false; }  // the caller knows that the stream has drained
+  void destroy() {
+    if (pending) (void)hipEventSynchronize(ev);
+    if (ev) (void)hipEventDestroy(ev);
+    ev = nullptr, pending = false;
+  }
+};
+
+// what every create function does first with the device it is given
+inline int rt_open_device(int device) {
+  const int ndev = rt_device_count();
+  if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
+  if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+  return RT_OK;
+}
 
 // The device side of an entry point that takes HOST arrays (rt_cast_rays, rt_any_intersection, rt_trace_rays*,
 // rt_ray_order_build): one device allocation for the call, every array 256-byte aligned in it, and a private stream, so
@@ -88,24 +172,22 @@ struct HostCall {
     bool up, down;
   };
   std::vector<Array> arrays;
+  RtArena lay;
   DevBuf buf;
   hipStream_t stream = nullptr;
   template <class T>
   void in(const T** slot, size_t bytes) {
-    if (*slot) arrays.push_back({(void*)*slot, (void**)slot, bytes, true, false});
+    if (*slot) arrays.push_back({(void*)*slot, (void**)slot, bytes, true, false}), lay.add(bytes, slot);
   }
   // upload_first: a plane the kernels write only in part (argb: a miss leaves the caller's value)
   template <class T>
   void out(T** slot, size_t bytes, bool upload_first = false) {
-    if (*slot) arrays.push_back({*slot, (void**)slot, bytes, upload_first, true});
+    if (*slot) arrays.push_back({*slot, (void**)slot, bytes, upload_first, true}), lay.add(bytes, slot);
   }
   int begin() {
-    size_t total = 0;
-    for (const Array& a : arrays) total += rt_pad256(a.bytes);
-    const int rc = buf.ensure(total);
+    const int rc = buf.ensure(lay.total());
     if (rc != RT_OK) return rc;
-    size_t used = 0;
-    for (const Array& a : arrays) *a.dev = (char*)buf.p + used, used += rt_pad256(a.bytes);
+    lay.bind(buf.p);
     HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     for (const Array& a : arrays)
       if (a.up) HIP_TRY(hipMemcpyAsync(*a.dev, a.host, a.bytes, hipMemcpyHostToDevice, stream));
@@ -120,6 +202,19 @@ struct HostCall {
   ~HostCall() {
     if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
     buf.release();
+  }
+};
+
+// `stream` has drained and is about to be destroyed: what the scene enqueued on it is done, and its handle must not be used again
+void rt_scene_forget_stream(rt_scene* s, hipStream_t stream);
+
+// A HostCall's stream that carried frames of a scene: the scene remembers streams -- of table uploads, of its frame slots --
+// and must not remember this one once it is gone.  Declared behind the HostCall, so that it runs before the stream goes.
+struct Forget {
+  rt_scene* scene;
+  HostCall& c;
+  ~Forget() {
+    if (c.stream) (void)hipStreamSynchronize(c.stream), rt_scene_forget_stream(scene, c.stream);
   }
 };
 
@@ -301,8 +396,6 @@ int rt_trace_rays_enqueue(rt_scene* s, const rt_params* p, const RtRayArgs& r, h
 int rt_trace_rays_check(const rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, const char* fn);
 // the device memory an order holds (rt_ray_order_info.bytes), readable before the order was ever built (rt_rays.cpp)
 size_t rt_ray_order_bytes(const rt_ray_order* o);
-// `stream` has drained and is about to be destroyed: what the scene enqueued on it is done, and its handle must not be used again
-void rt_scene_forget_stream(rt_scene* s, hipStream_t stream);
 // the ray counters of the frame that used frame slot `slot` of the scene last (rt_scene::cur_block right after a frame
 // was enqueued); the caller has waited for that frame
 int rt_collect_stats_slot(rt_scene* s, int slot, rt_stats* st);

@@ -10,21 +10,23 @@
 #include <algorithm>
 #include <cstring>
 
-#include "rt_host.h"
+#include "rt_deform.h"
 #include "rt_pose.h"
 
-static_assert(sizeof(rt_transform) == 32, "a transform is 8 floats");
-
 struct rt_pose {
-  int device = 0;
-  uint32_t n_parts = 0, n_triangles = 0, n_spheres = 0;
+  RtDeformer m;                   // (n_xf: parts; buf: part tables, rest pose, posed arrays, the staged transforms)
+  uint32_t n_triangles = 0, n_spheres = 0;
   bool has_spheres = false;       // some part has spheres: the sphere group travels with every apply
-  RtPoseArrays a{};               // device pointers into `buf`
-  DevBuf buf;                     // part tables, rest pose, posed arrays, the staged transforms
-  rt_transform* xf_dev = nullptr;
-  rt_transform* xf_stage = nullptr;  // pinned, [n_parts]
-  hipEvent_t done_ev = nullptr;      // behind the last kernel enqueued for this pose
-  bool pending = false;
+  RtPoseArrays a{};               // device pointers into m.buf
+  int launch(const rt_transform* transforms_dev, hipStream_t stream) {
+    const hipError_t e = (hipError_t)rt_launch_pose(a, transforms_dev, stream);
+    return e == hipSuccess ? RT_OK : fail(RT_ERR_HIP, "pose kernel launch failed: %s", hipGetErrorString(e));
+  }
+  static int check_apply(const rt_scene* s, const rt_pose* p, const rt_transform* t, const char* fn, rt_scene_delta* delta);
+  static int check_table(const rt_transform* t, uint32_t n, const char* fn) {
+    const int64_t bad = rt_deform_first_non_finite(t, n);
+    return bad < 0 ? RT_OK : fail(RT_ERR_INVALID_ARG, "%s: transform %u has a non-finite member", fn, (uint32_t)bad);
+  }
 };
 
 namespace {
@@ -86,50 +88,17 @@ void part_tables(const rt_pose_desc* d, const Cover& c, std::vector<uint32_t>* t
   }
 }
 
-int check_transforms(const rt_transform* t, uint32_t n, const char* fn) {
-  for (uint32_t p = 0; p < n; p++) {
-    const float* q = (const float*)(t + p);
-    for (int k = 0; k < 8; k++)
-      if (!rt_finite(q[k])) return fail(RT_ERR_INVALID_ARG, "%s: transform %u has a non-finite member", fn, p);
-  }
-  return RT_OK;
-}
-
-void pose_free(rt_pose* p) {
-  if (!p) return;
-  (void)hipSetDevice(p->device);
-  if (p->pending) (void)hipEventSynchronize(p->done_ev);
-  if (p->done_ev) (void)hipEventDestroy(p->done_ev);
-  if (p->xf_stage) (void)hipHostFree(p->xf_stage);
-  p->buf.release();
-  delete p;
-}
-
-int pose_wait(rt_pose* p) {
-  if (p->pending) {
-    HIP_TRY(hipEventSynchronize(p->done_ev));
-    p->pending = false;
-  }
-  return RT_OK;
-}
-
-int kernel_enqueue(rt_pose* p, const rt_transform* transforms_dev, hipStream_t stream) {
-  const hipError_t e = (hipError_t)rt_launch_pose(p->a, transforms_dev, stream);
-  if (e != hipSuccess) return fail(RT_ERR_HIP, "pose kernel launch failed: %s", hipGetErrorString(e));
-  HIP_TRY(hipEventRecord(p->done_ev, stream));
-  p->pending = true;
-  return RT_OK;
-}
+}  // namespace
 
 // what an apply refuses itself, before any HIP call, and the delta it hands on
-int check_apply(const rt_scene* s, const rt_pose* p, const rt_transform* t, const char* fn, rt_scene_delta* delta) {
+int rt_pose::check_apply(const rt_scene* s, const rt_pose* p, const rt_transform* t, const char* fn, rt_scene_delta* delta) {
   if (!s) return fail(RT_ERR_INVALID_ARG, "%s: null scene", fn);
   if (!p) return fail(RT_ERR_INVALID_ARG, "%s: null pose", fn);
   if (!t) return fail(RT_ERR_INVALID_ARG, "%s: null transforms", fn);
   if (p->n_triangles != s->dev.n_triangles || p->n_spheres != s->dev.n_spheres)
     return fail(RT_ERR_INVALID_ARG, "%s: the pose is for %u triangles and %u spheres, the scene has %u and %u", fn, p->n_triangles, p->n_spheres,
                 s->dev.n_triangles, s->dev.n_spheres);
-  if (p->device != s->device) return fail(RT_ERR_INVALID_ARG, "%s: the pose lives on device %d, the scene on device %d", fn, p->device, s->device);
+  if (p->m.device != s->device) return fail(RT_ERR_INVALID_ARG, "%s: the pose lives on device %d, the scene on device %d", fn, p->m.device, s->device);
   rt_scene_delta d{};
   d.abi_version = RT_ABI_VERSION;
   if (p->a.n_cover) {
@@ -137,15 +106,8 @@ int check_apply(const rt_scene* s, const rt_pose* p, const rt_transform* t, cons
     d.tri_v1 = p->a.o_v1, d.tri_e1 = p->a.o_e1, d.tri_e2 = p->a.o_e2, d.tri_normal = p->a.o_normal;
   }
   if (p->has_spheres) d.sphere_center = p->a.o_centre, d.sphere_r_sq = p->a.o_r_sq, d.sphere_r_inv = p->a.o_r_inv;
-  // rt_scene_update_device's own refusals, made here too so that a refused apply has not run the kernel
-  if (s->progress_active) return fail(RT_ERR_INVALID_ARG, "a progressive render owns this scene until rt_render_end");
-  const int rc = rt_check_scene_delta(s->dev, s->plan, &d, nullptr);
-  if (rc != RT_OK) return rc;
-  *delta = d;
-  return RT_OK;
+  return rt_deform_check_delta(s, d, delta);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -156,119 +118,66 @@ int rt_pose_create(const rt_pose_desc* d, int device, rt_pose** out) {
   Cover c;
   int rc = check_desc(d, fn, &c);
   if (rc != RT_OK) return rc;
-  const int ndev = rt_device_count();
-  if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
-  HIP_TRY(hipSetDevice(device));
+  if ((rc = rt_open_device(device)) != RT_OK) return rc;
   rt_pose* p = new rt_pose();
-  p->device = device, p->n_parts = d->n_parts, p->n_triangles = d->n_triangles, p->n_spheres = d->n_spheres, p->has_spheres = c.has_spheres;
-  // one host image of the allocation, every array on a multiple of 256 bytes, uploaded in one copy
+  p->m.device = device, p->m.n_xf = d->n_parts, p->n_triangles = d->n_triangles, p->n_spheres = d->n_spheres, p->has_spheres = c.has_spheres;
+  // one host image of the allocation: p->a points into it until it is uploaded
   const size_t nc = c.n_cover, ns = c.has_spheres ? d->n_spheres : 0u;
-  const size_t t1 = rt_pad256(nc * 4), t3 = rt_pad256(nc * 12), s1 = rt_pad256(ns * 4), s3 = rt_pad256(ns * 12), xf = rt_pad256((size_t)d->n_parts * 32);
-  const size_t total = t1 + 8 * t3 + s1 + 2 * s3 + 3 * s1 + xf;
-  std::vector<unsigned char> img(total, 0);
-  size_t used = 0;
-  auto take = [&](size_t bytes) {
-    unsigned char* at = img.data() + used;
-    used += bytes;
-    return at;
-  };
-  uint32_t* tri_part = (uint32_t*)take(t1);
-  float *v1 = (float*)take(t3), *v2 = (float*)take(t3), *v3 = (float*)take(t3), *nrm = (float*)take(t3);
-  float *o_v1 = (float*)take(t3), *o_e1 = (float*)take(t3), *o_e2 = (float*)take(t3), *o_n = (float*)take(t3);
-  uint32_t* sphere_part = (uint32_t*)take(s1);
-  float *centre = (float*)take(s3), *radius = (float*)take(s1);
-  float *o_c = (float*)take(s3), *o_rsq = (float*)take(s1), *o_rinv = (float*)take(s1);
-  unsigned char* xf_at = take(xf);
+  RtPoseArrays& a = p->a;
+  a.lo = c.lo, a.n_cover = (uint32_t)nc, a.n_spheres = (uint32_t)ns;
+  RtArena lay;
+  lay.add(nc * 4, &a.tri_part);
+  for (const float** in : {&a.v1, &a.v2, &a.v3, &a.normal}) lay.add(nc * 12, in);
+  for (float** o : {&a.o_v1, &a.o_e1, &a.o_e2, &a.o_normal}) lay.add(nc * 12, o);
+  lay.add(ns * 4, &a.sphere_part), lay.add(ns * 12, &a.centre), lay.add(ns * 4, &a.radius);
+  lay.add(ns * 12, &a.o_centre), lay.add(ns * 4, &a.o_r_sq), lay.add(ns * 4, &a.o_r_inv);
+  lay.add((size_t)d->n_parts * 32, &p->m.xf_dev);
+  std::vector<unsigned char> img(lay.total(), 0);
+  lay.bind(img.data());
   std::vector<uint32_t> tp, sp;
   part_tables(d, c, &tp, &sp);
+  const size_t off = 3 * (size_t)c.lo;
   if (nc) {
-    memcpy(tri_part, tp.data(), nc * 4);
-    memcpy(v1, d->tri_v1 + 3 * (size_t)c.lo, nc * 12), memcpy(v2, d->tri_v2 + 3 * (size_t)c.lo, nc * 12);
-    memcpy(v3, d->tri_v3 + 3 * (size_t)c.lo, nc * 12), memcpy(nrm, d->tri_normal + 3 * (size_t)c.lo, nc * 12);
+    memcpy((void*)a.tri_part, tp.data(), nc * 4);
+    memcpy((void*)a.v1, d->tri_v1 + off, nc * 12), memcpy((void*)a.v2, d->tri_v2 + off, nc * 12);
+    memcpy((void*)a.v3, d->tri_v3 + off, nc * 12), memcpy((void*)a.normal, d->tri_normal + off, nc * 12);
   }
-  if (ns) memcpy(sphere_part, sp.data(), ns * 4), memcpy(centre, d->sphere_center, ns * 12), memcpy(radius, d->sphere_radius, ns * 4);
-  RtPoseArrays host{c.lo, (uint32_t)nc, (uint32_t)ns, tri_part, sphere_part, v1, v2, v3, nrm, centre, radius, o_v1, o_e1, o_e2, o_n, o_c, o_rsq, o_rinv};
-  for (uint32_t k = 0; k < nc; k++) rt_pose_tri(host, k, nullptr);  // the posed arrays start as the rest pose
-  for (uint32_t i = 0; i < ns; i++) rt_pose_sphere(host, i, nullptr);
-  rc = p->buf.ensure(total);
-  if (rc == RT_OK) {
-    const hipError_t e = hipMemcpy(p->buf.p, img.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = fail(RT_ERR_HIP, "hipMemcpy H2D failed: %s", hipGetErrorString(e));
-  }
-  if (rc == RT_OK && hipHostMalloc((void**)&p->xf_stage, (size_t)d->n_parts * 32, hipHostMallocDefault) != hipSuccess)
-    p->xf_stage = nullptr, rc = fail(RT_ERR_OOM, "hipHostMalloc(%zu) failed", (size_t)d->n_parts * 32);
-  if (rc == RT_OK && hipEventCreate(&p->done_ev) != hipSuccess) p->done_ev = nullptr, rc = fail(RT_ERR_HIP, "hipEventCreate failed");
-  if (rc != RT_OK) {
-    pose_free(p);
-    return rc;
-  }
-  char* base = (char*)p->buf.p;
-  auto dev = [&](const void* host_at) { return base + ((const unsigned char*)host_at - img.data()); };
-  p->a = RtPoseArrays{c.lo, (uint32_t)nc, (uint32_t)ns, (const uint32_t*)dev(tri_part), (const uint32_t*)dev(sphere_part),
-                      (const float*)dev(v1), (const float*)dev(v2), (const float*)dev(v3), (const float*)dev(nrm),
-                      (const float*)dev(centre), (const float*)dev(radius), (float*)dev(o_v1), (float*)dev(o_e1), (float*)dev(o_e2),
-                      (float*)dev(o_n), (float*)dev(o_c), (float*)dev(o_rsq), (float*)dev(o_rinv)};
-  p->xf_dev = (rt_transform*)dev(xf_at);
+  if (ns) memcpy((void*)a.sphere_part, sp.data(), ns * 4), memcpy((void*)a.centre, d->sphere_center, ns * 12), memcpy((void*)a.radius, d->sphere_radius, ns * 4);
+  for (uint32_t k = 0; k < nc; k++) rt_pose_tri(a, k, nullptr);  // the posed arrays start as the rest pose
+  for (uint32_t i = 0; i < ns; i++) rt_pose_sphere(a, i, nullptr);
+  if ((rc = rt_deform_upload(p, lay, img)) != RT_OK) return rc;
   *out = p;
   return RT_OK;
 }
 
-void rt_pose_destroy(rt_pose* p) { pose_free(p); }
+void rt_pose_destroy(rt_pose* p) { rt_deform_free(p); }
 
 int rt_pose_geometry_device(rt_pose* p, const rt_transform* transforms_dev, void* hip_stream) {
   const char* fn = "rt_pose_geometry_device";
   if (!p) return fail(RT_ERR_INVALID_ARG, "%s: null pose", fn);
   if (!transforms_dev) return fail(RT_ERR_INVALID_ARG, "%s: null transforms", fn);
-  HIP_TRY(hipSetDevice(p->device));
-  return kernel_enqueue(p, transforms_dev, (hipStream_t)hip_stream);
+  return rt_deform_geometry_device(p, transforms_dev, hip_stream);
 }
 
 int rt_pose_apply_device(rt_scene* s, rt_pose* p, const rt_transform* transforms_dev, void* hip_stream, rt_update_info* info) {
-  rt_scene_delta d;
-  int rc = check_apply(s, p, transforms_dev, "rt_pose_apply_device", &d);
-  if (rc != RT_OK) return rc;
-  HIP_TRY(hipSetDevice(p->device));
-  if ((rc = kernel_enqueue(p, transforms_dev, (hipStream_t)hip_stream)) != RT_OK) return rc;
-  rc = rt_scene_update_device(s, &d, hip_stream, info);  // (blocks: the stream has drained)
-  if (rc == RT_OK) p->pending = false;
-  return rc;
+  return rt_deform_apply_device(s, p, transforms_dev, hip_stream, info, "rt_pose_apply_device");
 }
 
 int rt_pose_apply(rt_scene* s, rt_pose* p, const rt_transform* transforms_host, rt_update_info* info) {
-  const char* fn = "rt_pose_apply";
-  rt_scene_delta d;
-  int rc = check_apply(s, p, transforms_host, fn, &d);
-  if (rc == RT_OK) rc = check_transforms(transforms_host, p->n_parts, fn);
-  if (rc != RT_OK) return rc;
-  HIP_TRY(hipSetDevice(p->device));
-  if ((rc = pose_wait(p)) != RT_OK) return rc;  // (a kernel still in flight reads the staged transforms)
-  memcpy(p->xf_stage, transforms_host, (size_t)p->n_parts * 32);
-  HIP_TRY(hipMemcpyAsync(p->xf_dev, p->xf_stage, (size_t)p->n_parts * 32, hipMemcpyHostToDevice, nullptr));
-  if ((rc = kernel_enqueue(p, p->xf_dev, nullptr)) != RT_OK) return rc;
-  rc = rt_scene_update_device(s, &d, nullptr, info);
-  if (rc == RT_OK) p->pending = false;
-  return rc;
+  return rt_deform_apply(s, p, transforms_host, info, "rt_pose_apply");
 }
 
 int rt_pose_read(rt_pose* p, float* tri_v1, float* tri_e1, float* tri_e2, float* tri_normal, uint32_t* tri_first, uint32_t* tri_count,
                  float* sphere_center, float* sphere_r_sq, float* sphere_r_inv) {
   if (!p) return fail(RT_ERR_INVALID_ARG, "rt_pose_read: null pose");
-  HIP_TRY(hipSetDevice(p->device));
-  const int rc = pose_wait(p);
+  const int rc = rt_deform_wait(p->m);
   if (rc != RT_OK) return rc;
   const size_t nc = p->a.n_cover, ns = p->a.n_spheres;
   if (tri_first) *tri_first = p->a.lo;
   if (tri_count) *tri_count = p->a.n_cover;
-  const struct {
-    float* host;
-    const float* dev;
-    size_t bytes;
-  } arrays[7] = {{tri_v1, p->a.o_v1, nc * 12},  {tri_e1, p->a.o_e1, nc * 12},      {tri_e2, p->a.o_e2, nc * 12},     {tri_normal, p->a.o_normal, nc * 12},
-                 {sphere_center, p->a.o_centre, ns * 12}, {sphere_r_sq, p->a.o_r_sq, ns * 4}, {sphere_r_inv, p->a.o_r_inv, ns * 4}};
-  for (const auto& a : arrays)
-    if (a.host && a.bytes) HIP_TRY(hipMemcpy(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  const RtReadBack arrays[7] = {{tri_v1, p->a.o_v1, nc * 12}, {tri_e1, p->a.o_e1, nc * 12}, {tri_e2, p->a.o_e2, nc * 12}, {tri_normal, p->a.o_normal, nc * 12},
+                                {sphere_center, p->a.o_centre, ns * 12}, {sphere_r_sq, p->a.o_r_sq, ns * 4}, {sphere_r_inv, p->a.o_r_inv, ns * 4}};
+  return rt_deform_read(arrays);
 }
 
 int rt_pose_model(const rt_pose_desc* d, const rt_transform* transforms, float* tri_v1, float* tri_e1, float* tri_e2, float* tri_normal,
@@ -281,12 +190,10 @@ int rt_pose_model(const rt_pose_desc* d, const rt_transform* transforms, float* 
   std::vector<uint32_t> tp, sp;
   part_tables(d, c, &tp, &sp);
   const size_t nc = c.n_cover, ns = sp.size();
-  // outputs the caller does not want land in scratch arrays
   std::vector<float> scratch[7];
   float* o[7] = {tri_v1, tri_e1, tri_e2, tri_normal, sphere_center, sphere_r_sq, sphere_r_inv};
   const size_t floats[7] = {3 * nc, 3 * nc, 3 * nc, 3 * nc, 3 * ns, ns, ns};
-  for (int k = 0; k < 7; k++)
-    if (!o[k]) scratch[k].resize(floats[k] + 1), o[k] = scratch[k].data();
+  rt_deform_scratch(o, floats, scratch);
   const size_t off = 3 * (size_t)c.lo;
   const RtPoseArrays a{c.lo, (uint32_t)nc, (uint32_t)ns, tp.data(), sp.data(),
                        nc ? d->tri_v1 + off : nullptr, nc ? d->tri_v2 + off : nullptr, nc ? d->tri_v3 + off : nullptr, nc ? d->tri_normal + off : nullptr,

@@ -25,8 +25,7 @@ struct rt_ray_order {
   bool has_keys = false;  // built (rt_ray_order_set leaves no keys)
   DevBuf buf;
   RtOrderWs ws{};
-  hipEvent_t built_ev = nullptr;  // recorded behind the kernels of the last build
-  bool build_pending = false;
+  RtPending built;        // behind the kernels of the last build
   double device_ms = 0.0;
 };
 
@@ -57,18 +56,10 @@ int order_enqueue(rt_ray_order* o, const float* origin, const float* direction, 
   if (n) {
     const hipError_t e = (hipError_t)rt_launch_order_build(o->ws, origin, direction, n, o->origin_bits, stream);
     if (e != hipSuccess) return fail(RT_ERR_HIP, "ray order launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(hipEventRecord(o->built_ev, stream));
-    o->build_pending = true;
+    const int rc = o->built.mark(stream);
+    if (rc != RT_OK) return rc;
   }
   o->n = n, o->ready = true, o->has_keys = true, o->device_ms = 0.0;
-  return RT_OK;
-}
-
-int order_wait(rt_ray_order* o) {
-  if (o->build_pending) {
-    HIP_TRY(hipEventSynchronize(o->built_ev));
-    o->build_pending = false;
-  }
   return RT_OK;
 }
 
@@ -115,28 +106,19 @@ RtRayArgs args_of(const rt_ray_batch* b, const rt_ray_radiance* o, const rt_ray_
 
 // the device memory of an order for `capacity` rays on the current device
 int order_alloc(rt_ray_order* o) {
-  const size_t per = rt_pad256((size_t)o->capacity * 4);
-  const size_t n_tiles = ((size_t)o->capacity + RT_ORDER_TILE - 1u) / RT_ORDER_TILE;
-  const size_t sums = rt_pad256(RT_ORDER_SCAN_BLOCKS * 4);
-  const size_t hist = rt_pad256(256u * n_tiles * 4), partial = rt_pad256(RT_ORDER_BOUNDS_WGS * sizeof(RtKeyBounds)), frame = rt_pad256(sizeof(RtKeyFrame));
-  int rc = o->buf.ensure(5 * per + hist + sums + partial + frame);
+  RtArena lay;
+  rt_sort_ws_add(lay, o->capacity, &o->ws);
+  lay.add(RT_ORDER_BOUNDS_WGS * sizeof(RtKeyBounds), &o->ws.partial), lay.add(sizeof(RtKeyFrame), &o->ws.frame);
+  const int rc = o->buf.ensure(lay.total());
   if (rc != RT_OK) return rc;
-  char* p = (char*)o->buf.p;
-  o->ws.keys = (uint32_t*)p, o->ws.key_a = (uint32_t*)(p + per), o->ws.key_b = (uint32_t*)(p + 2 * per);
-  o->ws.idx_a = (uint32_t*)(p + 3 * per), o->ws.idx_b = (uint32_t*)(p + 4 * per);
-  o->ws.hist = (uint32_t*)(p + 5 * per);
-  o->ws.sums = (uint32_t*)(p + 5 * per + hist);
-  o->ws.partial = (RtKeyBounds*)(p + 5 * per + hist + sums);
-  o->ws.frame = (RtKeyFrame*)(p + 5 * per + hist + sums + partial);
-  HIP_TRY(hipEventCreate(&o->built_ev));
-  return RT_OK;
+  lay.bind(o->buf.p);
+  return o->built.create();
 }
 
 void order_free(rt_ray_order* o) {
   if (!o) return;
   (void)hipSetDevice(o->device);
-  if (o->build_pending) (void)hipEventSynchronize(o->built_ev);
-  if (o->built_ev) (void)hipEventDestroy(o->built_ev);
+  o->built.destroy();
   o->buf.release();
   delete o;
 }
@@ -170,19 +152,11 @@ int trace_host(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_
   HostCall c;  // (declared behind `own`: the stream drains before the call's order is freed)
   c.in(&r.origin, n * 12), c.in(&r.direction, n * 12);
   c.out(&r.rgb, n * 12), c.out(&r.valid, n), c.out(&r.id, n * 4), c.out(&r.t, n * 4), c.out(&r.argb, n * 4, true);
-  struct Forget {  // the scene remembers streams -- of table uploads, of its frame slots: not this one, once it is gone
-    rt_scene* scene;
-    HostCall& c;
-    ~Forget() {
-      if (c.stream) (void)hipStreamSynchronize(c.stream), rt_scene_forget_stream(scene, c.stream);
-    }
-  } forget{s, c};
+  Forget forget{s, c};
   EventPair ev;
-  HIP_TRY(hipEventCreate(&ev.e0));
-  HIP_TRY(hipEventCreate(&ev.e1));
-  if ((rc = c.begin()) != RT_OK) return rc;
+  if ((rc = ev.create()) != RT_OK || (rc = c.begin()) != RT_OK) return rc;
   // an order another stream is still building: this stream waits for it
-  if (order && !build_one && order->build_pending) HIP_TRY(hipStreamWaitEvent(c.stream, order->built_ev, 0));
+  if (order && !build_one && order->built.pending) HIP_TRY(hipStreamWaitEvent(c.stream, order->built.ev, 0));
   HIP_TRY(hipEventRecord(ev.e0, c.stream));
   if (build_one && (rc = order_enqueue(own.o, r.origin, r.direction, b->n_rays, c.stream)) != RT_OK) return rc;
   if ((rc = rt_trace_rays_enqueue(s, &q, r, c.stream)) != RT_OK) return rc;
@@ -251,13 +225,11 @@ int rt_ray_order_create(const rt_ray_order_desc* d, int device, rt_ray_order** o
   if (d->capacity > RT_ORDER_MAX_RAYS) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_create: capacity %u exceeds the %u rays an order sorts", d->capacity, RT_ORDER_MAX_RAYS);
   if (d->origin_bits > RT_KEY_AXIS_BITS) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_create: origin_bits %u > %u", d->origin_bits, RT_KEY_AXIS_BITS);
   if (d->reserved) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_create: rt_ray_order_desc.reserved must be 0");
-  const int ndev = rt_device_count();
-  if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
-  HIP_TRY(hipSetDevice(device));
+  int rc = rt_open_device(device);
+  if (rc != RT_OK) return rc;
   rt_ray_order* o = new rt_ray_order();
   o->device = device, o->capacity = d->capacity, o->origin_bits = d->origin_bits;
-  const int rc = order_alloc(o);
+  rc = order_alloc(o);
   if (rc != RT_OK) {
     order_free(o);
     return rc;
@@ -279,21 +251,19 @@ int rt_ray_order_build(rt_ray_order* o, const rt_ray_batch* b) {
   int rc = check_order_batch(o, b, "rt_ray_order_build");
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(o->device));
-  if ((rc = order_wait(o)) != RT_OK) return rc;
+  if ((rc = o->built.wait()) != RT_OK) return rc;
   const size_t n = b->n_rays;
   if (n == 0) return order_enqueue(o, nullptr, nullptr, 0, nullptr);
   const float *d_o = b->origin, *d_d = b->direction;
   HostCall c;
   c.in(&d_o, n * 12), c.in(&d_d, n * 12);
   EventPair ev;
-  HIP_TRY(hipEventCreate(&ev.e0));
-  HIP_TRY(hipEventCreate(&ev.e1));
-  if ((rc = c.begin()) != RT_OK) return rc;
+  if ((rc = ev.create()) != RT_OK || (rc = c.begin()) != RT_OK) return rc;
   HIP_TRY(hipEventRecord(ev.e0, c.stream));
   if ((rc = order_enqueue(o, d_o, d_d, b->n_rays, c.stream)) != RT_OK) return rc;
   HIP_TRY(hipEventRecord(ev.e1, c.stream));
   if ((rc = c.finish()) != RT_OK) return rc;
-  o->build_pending = false;
+  o->built.clear();
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   o->device_ms = ms;
@@ -306,7 +276,7 @@ int rt_ray_order_set(rt_ray_order* o, const uint32_t* perm, uint32_t n) {
   int rc = rt_check_permutation(perm, n);
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(o->device));
-  if ((rc = order_wait(o)) != RT_OK) return rc;
+  if ((rc = o->built.wait()) != RT_OK) return rc;
   if (n) HIP_TRY(hipMemcpy(o->ws.idx_b, perm, (size_t)n * 4, hipMemcpyHostToDevice));
   o->n = n, o->ready = true, o->has_keys = false, o->device_ms = 0.0;
   return RT_OK;
@@ -317,7 +287,7 @@ int rt_ray_order_read(rt_ray_order* o, uint32_t* perm, uint32_t* keys, rt_ray_or
   if (!o->ready) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_read: the ray order has never been built or set");
   if (keys && !o->has_keys) return fail(RT_ERR_INVALID_ARG, "rt_ray_order_read: an order given by rt_ray_order_set has no keys");
   HIP_TRY(hipSetDevice(o->device));
-  const int rc = order_wait(o);
+  const int rc = o->built.wait();
   if (rc != RT_OK) return rc;
   if (perm && o->n) HIP_TRY(hipMemcpy(perm, o->ws.idx_b, (size_t)o->n * 4, hipMemcpyDeviceToHost));
   if (keys && o->n) HIP_TRY(hipMemcpy(keys, o->ws.keys, (size_t)o->n * 4, hipMemcpyDeviceToHost));

@@ -18,32 +18,26 @@ int rt_rebuild_device(const RtRebuildIn& in, hipStream_t stream, RtRebuildOut* o
     ~Bufs() { ws.release(), blob.release(), plan.release(); }
   } b;
   // ---- scratch
-  const uint32_t n_tiles = (n + RT_ORDER_TILE - 1u) / RT_ORDER_TILE, total = (n + 7u) / 8u * 8u;
-  const size_t per = rt_pad256((size_t)n * 4), hist = rt_pad256((size_t)256u * n_tiles * 4), sums = rt_pad256(RT_ORDER_SCAN_BLOCKS * 4);
-  const size_t kn = rt_pad256((size_t)n * sizeof(RtLbvhNode)), rank = rt_pad256((size_t)total * 4), res = rt_pad256(RT_LBVH_RES_WORDS * 4);
+  const size_t per = (size_t)n * 4, sums = RT_ORDER_SCAN_BLOCKS * 4, rank = (size_t)(n + 7u) / 8u * 8u * 4, ids = 2 * (size_t)n - 1u;
   const bool ploc = in.method == RT_REBUILD_PLOC && n > max_leaf;  // (n <= max_leaf: the single root of either method)
-  const size_t ids = 2 * (size_t)n - 1u, nodes = rt_pad256(ids * sizeof(RtPlocNode)), places = rt_pad256(ids * sizeof(RtPlocPlace));
-  int rc = b.ws.ensure(5 * per + hist + sums + 256 + res + (ploc ? nodes + places + 3 * per + rank + sums + 256 : 2 * per + sums + kn + rank));
-  if (rc != RT_OK) return rc;
   RtRebuildWs w{};
   RtPlocWs pw{};
-  char* p = (char*)b.ws.p;
-  auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
-  w.sort.keys = (uint32_t*)take(per), w.sort.key_a = (uint32_t*)take(per), w.sort.key_b = (uint32_t*)take(per);
-  w.sort.idx_a = (uint32_t*)take(per), w.sort.idx_b = (uint32_t*)take(per);
-  w.sort.hist = (uint32_t*)take(hist), w.sort.sums = (uint32_t*)take(sums);
-  w.frame = (float*)take(256), w.result = (uint32_t*)take(res);
+  RtArena lay;
+  rt_sort_ws_add(lay, n, &w.sort);
+  lay.add(256, &w.frame), lay.add(RT_LBVH_RES_WORDS * 4, &w.result);
   if (ploc) {
-    pw.node = (RtPlocNode*)take(nodes), pw.place = (RtPlocPlace*)take(places);
-    pw.cid[0] = (uint32_t*)take(per), pw.cid[1] = (uint32_t*)take(per), pw.nn = (uint32_t*)take(per);
-    pw.flags = (uint32_t*)take(rank), pw.scan_sums = (uint32_t*)take(sums), pw.state = (RtPlocState*)take(256);
+    lay.add(ids * sizeof(RtPlocNode), &pw.node), lay.add(ids * sizeof(RtPlocPlace), &pw.place);
+    lay.add(per, &pw.cid[0]), lay.add(per, &pw.cid[1]), lay.add(per, &pw.nn);
+    lay.add(rank, &pw.flags), lay.add(sums, &pw.scan_sums), lay.add(256, &pw.state);
   } else {
-    w.depth = (uint32_t*)take(per), w.start = (uint32_t*)take(per), w.scan_sums = (uint32_t*)take(sums);
-    w.kn = (RtLbvhNode*)take(kn), w.rank = (uint32_t*)take(rank);
+    lay.add(per, &w.depth), lay.add(per, &w.start), lay.add(sums, &w.scan_sums);
+    lay.add((size_t)n * sizeof(RtLbvhNode), &w.kn), lay.add(rank, &w.rank);
   }
+  int rc = b.ws.ensure(lay.total());
+  if (rc != RT_OK) return rc;
+  lay.bind(b.ws.p);
   EventPair ev;
-  HIP_TRY(hipEventCreate(&ev.e0));
-  HIP_TRY(hipEventCreate(&ev.e1));
+  if ((rc = ev.create()) != RT_OK) return rc;
   HIP_TRY(hipEventRecord(ev.e0, stream));
   // ---- phase 1: the topology, and the few words the new blob is laid out with
   hipError_t e;
@@ -69,10 +63,8 @@ int rt_rebuild_device(const RtRebuildIn& in, hipStream_t stream, RtRebuildOut* o
   rc = b.blob.ensure(bytes);
   if (rc != RT_OK) return rc;
   sc.base = (const char*)b.blob.p;
-  const size_t part[4] = {(size_t)sh.n_nodes * 4, (size_t)sh.n_thr * 4, (size_t)n * 8, (size_t)n * 4};  // as rt_scene_upload_plan
-  size_t plan_bytes = 0;
-  for (int k = 0; k < 4; k++) out->plan_off[k] = plan_bytes, plan_bytes += rt_pad256(part[k]);
-  out->plan_off[4] = plan_bytes, plan_bytes += 256;
+  const size_t part[4] = {(size_t)sh.n_nodes * 4, (size_t)sh.n_thr * 4, (size_t)n * 8, (size_t)n * 4};
+  const size_t plan_bytes = rt_plan_layout(part, out->plan_off);
   rc = b.plan.ensure(plan_bytes);
   if (rc != RT_OK) return rc;
   // ---- phase 2: the new blob

@@ -14,10 +14,8 @@
 int rt_scene_upload_plan(rt_scene* s, const RtPackedScene& pk) {
   s->plan = pk.plan;
   const std::vector<uint32_t>* parts[4] = {&s->plan.height_nodes, &s->plan.thr_src, &s->plan.recv_cell, &s->plan.tri_slot};
-  size_t bytes = 0;
-  for (int k = 0; k < 4; k++) s->plan_off[k] = bytes, bytes += (parts[k]->size() * 4 + 255) / 256 * 256;
-  s->plan_off[4] = bytes, bytes += 256;
-  int rc = s->plan_dev.ensure(bytes);
+  const size_t part_bytes[4] = {parts[0]->size() * 4, parts[1]->size() * 4, parts[2]->size() * 4, parts[3]->size() * 4};
+  int rc = s->plan_dev.ensure(rt_plan_layout(part_bytes, s->plan_off));
   if (rc != RT_OK) return rc;
   for (int k = 0; k < 4; k++)
     if (!parts[k]->empty()) HIP_TRY(hipMemcpy((char*)s->plan_dev.p + s->plan_off[k], parts[k]->data(), parts[k]->size() * 4, hipMemcpyHostToDevice));
@@ -83,8 +81,8 @@ int update_impl(rt_scene* s, const rt_scene_delta* host, rt_scene_delta dev, hip
   }
   if (!s->upd_back) HIP_TRY(hipHostMalloc((void**)&s->upd_back, 32, hipHostMallocDefault));
   EventPair ev;
-  HIP_TRY(hipEventCreate(&ev.e0));
-  HIP_TRY(hipEventCreate(&ev.e1));
+  const int rc_ev = ev.create();
+  if (rc_ev != RT_OK) return rc_ev;
   HIP_TRY(hipEventRecord(ev.e0, stream));
   if (host) {  // one pinned buffer, one copy; the groups follow one another, each on a multiple of 16 bytes
     Group g[8];
@@ -191,8 +189,8 @@ int rt_scene_bvh_quality(rt_scene* s, rt_bvh_quality* out) {
   } q;
   HIP_TRY(hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking));
   EventPair ev;
-  HIP_TRY(hipEventCreate(&ev.e0));
-  HIP_TRY(hipEventCreate(&ev.e1));
+  const int rc = ev.create();
+  if (rc != RT_OK) return rc;
   HIP_TRY(hipEventRecord(ev.e0, q.st));
   unsigned long long* dev = (unsigned long long*)s->sah_dev.p;
   const hipError_t e = (hipError_t)rt_launch_sah((const RtNode*)((const char*)s->blob.p + s->dev.off_nodes), s->dev.n_nodes, dev, q.st);

@@ -28,8 +28,7 @@ struct rt_view {
   int32_t* id = nullptr;
   rt_ray_order* order = nullptr;  // capacity n_rays; none with RT_VIEW_ORDER_NONE
   bool order_built = false;
-  hipEvent_t done_ev = nullptr;  // behind the last work enqueued for this view
-  bool pending = false;
+  RtPending done;                // behind the last work enqueued for this view
   hipEvent_t ev[5] = {};         // host form: before / after the generator, after the order, before / after the resolve
   double rays_ms = 0.0, order_ms = 0.0, resolve_ms = 0.0;
 };
@@ -77,16 +76,16 @@ namespace {
 
 int view_alloc(rt_view* v) {
   const size_t n = v->n_rays;
-  const size_t b3 = rt_pad256(n * 12), b1 = rt_pad256(n * 4), bv = rt_pad256(n), tab = rt_pad256(sizeof(v->distinct)), po = rt_pad256(sizeof(v->plane_of));
-  int rc = v->buf.ensure(3 * b3 + 2 * b1 + bv + tab + po);
+  RtArena lay;
+  lay.add(n * 12, &v->origin), lay.add(n * 12, &v->direction), lay.add(n * 12, &v->rgb);
+  lay.add(n * 4, &v->id), lay.add(n * 4, &v->t), lay.add(n, &v->valid);
+  lay.add(sizeof(v->distinct), &v->distinct_dev), lay.add(sizeof(v->plane_of), &v->plane_of_dev);
+  int rc = v->buf.ensure(lay.total());
   if (rc != RT_OK) return rc;
-  char* p = (char*)v->buf.p;
-  v->origin = (float*)p, v->direction = (float*)(p + b3), v->rgb = (float*)(p + 2 * b3);
-  v->id = (int32_t*)(p + 3 * b3), v->t = (float*)(p + 3 * b3 + b1), v->valid = (uint8_t*)(p + 3 * b3 + 2 * b1);
-  v->distinct_dev = (float*)(p + 3 * b3 + 2 * b1 + bv), v->plane_of_dev = (uint8_t*)(p + 3 * b3 + 2 * b1 + bv + tab);
+  lay.bind(v->buf.p);
   HIP_TRY(hipMemcpy(v->distinct_dev, v->distinct, sizeof(v->distinct), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(v->plane_of_dev, v->plane_of, sizeof(v->plane_of), hipMemcpyHostToDevice));
-  HIP_TRY(hipEventCreate(&v->done_ev));
+  if ((rc = v->done.create()) != RT_OK) return rc;
   for (hipEvent_t& e : v->ev) HIP_TRY(hipEventCreate(&e));
   if (v->order_mode != RT_VIEW_ORDER_NONE) {
     rt_ray_order_desc od{};
@@ -96,30 +95,15 @@ int view_alloc(rt_view* v) {
   return RT_OK;
 }
 
-int view_wait(rt_view* v) {
-  if (v->pending) {
-    HIP_TRY(hipEventSynchronize(v->done_ev));
-    v->pending = false;
-  }
-  return RT_OK;
-}
-
 void view_free(rt_view* v) {
   if (!v) return;
   (void)hipSetDevice(v->device);
-  if (v->pending) (void)hipEventSynchronize(v->done_ev);
+  v->done.destroy();
   rt_ray_order_destroy(v->order);
-  if (v->done_ev) (void)hipEventDestroy(v->done_ev);
   for (hipEvent_t e : v->ev)
     if (e) (void)hipEventDestroy(e);
   v->buf.release();
   delete v;
-}
-
-int view_mark(rt_view* v, hipStream_t stream) {
-  HIP_TRY(hipEventRecord(v->done_ev, stream));
-  v->pending = true;
-  return RT_OK;
 }
 
 int rays_enqueue(rt_view* v, float* origin, float* direction, hipStream_t stream) {
@@ -170,7 +154,7 @@ int render_enqueue(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_rad
   if (e != hipSuccess) return fail(RT_ERR_HIP, "view resolve launch failed: %s", hipGetErrorString(e));
   if (timed) HIP_TRY(hipEventRecord(v->ev[4], stream));
   if (timed) v->order_ms = build ? -1.0 : 0.0;  // (-1: read from the events once the stream has drained)
-  return view_mark(v, stream);
+  return v->done.mark(stream);
 }
 
 }  // namespace
@@ -182,10 +166,7 @@ int rt_view_create(const rt_view_desc* d, int device, rt_view** out) {
   *out = nullptr;
   int rc = rt_view_check_desc(d, "rt_view_create");
   if (rc != RT_OK) return rc;
-  const int ndev = rt_device_count();
-  if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
-  HIP_TRY(hipSetDevice(device));
+  if ((rc = rt_open_device(device)) != RT_OK) return rc;
   rt_view* v = new rt_view();
   v->device = device, v->width = d->width, v->height = d->height, v->n_pixels = d->width * d->height, v->n_samples = d->n_samples;
   v->order_mode = d->order;
@@ -217,7 +198,7 @@ int rt_view_rays_device(rt_view* v, float* origin, float* direction, void* hip_s
   if (!v->has_camera) return fail(RT_ERR_INVALID_ARG, "%s: the view has no camera yet (rt_view_set_camera)", fn);
   HIP_TRY(hipSetDevice(v->device));
   const int rc = rays_enqueue(v, origin, direction, (hipStream_t)hip_stream);
-  return rc != RT_OK ? rc : view_mark(v, (hipStream_t)hip_stream);
+  return rc != RT_OK ? rc : v->done.mark((hipStream_t)hip_stream);
 }
 
 int rt_view_rays(rt_view* v, float* origin, float* direction) {
@@ -246,23 +227,17 @@ int rt_render_view(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_rad
   if (rc != RT_OK) return rc;
   if (stats) memset(stats, 0, sizeof(*stats));
   HIP_TRY(hipSetDevice(s->device));
-  if ((rc = view_wait(v)) != RT_OK) return rc;
+  if ((rc = v->done.wait()) != RT_OK) return rc;
   const auto t_begin = std::chrono::steady_clock::now();
   const size_t n = v->n_pixels;
   rt_ray_radiance dev = *out;
   HostCall c;
   c.out(&dev.rgb, n * 12), c.out(&dev.valid, n), c.out(&dev.id, n * 4), c.out(&dev.t, n * 4), c.out(&dev.argb, n * 4, true);
-  struct Forget {  // (as rt_trace_rays: the scene must not remember a stream that is gone)
-    rt_scene* scene;
-    HostCall& c;
-    ~Forget() {
-      if (c.stream) (void)hipStreamSynchronize(c.stream), rt_scene_forget_stream(scene, c.stream);
-    }
-  } forget{s, c};
+  Forget forget{s, c};
   if ((rc = c.begin()) != RT_OK) return rc;
   if ((rc = render_enqueue(s, v, p, &dev, c.stream, true)) != RT_OK) return rc;
   if ((rc = c.finish()) != RT_OK) return rc;
-  v->pending = false;
+  v->done.clear();
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, v->ev[0], v->ev[1]));
   v->rays_ms = ms;
@@ -284,7 +259,7 @@ int rt_render_view(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_rad
 int rt_view_read(rt_view* v, uint8_t* plane_of, rt_view_info* info) {
   if (!v) return fail(RT_ERR_INVALID_ARG, "rt_view_read: null view");
   HIP_TRY(hipSetDevice(v->device));
-  const int rc = view_wait(v);
+  const int rc = v->done.wait();
   if (rc != RT_OK) return rc;
   if (plane_of) memcpy(plane_of, v->plane_of, v->n_samples);
   if (info) {
