@@ -1674,6 +1674,75 @@ __device__ __forceinline__ void hard_push(const RtDevParams& P, lanemask m, V3 p
   P.hard_q[3 * stride + i] = make_float4(Wa.x, Wa.y, Wa.z, __uint_as_float(mult));
 }
 
+// The children of a Whitted node: calculate_reflection (raytracer_renderer.rs:526-729) and calculate_refractions (:279-524), appended
+// to the ray queue.  W0 = the node's weight with a reflection child's
+// own atten(t) already in it (:722-726); every lane of the wavefront calls this (idle lanes: hit = false).
+__device__ __forceinline__ void spawn_children(const RtDevScene& sc, const RtDevParams& P, bool hit, V3 d, const Surf& sf, const Mat& m, V3 W0,
+                                               float n_start, int depth, uint32_t pix, uint32_t mult) {
+  const V3 epsv = mk(P.eps_distance, P.eps_distance, P.eps_distance);
+  const bool T = m.transmissive;
+  {
+    bool spawn = false;
+    V3 co = mk(0, 0, 0), cd = mk(0, 0, 1), cW = mk(0, 0, 0);
+    int cdepth = 0;
+    const bool R = (m.metallic > 0.0f) || T;
+    if (hit && (P.flags & RT_FLAG_REFLECTIONS) && R) {
+      float cos_theta = dot(d, sf.n);
+      bool inside = cos_theta < 0.0f;
+      V3 inormal = inside ? -sf.n : sf.n;
+      float n2 = inside ? m.ior : P.air_ior;
+      float eta = inside ? (n2 / n_start) : (n_start / n2);
+      float cos_i = fabsf(cos_theta);
+      float sin2 = eta * eta * (1.0f - cos_i * cos_i);
+      bool tir = sin2 >= 1.0f;
+      bool reflective = (m.metallic > 0.0f) || (T && tir);
+      cdepth = depth < 0 ? (int)P.max_depth_reflection : (depth > 0 ? depth - 1 : 0);
+      if (reflective && cdepth > 0) {
+        V3 rr = normalize(reflected(d, sf.n));
+        V3 Rf = fresnel_reflectance(m, inormal, -d, n_start);
+        spawn = true;
+        co = sf.p + rr * epsv;
+        cd = rr;
+        cW = W0 * Rf;
+      }
+    }
+    queue_push(P, spawn, co, cd, n_start, cW, cdepth, KIND_REFL, pix, mult);
+  }
+  {
+    bool spawn = false;
+    V3 co = mk(0, 0, 0), cd = mk(0, 0, 1), cW = mk(0, 0, 0);
+    int cdepth = 0;
+    float cior = 0.0f;
+    if (hit && (P.flags & RT_FLAG_REFRACTIONS) && T) {
+      float cos_theta = dot(d, sf.n);
+      bool inside = cos_theta <= 0.0f;
+      V3 inormal = inside ? -sf.n : sf.n;
+      float n2 = inside ? m.ior : P.air_ior;
+      float eta = inside ? (n2 / n_start) : (n_start / n2);
+      float inv_eta = 1.0f / eta;
+      V3 Rf = fresnel_reflectance(m, inormal, d, inv_eta);
+      V3 Tr = mk(1.0f - Rf.x, 1.0f - Rf.y, 1.0f - Rf.z);
+      V3 nn = -inormal;  // ultraviolet refracted(n = -inormal, eta = 1/eta)
+      float ndi = dot(nn, d);
+      float kk = 1.0f - inv_eta * inv_eta * (1.0f - ndi * ndi);
+      float op = m.opacity;
+      int step = (op < 0.5f) ? 2 : 1;
+      int fac = (op <= 0.3f) ? 3 : ((op < 0.5f) ? 2 : 1);
+      cdepth = depth < 0 ? (int)P.max_depth_refraction / fac : (depth > step ? depth - step : 0);
+      if (!(kk < 0.0f) && cdepth > 0) {  // kk < 0: zero vector -> NaN direction -> miss (deviation D2)
+        float sq = inv_eta * ndi + __builtin_sqrtf(kk);
+        V3 q = normalize(d * inv_eta - nn * sq);
+        spawn = true;
+        co = sf.p + q * epsv;
+        cd = q;
+        cW = (W0 * (m.boost + 1.0f)) * Tr;
+        cior = n2;
+      }
+    }
+    queue_push(P, spawn, co, cd, cior, cW, cdepth, KIND_REFR, pix, mult);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // trace + shade one ray per lane (wave-cooperative traversal inside); children go to the queue
 // ------------------------------------------------------------------------------------------------
@@ -1686,6 +1755,129 @@ __device__ __forceinline__ void hard_push(const RtDevParams& P, lanemask m, V3 p
 #define RT_NO_CELL 0xFFFFFFFFu
 #define RT_MAT_TRANS_BIT 0x80000000u  /* stash field 6: material row | this bit when the material is transmissive */
 __device__ __forceinline__ long long* stash_fix(float* stash) { return (long long*)(stash + RT_STASH_FIX * 256u); }
+
+// ---- rules that process_ray below, the phase kernels (rt_phases.h) and rt_hard_kernel share: one copy each, because the
+// forms are held to bit-equal frames ---------------------------------------------------------------------------------------
+
+// a colour term in the pixel accumulator's fixed point
+struct Fix3 {
+  long long x, y, z;
+};
+__device__ __forceinline__ Fix3 to_fixed(V3 c) {
+  Fix3 f;
+  f.x = __float2ll_rn(c.x * RT_ACC_SCALE);
+  f.y = __float2ll_rn(c.y * RT_ACC_SCALE);
+  f.z = __float2ll_rn(c.z * RT_ACC_SCALE);
+  return f;
+}
+
+// "nothing known yet" about a (wavefront, light) set: no shared list (one BVH walk per sample), every sphere, no umbra
+__device__ __forceinline__ CandList cand_unknown() {
+  CandList cand;
+  cand.reg = 0;
+  cand.count = RT_CAND_OVERFLOW;
+  cand.spheres = 0xFFFFFFFFu;
+  cand.umbra = 0ull;
+  return cand;
+}
+
+// Receiver cell of the hit point p of primitive `id` and the cell's flags (bit l: no triangle can shadow it for light l,
+// bit 8 + l: no sphere), for the lanes with `on`; RT_NO_CELL / 0 where there is none.
+__device__ __forceinline__ void receiver_cell(const RtDevScene& sc, const RtDevParams& P, bool on, int id, V3 p, uint32_t& cell, uint32_t& rflags) {
+  if (on && id >= (int)sc.n_spheres) {
+    const uint32_t ro = sc.off_recv + (uint32_t)(id - (int)sc.n_spheres) * 48u;
+    const float4 ru = vload<float4>(sc, ro), rv = vload<float4>(sc, ro + 16u);
+    const uint2 rr = vload<uint2>(sc, ro + 32u);  // {R, first cell}
+    const float Rf = (float)rr.x;
+    const float cu = (__builtin_fmaf(ru.x, p.x, __builtin_fmaf(ru.y, p.y, ru.z * p.z)) + ru.w) * Rf;
+    const float cv = (__builtin_fmaf(rv.x, p.x, __builtin_fmaf(rv.y, p.y, rv.z * p.z)) + rv.w) * Rf;
+    const uint32_t ci = (uint32_t)fminf(fmaxf(cu, 0.0f), Rf - 1.0f), cj = (uint32_t)fminf(fmaxf(cv, 0.0f), Rf - 1.0f);
+    // (cells beyond the hypotenuse carry no flags; the cells are computed 5 % larger than they are, which covers the
+    // rounding of u and v)
+    if (rr.x != 0u && ci + cj < rr.x) cell = rr.y + ci + rr.x * cj, rflags = P.recv_flags[cell];
+  } else if (on && id >= 0) {
+    // a sphere: the cell of the direction centre -> p in the sphere's cube map (face = largest component)
+    const uint2 sr = vload<uint2>(sc, sc.off_srecv + (uint32_t)id * 8u);  // {Rs, first cell}
+    const float4 sp = vload<float4>(sc, sc.off_spheres + (uint32_t)id * 16u);
+    const V3 dd = p - mk(sp.x, sp.y, sp.z);
+    const float ax = fabsf(dd.x), ay = fabsf(dd.y), az = fabsf(dd.z);
+    const bool mx = ax >= ay && ax >= az, my = !mx && ay >= az;
+    const float dm = mx ? dd.x : (my ? dd.y : dd.z), du = mx ? dd.y : (my ? dd.z : dd.x), dv = mx ? dd.z : (my ? dd.x : dd.y);
+    const uint32_t face = (mx ? 0u : (my ? 2u : 4u)) + (dm < 0.0f ? 1u : 0u);
+    const float inv = __builtin_amdgcn_rcpf(fmaxf(fabsf(dm), 1e-30f)), Rf = (float)sr.x;
+    const uint32_t ci = (uint32_t)fminf(fmaxf((__builtin_fmaf(du, inv, 1.0f)) * 0.5f * Rf, 0.0f), Rf - 1.0f);
+    const uint32_t cj = (uint32_t)fminf(fmaxf((__builtin_fmaf(dv, inv, 1.0f)) * 0.5f * Rf, 0.0f), Rf - 1.0f);
+    if (sr.x != 0u) cell = sr.y + (face * sr.x + cj) * sr.x + ci, rflags = P.recv_flags[cell];
+  }
+}
+
+// Per-cell candidate lists: when every lane in use sits in a receiver cell whose list for this light is complete, their
+// union replaces the BVH walk (typically one to three distinct cells per wavefront: lanes of one cell share a list).
+// lst = the lane's list of its `cell` for the light (all ones on lanes not in use or without a cell); returns whether the
+// union stands, lane i of pre_reg = its i-th slot.
+__device__ __forceinline__ bool union_cell_lists(lanemask use_m, uint32_t cell, uint4 lst, uint32_t& pre_reg, uint32_t& pre_count) {
+  const lanemask unusable = use_m & (wave_ballot(cell == RT_NO_CELL) | wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_OVERFLOW));
+  if (unusable) return false;
+  const uint32_t lane_id = threadIdx.x & 63u;
+  for (lanemask todo = use_m & ~wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_END); todo;) {
+    const int fl = __ffsll((long long)todo) - 1;
+    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cell, fl);
+    auto add_slot = [&](uint32_t slot) {  // (uniform)
+      if (slot >= RT_CELL_LIST_OVERFLOW) return;  // end marker
+      const lanemask filled = pre_count >= 64u ? ~0ull : ((1ull << pre_count) - 1ull);
+      if (wave_ballot(pre_reg == slot) & filled) return;  // another cell listed it already
+      lane_put(pre_reg, pre_count, slot, lane_id);
+      pre_count++;
+    };
+    auto add_pair = [&](uint32_t v) {
+      const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)v, fl);
+      add_slot(w & 0xFFFFu);
+      add_slot(w >> 16);
+    };
+    add_pair(lst.x), add_pair(lst.y), add_pair(lst.z), add_pair(lst.w);
+    todo &= ~wave_ballot(cell == c);
+  }
+  return pre_count <= 64u;  // (more than a VGPR's worth of lanes: walk)
+}
+
+// first hit point of the wavefront and how far the others are from it (sphere pre-selection of the candidate collection)
+__device__ __forceinline__ void wave_spread(bool hit, lanemask hit_m, V3 p, V3& p_first, float& p_spread) {
+  const int fl = __ffsll((long long)hit_m) - 1;
+  p_first = mk(__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(p.x), fl)),
+               __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(p.y), fl)),
+               __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(p.z), fl)));
+  const V3 dp = p - p_first;
+  float m = hit ? (fabsf(dp.x) + fabsf(dp.y) + fabsf(dp.z)) : 0.0f;  // 1-norm >= distance
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  p_spread = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(m))) * 1.000001f;
+}
+
+// The cloud set of (pixel, light) -- N sample offsets, light.rs:218; the table holds offset * (fw, fh, fd) -- and the
+// intensity of one of its samples.  POW2: the table is known to be a power of two (the default 1024), which needs no
+// integer division: ~25 vector instructions per light.
+template <bool POW2>
+__device__ __forceinline__ const float4* cloud_set(const RtDevParams& P, uint32_t pix, uint32_t l, uint32_t N, float intensity, float& lI) {
+  const uint32_t hsh = rt_cloud_hash(P.cloud_seed, pix, l);
+  const uint32_t set = (POW2 || (P.n_cloud_sets & (P.n_cloud_sets - 1u)) == 0u) ? (hsh & (P.n_cloud_sets - 1u)) : (hsh % P.n_cloud_sets);
+  lI = (1.0f / (float)N) * intensity;
+  return P.cloud_sets + (size_t)set * N;
+}
+
+// the shadow ray from p towards the light sample at lp (raytracer_renderer.rs:770-790)
+struct ShadowGeom {
+  V3 ltp, ld, so;
+  float tmax;
+};
+__device__ __forceinline__ ShadowGeom shadow_geom(V3 lp, V3 p, V3 epsv) {
+  ShadowGeom g;
+  g.ltp = lp - p;
+  g.ld = g.ltp * exact_rcp(mag(g.ltp));  // normalize(ltp): the shadow ray's geometry is exact
+  g.so = p + g.ld * epsv;
+  g.tmax = mag(lp - g.so);
+  return g;
+}
+
 // PRE: the nearest hit was found by rt_trace_kernel and is passed in (`pre`); otherwise it is traced here.
 // STREAM: secondary rays exist (reflections / refractions): children are queued, pixel sums go through the fixed-point
 // accumulator, hard soft-shadow pairs are deferred.  The frames without them (configs 1-3) run a kernel that does not
@@ -1777,6 +1969,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       const V3 q = (r.o - mk(P.morton_lo[0], P.morton_lo[1], P.morton_lo[2])) * mk(P.morton_scale[0], P.morton_scale[1], P.morton_scale[2]);
       on_cell = hit && fminf(fminf(q.x, q.y), q.z) >= -1024.0f && fmaxf(fmaxf(q.x, q.y), q.z) <= 2048.0f;
     }
+    // (mirrors receiver_cell: calling it changes the benchmark-path kernels, profiles/shared_rules.md)
     if ((C::TABLES != CFG_TABLES_RUNTIME || P.recv_flags) && on_cell && h.id >= (int)sc.n_spheres) {
       const uint32_t ro = sc.off_recv + (uint32_t)(h.id - (int)sc.n_spheres) * 48u;
       const float4 ru = vload<float4>(sc, ro), rv = vload<float4>(sc, ro + 16u);
@@ -1814,17 +2007,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
   // first hit point of the wavefront and how far the others are from it (sphere pre-selection of the candidate collection)
   V3 p_first = mk(0, 0, 0);
   float p_spread = 0.0f;
-  if (N > 1 && sc.n_spheres) {
-    const int fl = __ffsll((long long)hit_m) - 1;
-    p_first = mk(__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(sf.p.x), fl)),
-                 __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(sf.p.y), fl)),
-                 __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(sf.p.z), fl)));
-    const V3 dp = sf.p - p_first;
-    float m = hit ? (fabsf(dp.x) + fabsf(dp.y) + fabsf(dp.z)) : 0.0f;  // 1-norm >= distance
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    p_spread = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(m))) * 1.000001f;
-  }
+  if (N > 1 && sc.n_spheres) wave_spread(hit, hit_m, sf.p, p_first, p_spread);
   // every hit point casts lights x N shadow rays in the reference (raytracer.rs:24); counted here once, whatever
   // part of them the classifications below resolve without a traversal
   wv.cnt_shadow += sc.n_lights * N * (P.weighted ? wave_sum(hit ? r.mult : 0u) : (uint32_t)__popcll(hit_m));
@@ -1840,17 +2023,13 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     if (N > 1) {
       uint32_t tix = threadIdx.x;
       RT_OPAQUE(tix);  // a real LDS read per light instead of a register held through the loop
-      const uint32_t pixel = __float_as_uint(stash[9u * 256u + tix]);
-      const uint32_t hsh = rt_cloud_hash(P.cloud_seed, pixel, l);
-      // (a power-of-two table -- the default 1024 -- needs no integer division: ~25 vector instructions per light)
-      const uint32_t set = (C::POW2_SETS || (P.n_cloud_sets & (P.n_cloud_sets - 1u)) == 0u) ? (hsh & (P.n_cloud_sets - 1u)) : (hsh % P.n_cloud_sets);
-      cs = P.cloud_sets + (size_t)set * N;
-      lI = (1.0f / (float)N) * L0.w;
+      cs = cloud_set<C::POW2_SETS>(P, __float_as_uint(stash[9u * 256u + tix]), l, N, L0.w, lI);
     }
     // Lights below the horizon of the hit point: the contribution is gated by diff = max(n.ld, 0) > 0
     // (light.rs / :800-802), so a lane whose every sample direction has n.ld_j <= 0 adds nothing for this
     // light whatever its shadow rays would find -- they are not traced (they still count in rays_shadow).
     // n.D_j <= n.dc + delta |n|_1 over the cloud; the margin covers the fp32 rounding of n.ld_j.
+    // (classify_wave, rt_phases.h, holds the second copy of this test: no shared form kept both kernel groups as they compile now)
     bool use = hit;
     {
       const float dl = (N > 1) ? P.cloud_delta : 0.0f;
@@ -1864,11 +2043,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     if (!use_m) {
       continue;
     }
-    CandList cand;
-    cand.reg = 0;
-    cand.count = RT_CAND_OVERFLOW;
-    cand.spheres = 0xFFFFFFFFu;
-    cand.umbra = 0ull;
+    CandList cand = cand_unknown();
 #if RT_PROFILE == 4
     uint32_t prof_walked = 0, prof_listed = 0, prof_pre = 0;
 #endif
@@ -1896,6 +2071,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
         const uint32_t cidx = __float_as_uint(stash[RT_STASH_CELL * 256u + tix]);
         uint4 lst = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
         if (use && cidx != RT_NO_CELL) lst = P.cell_lists[(size_t)cidx * sc.n_lights + l];
+        // (mirrors union_cell_lists: calling it changes the benchmark-path kernels, profiles/shared_rules.md)
         const lanemask unusable = use_m & (wave_ballot(cidx == RT_NO_CELL) | wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_OVERFLOW));
         if (!unusable) {
           have_pre = true;
@@ -2067,7 +2243,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
     // are unconditional: no exec-mask bracket and no register shuffle between the current and the next offsets)
     float4 cnext = make_float4(0, 0, 0, 0);
     if (N > 1 && (!STREAM || use)) cnext = cs[0];
-    auto light_position = [&](uint32_t j) {
+    auto light_position = [&](uint32_t j) {  // (set_samples, rt_phases.h, holds a copy of the STREAM form)
       V3 lp = mk(L0.x, L0.y, L0.z);
       if (N > 1) {
         lp.x = L0.x + cnext.x;  // light.rs:218; the table holds offset * (fw, fh, fd)
@@ -2104,11 +2280,9 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
 #if RT_PROFILE
           W.t_mark = PROF_T();
 #endif
-          const V3 lp = light_position(j);
-          const V3 ltp = lp - sf.p;
-          const V3 ld = ltp * exact_rcp(mag(ltp));  // normalize(ltp): the shadow ray's geometry is exact
-          const V3 so = sf.p + ld * epsv;
-          const float tmax = mag(lp - so);
+          const ShadowGeom g = shadow_geom(light_position(j), sf.p, epsv);
+          const V3 ltp = g.ltp, ld = g.ld, so = g.so;
+          const float tmax = g.tmax;
           const Shadow S = shadow_ray<CULL, decltype(list_tag)::value, C>(sc, P, W, use_m, so, ld, tmax, cand, memo);
           const lanemask reach_m = use_m & ~S.occ;
 #if RT_PROFILE == 3
@@ -2137,11 +2311,11 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
       const float a0 = st[3 * 256];
       const V3 Wa = mk(st[0 * 256] * a0, st[1 * 256] * a0, st[2 * 256] * a0);
       const bool Tm = (__float_as_uint(st[6 * 256]) & RT_MAT_TRANS_BIT) != 0u;
-      const V3 c = Wa * (Tm ? ds : (dl + ds));
+      const Fix3 f = to_fixed(Wa * (Tm ? ds : (dl + ds)));
       long long* fx = stash_fix(stash) + tix;
-      fx[0] += __float2ll_rn(c.x * RT_ACC_SCALE);
-      fx[256] += __float2ll_rn(c.y * RT_ACC_SCALE);
-      fx[512] += __float2ll_rn(c.z * RT_ACC_SCALE);
+      fx[0] += f.x;
+      fx[256] += f.y;
+      fx[512] += f.z;
     }
 #if RT_PROFILE == 3  // outcome of the (wavefront, light) sets that had something to test
     if (!nothing && set_tot) {
@@ -2188,13 +2362,13 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
   if (STREAM) {
     // the lights' shares are already in the fixed-point sums; the ambient term (part of `direct`) joins them
     if (hit && !T) {
-      const V3 c = mk(Wt.x * a, Wt.y * a, Wt.z * a) * ambient;
+      const Fix3 f = to_fixed(mk(Wt.x * a, Wt.y * a, Wt.z * a) * ambient);
       uint32_t tix = threadIdx.x;
       RT_OPAQUE(tix);
       long long* fx = stash_fix(stash) + tix;
-      fx[0] += __float2ll_rn(c.x * RT_ACC_SCALE);
-      fx[256] += __float2ll_rn(c.y * RT_ACC_SCALE);
-      fx[512] += __float2ll_rn(c.z * RT_ACC_SCALE);
+      fx[0] += f.x;
+      fx[256] += f.y;
+      fx[512] += f.z;
     }
   } else if (hit) {
     V3 direct = (ambient + light_color) * a;  // :206-209
@@ -2204,69 +2378,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
   }
   if (!stream) return out;
 
-  // ---- calculate_reflection, :526-729 -------------------------------------------------------------
-  {
-    bool spawn = false;
-    V3 co = mk(0, 0, 0), cd = mk(0, 0, 1), cW = mk(0, 0, 0);
-    int cdepth = 0;
-    const bool R = (m.metallic > 0.0f) || T;
-    if (hit && (P1.flags & RT_FLAG_REFLECTIONS) && R) {
-      float cos_theta = dot(d, sf.n);
-      bool inside = cos_theta < 0.0f;
-      V3 inormal = inside ? -sf.n : sf.n;
-      float n2 = inside ? m.ior : P1.air_ior;
-      float eta = inside ? (n2 / n_start) : (n_start / n2);
-      float cos_i = fabsf(cos_theta);
-      float sin2 = eta * eta * (1.0f - cos_i * cos_i);
-      bool tir = sin2 >= 1.0f;
-      bool reflective = (m.metallic > 0.0f) || (T && tir);
-      cdepth = depth < 0 ? (int)P1.max_depth_reflection : (depth > 0 ? depth - 1 : 0);
-      if (reflective && cdepth > 0) {
-        V3 rr = normalize(reflected(d, sf.n));
-        V3 Rf = fresnel_reflectance(m, inormal, -d, n_start);
-        spawn = true;
-        co = sf.p + rr * epsv;
-        cd = rr;
-        cW = Wt * Rf;
-      }
-    }
-    queue_push(P1, spawn, co, cd, n_start, cW, cdepth, KIND_REFL, pixel, out.mult);
-  }
-  // ---- calculate_refractions, :279-524 --------------------------------------------------------------
-  {
-    bool spawn = false;
-    V3 co = mk(0, 0, 0), cd = mk(0, 0, 1), cW = mk(0, 0, 0);
-    int cdepth = 0;
-    float cior = 0.0f;
-    if (hit && (P1.flags & RT_FLAG_REFRACTIONS) && T) {
-      float cos_theta = dot(d, sf.n);
-      bool inside = cos_theta <= 0.0f;
-      V3 inormal = inside ? -sf.n : sf.n;
-      float n2 = inside ? m.ior : P1.air_ior;
-      float eta = inside ? (n2 / n_start) : (n_start / n2);
-      float inv_eta = 1.0f / eta;
-      V3 Rf = fresnel_reflectance(m, inormal, d, inv_eta);
-      V3 Tr = mk(1.0f - Rf.x, 1.0f - Rf.y, 1.0f - Rf.z);
-      // ultraviolet refracted(n = -inormal, eta = 1/eta)
-      V3 nn = -inormal;
-      float ndi = dot(nn, d);
-      float kk = 1.0f - inv_eta * inv_eta * (1.0f - ndi * ndi);
-      float op = m.opacity;
-      int step = (op < 0.5f) ? 2 : 1;
-      int fac = (op <= 0.3f) ? 3 : ((op < 0.5f) ? 2 : 1);
-      cdepth = depth < 0 ? (int)P1.max_depth_refraction / fac : (depth > step ? depth - step : 0);
-      if (!(kk < 0.0f) && cdepth > 0) {  // kk < 0: zero vector -> NaN direction -> miss (deviation D2)
-        float s = inv_eta * ndi + __builtin_sqrtf(kk);
-        V3 q = normalize(d * inv_eta - nn * s);
-        spawn = true;
-        co = sf.p + q * epsv;
-        cd = q;
-        cW = (Wt * (m.boost + 1.0f)) * Tr;
-        cior = n2;
-      }
-    }
-    queue_push(P1, spawn, co, cd, cior, cW, cdepth, KIND_REFR, pixel, out.mult);
-  }
+  spawn_children(sc1, P1, hit, d, sf, m, Wt, n_start, depth, pixel, out.mult);
   return out;
 }
 
@@ -2284,9 +2396,10 @@ __device__ __forceinline__ uint32_t pack_argb(V3 c) {
 // `mult` identical rays of the reference add `mult` identical fixed-point terms: exact in the integer domain
 __device__ __forceinline__ void acc_add(const RtDevParams& P, uint32_t pix, V3 c, uint32_t mult) {
   long long* a = P.acc + 4 * (size_t)pix;
-  atomicAdd((unsigned long long*)&a[0], (unsigned long long)(__float2ll_rn(c.x * RT_ACC_SCALE) * (long long)mult));
-  atomicAdd((unsigned long long*)&a[1], (unsigned long long)(__float2ll_rn(c.y * RT_ACC_SCALE) * (long long)mult));
-  atomicAdd((unsigned long long*)&a[2], (unsigned long long)(__float2ll_rn(c.z * RT_ACC_SCALE) * (long long)mult));
+  const Fix3 f = to_fixed(c);
+  atomicAdd((unsigned long long*)&a[0], (unsigned long long)(f.x * (long long)mult));
+  atomicAdd((unsigned long long*)&a[1], (unsigned long long)(f.y * (long long)mult));
+  atomicAdd((unsigned long long*)&a[2], (unsigned long long)(f.z * (long long)mult));
 }
 
 __device__ __forceinline__ void acc_add_fixed(const RtDevParams& P, uint32_t pix, long long x, long long y, long long z, uint32_t mult) {
@@ -2321,6 +2434,8 @@ __device__ __forceinline__ void primary_body(const RtDevScene& sc, const RtDevPa
   const bool aa = (P.flags & RT_FLAG_ANTI_ALIASING) && P.aa_rays > 0;
   const uint32_t n_samples = aa ? P.aa_rays : 1u;  // samples of the reference's per-pixel sum
   const uint32_t n_thr = aa ? P.aa_unique : 1u;    // threads per pixel (distinct samples)
+  // (map_item and primary_ray, rt_phases.h, mirror this mapping and the ray set-up below: no shared form kept both kernel groups
+  // as they compile now, profiles/shared_rules.md)
   // thread -> (pixel, AA sample): workgroup -> 16x16 super-tile (through the list of super-tiles this rank
   // owns, if any) -> 4x4 tile -> pixel.  Evaluated twice (before the ray and again for the accumulation) so
   // that nothing of it has to survive the light loops in registers.
@@ -2595,76 +2710,7 @@ __global__ __launch_bounds__(256, RT_MIN_WAVES) void rt_primary_cost_kernel(RtDe
 // neighbouring surface points whatever pixel they belong to.  The image does not depend on the order
 // (integer pixel accumulation).
 // ------------------------------------------------------------------------------------------------
-// The children of a Whitted node: calculate_reflection (raytracer_renderer.rs:526-729) and calculate_refractions (:279-524), appended
-// to the ray queue (the same op sequence as the two blocks at the end of process_ray).  W0 = the node's weight with a reflection child's
-// own atten(t) already in it (:722-726); every lane of the wavefront calls this (idle lanes: hit = false).
-__device__ __forceinline__ void spawn_children(const RtDevScene& sc, const RtDevParams& P, bool hit, V3 d, const Surf& sf, const Mat& m, V3 W0,
-                                               float n_start, int depth, uint32_t pix, uint32_t mult) {
-  const V3 epsv = mk(P.eps_distance, P.eps_distance, P.eps_distance);
-  const bool T = m.transmissive;
-  {
-    bool spawn = false;
-    V3 co = mk(0, 0, 0), cd = mk(0, 0, 1), cW = mk(0, 0, 0);
-    int cdepth = 0;
-    const bool R = (m.metallic > 0.0f) || T;
-    if (hit && (P.flags & RT_FLAG_REFLECTIONS) && R) {
-      float cos_theta = dot(d, sf.n);
-      bool inside = cos_theta < 0.0f;
-      V3 inormal = inside ? -sf.n : sf.n;
-      float n2 = inside ? m.ior : P.air_ior;
-      float eta = inside ? (n2 / n_start) : (n_start / n2);
-      float cos_i = fabsf(cos_theta);
-      float sin2 = eta * eta * (1.0f - cos_i * cos_i);
-      bool tir = sin2 >= 1.0f;
-      bool reflective = (m.metallic > 0.0f) || (T && tir);
-      cdepth = depth < 0 ? (int)P.max_depth_reflection : (depth > 0 ? depth - 1 : 0);
-      if (reflective && cdepth > 0) {
-        V3 rr = normalize(reflected(d, sf.n));
-        V3 Rf = fresnel_reflectance(m, inormal, -d, n_start);
-        spawn = true;
-        co = sf.p + rr * epsv;
-        cd = rr;
-        cW = W0 * Rf;
-      }
-    }
-    queue_push(P, spawn, co, cd, n_start, cW, cdepth, KIND_REFL, pix, mult);
-  }
-  {
-    bool spawn = false;
-    V3 co = mk(0, 0, 0), cd = mk(0, 0, 1), cW = mk(0, 0, 0);
-    int cdepth = 0;
-    float cior = 0.0f;
-    if (hit && (P.flags & RT_FLAG_REFRACTIONS) && T) {
-      float cos_theta = dot(d, sf.n);
-      bool inside = cos_theta <= 0.0f;
-      V3 inormal = inside ? -sf.n : sf.n;
-      float n2 = inside ? m.ior : P.air_ior;
-      float eta = inside ? (n2 / n_start) : (n_start / n2);
-      float inv_eta = 1.0f / eta;
-      V3 Rf = fresnel_reflectance(m, inormal, d, inv_eta);
-      V3 Tr = mk(1.0f - Rf.x, 1.0f - Rf.y, 1.0f - Rf.z);
-      V3 nn = -inormal;  // ultraviolet refracted(n = -inormal, eta = 1/eta)
-      float ndi = dot(nn, d);
-      float kk = 1.0f - inv_eta * inv_eta * (1.0f - ndi * ndi);
-      float op = m.opacity;
-      int step = (op < 0.5f) ? 2 : 1;
-      int fac = (op <= 0.3f) ? 3 : ((op < 0.5f) ? 2 : 1);
-      cdepth = depth < 0 ? (int)P.max_depth_refraction / fac : (depth > step ? depth - step : 0);
-      if (!(kk < 0.0f) && cdepth > 0) {  // kk < 0: zero vector -> NaN direction -> miss (deviation D2)
-        float sq = inv_eta * ndi + __builtin_sqrtf(kk);
-        V3 q = normalize(d * inv_eta - nn * sq);
-        spawn = true;
-        co = sf.p + q * epsv;
-        cd = q;
-        cW = (W0 * (m.boost + 1.0f)) * Tr;
-        cior = n2;
-      }
-    }
-    queue_push(P, spawn, co, cd, cior, cW, cdepth, KIND_REFR, pix, mult);
-  }
-}
-
-// The same children, appended with ONE atomic per WORKGROUP (both kinds together) instead of two per wavefront: every queue slot comes
+// The children of spawn_children, appended with ONE atomic per WORKGROUP (both kinds together) instead of two per wavefront: every queue slot comes
 // from one counter, and returning atomics on one address retire at ~3 ns each whatever else the GPU does -- two per wavefront were
 // 6.9 M atomics = 20 ms of a 4K frame's trace launches (profiles/r04_phase_split.md, r04k).  Called by all 256 threads of the workgroup
 // the same number of times (two barriers); lds = 2 x 8 dwords, used alternately (`parity`) so that a wavefront that runs ahead into
@@ -3004,18 +3050,14 @@ __device__ __forceinline__ void hard_body(const RtDevScene& sc, const RtDevParam
   const Mat m = load_mat(sc, have ? __float_as_uint(r0.w) : 0u);
   const float4 L0 = vload<float4>(sc, sc.off_lights + l * 32u), L1 = vload<float4>(sc, sc.off_lights + l * 32u + 16u);
   const V3 lc = mk(L1.x, L1.y, L1.z);
-  // sample j of the pixel's cloud set of this light (light.rs:218; the table holds offset * (fw, fh, fd))
-  const uint32_t hsh = rt_cloud_hash(P.cloud_seed, pix, l);
-  const uint32_t set = (P.n_cloud_sets & (P.n_cloud_sets - 1u)) == 0u ? (hsh & (P.n_cloud_sets - 1u)) : (hsh % P.n_cloud_sets);
-  const float4 cs = have ? P.cloud_sets[(size_t)set * N + j] : make_float4(0, 0, 0, 0);
-  const float lI = (1.0f / (float)N) * L0.w;
-  // the shadow ray, exactly as the render kernels set it up (raytracer_renderer.rs:770-790)
-  const V3 lp = mk(L0.x + cs.x, L0.y + cs.y, L0.z + cs.z);
-  const V3 ltp = lp - p;
-  const V3 ld = ltp * exact_rcp(mag(ltp));
-  const V3 so = p + ld * mk(P.eps_distance, P.eps_distance, P.eps_distance);
-  const float tmax = mag(lp - so);
-  const V3 d = normalize_unit(ld, grp);
+  // sample j of the pixel's cloud set of this light, and its shadow ray
+  float lI;
+  const float4* set = cloud_set<false>(P, pix, l, N, L0.w, lI);
+  const float4 cs = have ? set[j] : make_float4(0, 0, 0, 0);
+  const ShadowGeom g = shadow_geom(mk(L0.x + cs.x, L0.y + cs.y, L0.z + cs.z), p, mk(P.eps_distance, P.eps_distance, P.eps_distance));
+  const V3 ltp = g.ltp, so = g.so;
+  const float tmax = g.tmax;
+  const V3 d = normalize_unit(g.ld, grp);
   Shadow S;
   shadow_init(S);
   for (uint32_t i = 0; i < sc.n_spheres; i++) {  // spheres: few, tested by the whole wavefront one by one

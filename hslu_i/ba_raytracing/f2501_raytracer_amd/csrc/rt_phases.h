@@ -324,7 +324,7 @@ __device__ __forceinline__ void set_samples(const RtDevScene& sc, const RtDevPar
   const V3 mmc_lc = m.color * (m.color * lc);
   const float4* cs = nullptr;
   float lI = L0v.w;
-  if (N > 1) {
+  if (N > 1) {  // (mirrors cloud_set: calling it here costs rt_sets0_list_kernel two VGPR spills, profiles/shared_rules.md)
     const uint32_t hsh = rt_cloud_hash(P.cloud_seed, it.pix, l);
     const uint32_t set = (P.n_cloud_sets & (P.n_cloud_sets - 1u)) == 0u ? (hsh & (P.n_cloud_sets - 1u)) : (hsh % P.n_cloud_sets);
     cs = P.cloud_sets + (size_t)set * N;
@@ -333,7 +333,7 @@ __device__ __forceinline__ void set_samples(const RtDevScene& sc, const RtDevPar
   V3 dl = mk(0.0f, 0.0f, 0.0f), ds = mk(0.0f, 0.0f, 0.0f);
   float4 cnext = make_float4(0, 0, 0, 0);
   if (N > 1 && use) cnext = cs[0];
-  auto light_position = [&](uint32_t j) {
+  auto light_position = [&](uint32_t j) {  // (mirrors the STREAM form of process_ray's light_position)
     V3 lp = mk(L0v.x, L0v.y, L0v.z);
     if (N > 1) {
       lp.x = L0v.x + cnext.x;  // light.rs:218; the table holds offset * (fw, fh, fd)
@@ -357,7 +357,7 @@ __device__ __forceinline__ void set_samples(const RtDevScene& sc, const RtDevPar
     }
   } else {
     for (uint32_t j = 0; j < N; j++) {
-      const V3 lp = light_position(j);
+      const V3 lp = light_position(j);  // (the four lines below mirror shadow_geom; see cloud_set above)
       const V3 ltp = lp - it.sf.p;
       const V3 ld = ltp * exact_rcp(mag(ltp));  // normalize(ltp): the shadow ray's geometry is exact
       const V3 so = it.sf.p + ld * epsv;
@@ -383,10 +383,8 @@ __device__ __forceinline__ void set_samples(const RtDevScene& sc, const RtDevPar
       }
     }
   }
-  const V3 c = it.Wa * (m.transmissive ? ds : (dl + ds));
-  fx = __float2ll_rn(c.x * RT_ACC_SCALE);
-  fy = __float2ll_rn(c.y * RT_ACC_SCALE);
-  fz = __float2ll_rn(c.z * RT_ACC_SCALE);
+  const Fix3 f = to_fixed(it.Wa * (m.transmissive ? ds : (dl + ds)));
+  fx = f.x, fy = f.y, fz = f.z;
 }
 
 // ---- K2: per hit -- ambient, children, and the class of every (wavefront, light) set --------------------------------------
@@ -415,8 +413,8 @@ __device__ __forceinline__ void classify_wave(const RtDevScene& sc, const RtDevP
   // finishes inline -- is summed here as integers and added ONCE at the end: a fifth of the atomics, same sum)
   long long own_x = 0, own_y = 0, own_z = 0;
   {
-    const V3 c = it.Wa * ((m.color * mk(1.0f, 1.0f, 1.0f)) * P.ambient);
-    if (hit && !T) own_x = __float2ll_rn(c.x * RT_ACC_SCALE), own_y = __float2ll_rn(c.y * RT_ACC_SCALE), own_z = __float2ll_rn(c.z * RT_ACC_SCALE);
+    const Fix3 f = to_fixed(it.Wa * ((m.color * mk(1.0f, 1.0f, 1.0f)) * P.ambient));
+    if (hit && !T) own_x = f.x, own_y = f.y, own_z = f.z;
     if (L0 && hit) P.acc[4 * (size_t)it.pix + 3] = 1;  // the pixel is written (any sample hit: antialiased_raytrace :1001-1015)
   }
   // ---- children: calculate_reflection :526-729, calculate_refractions :279-524 -------------------------------------------------
@@ -424,46 +422,11 @@ __device__ __forceinline__ void classify_wave(const RtDevScene& sc, const RtDevP
   // every hit point casts lights x N shadow rays in the reference (raytracer.rs:24); counted once, here
   wv.cnt_shadow += sc.n_lights * N * (P.weighted ? wave_sum(hit ? it.mult : 0u) : (uint32_t)__popcll(hit_m));
 
-  // ---- receiver cell of the hit point (as process_ray) ---------------------------------------------------------------------
   uint32_t rflags = 0u, cell = RT_NO_CELL;
-  if (N > 1 && P.recv_flags && hit) {
-    if (it.id >= (int)sc.n_spheres) {
-      const uint32_t ro = sc.off_recv + (uint32_t)(it.id - (int)sc.n_spheres) * 48u;
-      const float4 ru = vload<float4>(sc, ro), rv = vload<float4>(sc, ro + 16u);
-      const uint2 rr = vload<uint2>(sc, ro + 32u);  // {R, first cell}
-      const float Rf = (float)rr.x;
-      const float cu = (__builtin_fmaf(ru.x, it.sf.p.x, __builtin_fmaf(ru.y, it.sf.p.y, ru.z * it.sf.p.z)) + ru.w) * Rf;
-      const float cv = (__builtin_fmaf(rv.x, it.sf.p.x, __builtin_fmaf(rv.y, it.sf.p.y, rv.z * it.sf.p.z)) + rv.w) * Rf;
-      const uint32_t ci = (uint32_t)fminf(fmaxf(cu, 0.0f), Rf - 1.0f), cj = (uint32_t)fminf(fmaxf(cv, 0.0f), Rf - 1.0f);
-      if (rr.x != 0u && ci + cj < rr.x) cell = rr.y + ci + rr.x * cj, rflags = P.recv_flags[cell];
-    } else {
-      const uint2 sr = vload<uint2>(sc, sc.off_srecv + (uint32_t)it.id * 8u);  // {Rs, first cell}
-      const float4 sp = vload<float4>(sc, sc.off_spheres + (uint32_t)it.id * 16u);
-      const V3 dd = it.sf.p - mk(sp.x, sp.y, sp.z);
-      const float ax = fabsf(dd.x), ay = fabsf(dd.y), az = fabsf(dd.z);
-      const bool mx = ax >= ay && ax >= az, my = !mx && ay >= az;
-      const float dm = mx ? dd.x : (my ? dd.y : dd.z), du = mx ? dd.y : (my ? dd.z : dd.x), dv = mx ? dd.z : (my ? dd.x : dd.y);
-      const uint32_t face = (mx ? 0u : (my ? 2u : 4u)) + (dm < 0.0f ? 1u : 0u);
-      const float inv = __builtin_amdgcn_rcpf(fmaxf(fabsf(dm), 1e-30f)), Rf = (float)sr.x;
-      const uint32_t ci = (uint32_t)fminf(fmaxf((__builtin_fmaf(du, inv, 1.0f)) * 0.5f * Rf, 0.0f), Rf - 1.0f);
-      const uint32_t cj = (uint32_t)fminf(fmaxf((__builtin_fmaf(dv, inv, 1.0f)) * 0.5f * Rf, 0.0f), Rf - 1.0f);
-      if (sr.x != 0u) cell = sr.y + (face * sr.x + cj) * sr.x + ci, rflags = P.recv_flags[cell];
-    }
-  }
-  // first hit point of the wavefront and how far the others are from it (sphere pre-selection of the candidate collection)
+  if (N > 1) receiver_cell(sc, P, P.recv_flags && hit, it.id, it.sf.p, cell, rflags);
   V3 p_first = mk(0, 0, 0);
   float p_spread = 0.0f;
-  if (N > 1 && sc.n_spheres) {
-    const int fl = __ffsll((long long)hit_m) - 1;
-    p_first = mk(__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(it.sf.p.x), fl)),
-                 __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(it.sf.p.y), fl)),
-                 __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(it.sf.p.z), fl)));
-    const V3 dp = it.sf.p - p_first;
-    float mm = hit ? (fabsf(dp.x) + fabsf(dp.y) + fabsf(dp.z)) : 0.0f;  // 1-norm >= distance
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mm = fmaxf(mm, __shfl_xor(mm, o, 64));
-    p_spread = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(mm))) * 1.000001f;
-  }
+  if (N > 1 && sc.n_spheres) wave_spread(hit, hit_m, it.sf.p, p_first, p_spread);
   const bool hard_ok = P.hard_q && N > 1 && N <= 64u && P.traversal == RT_TRAVERSAL_BVH && sc.n_triangles && P.cand_cap != 0u;
   const uint32_t set_base = (item_base >> 6) * sc.n_lights;
   // The per-cell candidate lists are a gather from a table of hundreds of megabytes (HBM latency, and the first thing a light's
@@ -490,11 +453,7 @@ __device__ __forceinline__ void classify_wave(const RtDevScene& sc, const RtDevP
     }
     lanemask use_m = wave_ballot(use);
     if (!use_m) continue;
-    CandList cand;
-    cand.reg = 0;
-    cand.count = RT_CAND_OVERFLOW;
-    cand.spheres = 0xFFFFFFFFu;
-    cand.umbra = 0ull;
+    CandList cand = cand_unknown();
     if (N > 1 && P.cloud_delta > 0.0f && P.traversal == RT_TRAVERSAL_BVH && sc.n_triangles) {
       const V3 centre = mk(L0v.x + P.cloud_centre[0], L0v.y + P.cloud_centre[1], L0v.z + P.cloud_centre[2]);
       bool walk_tris = true, test_spheres = true;
@@ -503,35 +462,9 @@ __device__ __forceinline__ void classify_wave(const RtDevScene& sc, const RtDevP
         walk_tris = (use_m & ~wave_ballot(rf & 1u)) != 0ull;
         test_spheres = walk_tris || (use_m & ~wave_ballot((rf >> 8) & 1u)) != 0ull;
       }
-      // per-cell candidate lists: the union of the lanes' lists replaces the BVH walk (as process_ray)
       uint32_t pre_reg = 0, pre_count = 0;
       bool have_pre = false;
-      if (!CULL && P.cell_lists && walk_tris) {
-        const uint4 lst = use ? lst_now : no_list;
-        const lanemask unusable = use_m & (wave_ballot(cell == RT_NO_CELL) | wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_OVERFLOW));
-        if (!unusable) {
-          have_pre = true;
-          for (lanemask todo = use_m & ~wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_END); todo;) {
-            const int fl = __ffsll((long long)todo) - 1;
-            const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cell, fl);
-            auto add_slot = [&](uint32_t slot) {  // (uniform)
-              if (slot >= RT_CELL_LIST_OVERFLOW) return;  // end marker
-              const lanemask filled = pre_count >= 64u ? ~0ull : ((1ull << pre_count) - 1ull);
-              if (wave_ballot(pre_reg == slot) & filled) return;  // another cell listed it already
-              lane_put(pre_reg, pre_count, slot, lane);
-              pre_count++;
-            };
-            auto add_pair = [&](uint32_t v) {
-              const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)v, fl);
-              add_slot(w & 0xFFFFu);
-              add_slot(w >> 16);
-            };
-            add_pair(lst.x), add_pair(lst.y), add_pair(lst.z), add_pair(lst.w);
-            todo &= ~wave_ballot(cell == c);
-          }
-          if (pre_count > 64u) have_pre = false;  // (more than a VGPR's worth of lanes: walk)
-        }
-      }
+      if (!CULL && P.cell_lists && walk_tris) have_pre = union_cell_lists(use_m, cell, use ? lst_now : no_list, pre_reg, pre_count);
       if (test_spheres) {
         cand = collect_light_candidates<CULL>(sc, W, use, it.sf.p, centre, P, p_first, p_spread, P.cand_cap, nullptr, walk_tris, have_pre,
                                               pre_reg, pre_count);

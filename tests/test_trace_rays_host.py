@@ -214,9 +214,12 @@ def test_pinhole_camera():
 # installed with this repository's toolchain, gfx950, the Makefile's default flags.
 # kernel -> (VGPRs, TotalSGPRs, SGPRs Spill, VGPRs Spill, ScratchSize [bytes/lane], Occupancy [waves/SIMD], LDS Size [bytes/block])
 # No margin: the radiance queries add kernels, the existing ones keep their code.
+# Three rows moved DOWN since, when the render forms got one copy of their shared rules (profiles/shared_rules.md): SGPR / VGPR
+# spills and scratch of rt_classify0_kernel 126 / 34 / 108 -> 124 / 32 / 100, VGPR spills and scratch of rt_primary_pre_kernel
+# 22 / 36 -> 20 / 28, SGPR spills of rt_primary_stream_kernel 43 -> 33.  No row may move up.
 FIELDS = ("VGPRs", "TotalSGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]")
-PARENT = {
-    "rt_classify0_kernel": (80, 106, 126, 34, 108, 6, 6304),
+PINNED = {
+    "rt_classify0_kernel": (80, 106, 124, 32, 100, 6, 6304),
     "rt_classify_kernel": (80, 106, 187, 29, 92, 6, 160),
     "rt_compact_kernel": (27, 57, 0, 0, 0, 8, 0),
     "rt_flags_kernel": (77, 94, 0, 0, 0, 6, 0),
@@ -224,14 +227,14 @@ PARENT = {
     "rt_hit_kernel": (42, 78, 14, 0, 0, 8, 160),
     "rt_hit_spawn_kernel": (64, 78, 21, 4, 12, 8, 224),
     "rt_primary_kernel": (80, 106, 20, 14, 28, 6, 19616),
-    "rt_primary_pre_kernel": (80, 106, 23, 22, 36, 6, 25760),
+    "rt_primary_pre_kernel": (80, 106, 23, 20, 28, 6, 25760),
     "rt_primary_soft10_flags_kernel": (80, 106, 0, 7, 28, 6, 19616),
     "rt_primary_soft10_kernel": (80, 106, 0, 7, 28, 6, 19616),
     "rt_primary_soft19_flags_kernel": (80, 106, 0, 7, 28, 6, 19616),
     "rt_primary_soft19_kernel": (80, 106, 0, 7, 28, 6, 19616),
     "rt_primary_soft28_flags_kernel": (80, 106, 0, 7, 28, 6, 19616),
     "rt_primary_soft28_kernel": (80, 106, 0, 7, 28, 6, 19616),
-    "rt_primary_stream_kernel": (80, 104, 43, 20, 32, 6, 25760),
+    "rt_primary_stream_kernel": (80, 104, 33, 20, 32, 6, 25760),
     "rt_query_any_kernel": (55, 89, 0, 0, 0, 8, 0),
     "rt_query_nearest_kernel": (51, 88, 0, 0, 0, 8, 0),
     "rt_resolve_kernel": (20, 26, 0, 0, 0, 8, 0),
@@ -278,7 +281,7 @@ def test_ray_kernels_are_uniform_walks_at_six_waves(compiled):
 
 def test_existing_kernels_compile_to_what_they_did(compiled):
     _, _, remarks = compiled
-    assert set(remarks) - set(RAY_KERNELS) == set(PARENT), sorted(set(remarks) ^ set(PARENT) ^ set(RAY_KERNELS))
-    for name, want in PARENT.items():
+    assert set(remarks) - set(RAY_KERNELS) == set(PINNED), sorted(set(remarks) ^ set(PINNED) ^ set(RAY_KERNELS))
+    for name, want in PINNED.items():
         got = tuple(remarks[name][f] for f in FIELDS)
         assert got == want, (name, dict(zip(FIELDS, got)), dict(zip(FIELDS, want)))
