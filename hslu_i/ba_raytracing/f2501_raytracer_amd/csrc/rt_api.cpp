@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_cell_prune.h"
 #include "rt_host.h"
 
 static void trace_point(hipStream_t stream, const char* what, uint32_t a = 0, uint32_t b = 0, uint32_t c = 0);  // RT_TRACE_LAUNCHES
@@ -335,6 +336,23 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
       hipError_t e = (hipError_t)rt_launch_flags(s->dev, B, stream);
       if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_flags_kernel launch failed: %s", hipGetErrorString(e));
       trace_point(stream, "rt_flags_kernel: cells, lights, lists", s->n_cells, s->dev.n_lights, s->cell_lists_built ? 1u : 0u);
+      // the lists thinned out by the sharper per-cell rule (rt_cell_prune.h): same stream, same key, so it reruns whenever
+      // the flags do.  RT_CELL_PRUNE=0 (read once per process) leaves it out (A/B timing, equality tests).
+      static const char* const prune_env = getenv("RT_CELL_PRUNE");
+      static const bool prune_off = prune_env && *prune_env == '0';
+      if (s->cell_lists_built && !prune_off) {
+        RtCellPruneArgs a{};
+        a.flag_geo = (const float*)s->flag_geo.p;
+        a.lists = (uint16_t*)s->cell_lists.p;
+        a.flags = (uint16_t*)s->flags.p;
+        a.n_cells = s->n_cells, a.n_tri_cells = s->n_tri_cells;
+        memcpy(a.cloud_centre, P->cloud_centre, 12);
+        a.beam_delta = P->beam_delta, a.beam_eps_o = P->beam_eps_o;
+        a.mode = RT_PRUNE_FULL;
+        e = (hipError_t)rt_launch_cell_prune(s->dev, a, stream);
+        if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_cell_prune_kernel launch failed: %s", hipGetErrorString(e));
+        trace_point(stream, "rt_cell_prune_kernel: cells, lights", s->n_cells, s->dev.n_lights, 0u);
+      }
       memcpy(s->flags_key, key, sizeof(key));
     }
     P->recv_flags = (const uint16_t*)s->flags.p;

@@ -1,0 +1,162 @@
+"""What rt_cell_prune_kernel removes from the per-cell shadow candidate lists of a scene, counted on the GPU.
+
+Packs the scene with the library's own packer under --budget (default 2 GiB: bench.py's, the per-cell lists fit), runs
+rt_flags_kernel with lists, reads lists and flags back, runs rt_cell_prune_kernel and reads them back again.  Reports, before
+and after pruning: listed slots, non-empty lists, lists emptied, triangle-clear bits gained per light, and the overflowed
+lists (more than 8 candidates: left alone, the render walks the tree for such a cell).  A probe compiled on the fly links
+against the built librt_hip.so, so the kernels counted here are the ones that ship.  Prints one JSON line.
+
+    python tools/cell_list_stats.py [--scene semesterbild] [--model text] [--budget BYTES]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+from hslu_i.ba_raytracing.f2501_raytracer_amd import RenderConfig, _abi, _lib, sampling, scenes  # noqa: E402
+
+CSRC = os.path.join(ROOT, "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csrc")
+PROBE = r'''
+#include <hip/hip_runtime_api.h>
+#include <cstring>
+#include "rt_cell_prune.h"
+#include "rt_scene_pack.h"
+static RtPackedScene g;
+#define TRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return 1000 + (int)e_; } while (0)
+extern "C" {
+const char* probe_error() { return rt_last_error(); }
+int probe_pack(const rt_scene_desc* d, uint64_t budget, uint32_t* out) {
+  const int rc = rt_pack_scene(d, budget, &g);
+  out[0] = g.n_cells, out[1] = g.n_tri_cells, out[2] = g.dev.n_lights, out[3] = g.dev.n_slots;
+  return rc;
+}
+// lists [n_cells][n_lights][8] and flags [n_cells]: raw_* as rt_flags_kernel leaves them, out_* after rt_cell_prune_kernel
+int probe_run(const float* cloud, uint64_t n_floats, const float* f, float eps, uint16_t* raw_lists, uint16_t* raw_flags, uint16_t* out_lists,
+              uint16_t* out_flags, float* ms) {
+  if (!g.n_cells || g.dev.n_lights > 8u || g.dev.n_slots > 65533u) return -100;
+  std::vector<float> scaled;
+  float ball[4];
+  rt_scale_cloud(cloud, n_floats, f, &scaled, ball);
+  RtDevParams P{};
+  memcpy(P.cloud_centre, ball, 12);
+  P.cloud_delta = ball[3], P.eps_distance = eps, P.cand_cap = 64u;
+  rt_beam_constants(eps, &P);
+  const size_t list_bytes = (size_t)g.n_cells * g.dev.n_lights * 16u, flag_bytes = (size_t)g.n_cells * 2u;
+  char* blob = nullptr;
+  float* geo = nullptr;
+  uint16_t *lists = nullptr, *flags = nullptr;
+  hipEvent_t e[3];
+  TRY(hipSetDevice(0));
+  for (auto& x : e) TRY(hipEventCreate(&x));
+  TRY(hipMalloc((void**)&blob, g.blob.size()));
+  TRY(hipMalloc((void**)&geo, g.flag_geo.size() * 4));
+  TRY(hipMalloc((void**)&lists, list_bytes + 64));
+  TRY(hipMalloc((void**)&flags, flag_bytes + 64));
+  TRY(hipMemcpy(blob, g.blob.data(), g.blob.size(), hipMemcpyHostToDevice));
+  TRY(hipMemcpy(geo, g.flag_geo.data(), g.flag_geo.size() * 4, hipMemcpyHostToDevice));
+  TRY(hipMemset(lists, 0xFF, list_bytes));
+  TRY(hipMemset(flags, 0, flag_bytes));
+  RtDevScene sc = g.dev;
+  sc.base = blob;
+  P.flag_out = flags, P.flag_geo = (const float4*)geo, P.cell_list_out = lists;
+  P.n_cells = g.n_cells, P.n_tri_cells = g.n_tri_cells;
+  TRY(hipEventRecord(e[0], nullptr));
+  TRY((hipError_t)rt_launch_flags(sc, P, nullptr));
+  TRY(hipEventRecord(e[1], nullptr));
+  TRY(hipDeviceSynchronize());
+  TRY(hipMemcpy(raw_lists, lists, list_bytes, hipMemcpyDeviceToHost));
+  TRY(hipMemcpy(raw_flags, flags, flag_bytes, hipMemcpyDeviceToHost));
+  RtCellPruneArgs a{};
+  a.flag_geo = geo, a.lists = lists, a.flags = flags;
+  a.n_cells = g.n_cells, a.n_tri_cells = g.n_tri_cells;
+  memcpy(a.cloud_centre, ball, 12);
+  a.beam_delta = P.beam_delta, a.beam_eps_o = P.beam_eps_o;
+  a.mode = RT_PRUNE_FULL;
+  TRY(hipEventRecord(e[1], nullptr));
+  TRY((hipError_t)rt_launch_cell_prune(sc, a, nullptr));
+  TRY(hipEventRecord(e[2], nullptr));
+  TRY(hipDeviceSynchronize());
+  TRY(hipMemcpy(out_lists, lists, list_bytes, hipMemcpyDeviceToHost));
+  TRY(hipMemcpy(out_flags, flags, flag_bytes, hipMemcpyDeviceToHost));
+  ms[0] = ms[1] = 0.f;
+  TRY(hipEventElapsedTime(&ms[1], e[1], e[2]));
+  TRY(hipFree(blob));
+  TRY(hipFree(geo));
+  TRY(hipFree(lists));
+  TRY(hipFree(flags));
+  return 0;
+}
+}
+'''
+
+
+def ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", default="semesterbild", choices=["semesterbild", "test_scene"])
+    ap.add_argument("--model", default="text")
+    ap.add_argument("--budget", type=int, default=2 << 30)
+    args = ap.parse_args()
+    cfg = RenderConfig.from_features(["high_resolution", "anti_aliasing", "soft_shadows"])  # bench.py's c3
+    flat = (scenes.semesterbild(cfg, args.model) if args.scene == "semesterbild" else scenes.test_scene(cfg)).flatten().contiguous()
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    with tempfile.TemporaryDirectory() as d:
+        src, so = os.path.join(d, "probe.cpp"), os.path.join(d, "probe.so")
+        with open(src, "w") as fh:
+            fh.write(PROBE)
+        lib_dir, lib_name = os.path.split(os.path.abspath(_lib.LIB_PATH))
+        subprocess.run([hipcc, "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip", "--cuda-host-only", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
+                        "-shared", "-o", so, src, "-L", lib_dir, f"-l:{lib_name}", f"-Wl,-rpath,{lib_dir}"], check=True)
+        probe = C.CDLL(so)
+    probe.probe_error.restype = C.c_char_p
+    desc, keep = _abi.make_scene_desc(flat)
+    out = np.zeros(4, np.uint32)
+    rc = probe.probe_pack(C.byref(desc), C.c_uint64(args.budget), ptr(out))
+    assert rc == 0, probe.probe_error()
+    n_cells, n_tri_cells, nl, ns = (int(v) for v in out)
+    cs = np.ascontiguousarray(sampling.cloud_sets(cfg), np.float32)
+    f = np.array([cfg.fw, cfg.fh, cfg.fd], np.float32)
+    raw_l, new_l = (np.zeros((n_cells, nl, 8), np.uint16) for _ in range(2))
+    raw_f, new_f = (np.zeros(n_cells, np.uint16) for _ in range(2))
+    ms = np.zeros(2, np.float32)
+    rc = probe.probe_run(ptr(cs), C.c_uint64(cs.size), ptr(f), C.c_float(cfg.eps_distance), ptr(raw_l), ptr(raw_f), ptr(new_l), ptr(new_f), ptr(ms))
+    assert rc == 0, f"probe_run: {rc}"
+    over = raw_l[:, :, 0] == 0xFFFE
+    usable = ~over
+
+    def count(lists, flags):
+        listed = (lists < 0xFFFE) & usable[:, :, None]
+        per_list = listed.sum(2)
+        return {"listed_slots": int(listed.sum()), "non_empty_lists": int((per_list > 0).sum()),
+                "mean_slots_per_non_empty_list": float(listed.sum() / max(1, (per_list > 0).sum())),
+                "histogram_slots_per_list": [int((per_list[usable] == k).sum()) for k in range(9)],
+                "triangle_clear_bits_per_light": [int(((flags >> l) & 1).sum()) for l in range(nl)]}
+    before, after = count(raw_l, raw_f), count(new_l, new_f)
+    emptied = ((raw_l[:, :, 0] < 0xFFFE) & (new_l[:, :, 0] == 0xFFFF)).sum(0)
+    res = {"scene": args.scene, "model": args.model, "budget": args.budget, "n_cells": n_cells, "n_tri_cells": n_tri_cells, "n_lights": nl, "n_slots": ns,
+           "overflowed_lists_left_alone": int(over.sum()), "overflowed_lists_per_light": [int(v) for v in over.sum(0)],
+           "cells_with_an_overflowed_list": int(over.any(1).sum()), "before": before, "after": after,
+           "lists_emptied_per_light": [int(v) for v in emptied],
+           "clear_bits_gained_per_light": [a - b for a, b in zip(after["triangle_clear_bits_per_light"], before["triangle_clear_bits_per_light"])],
+           "slots_removed": before["listed_slots"] - after["listed_slots"],
+           "slots_removed_fraction": (before["listed_slots"] - after["listed_slots"]) / max(1, before["listed_slots"]),
+           "prune_kernel_ms": float(ms[1]), "build_id": _lib.load().rt_build_id().decode()}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
