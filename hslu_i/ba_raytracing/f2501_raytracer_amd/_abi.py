@@ -182,6 +182,21 @@ class rt_view_info(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+RT_REFINE_ID, RT_REFINE_DEPTH, RT_REFINE_COLOUR, RT_REFINE_EVERY = 1, 2, 4, 8
+
+
+class rt_view_refine(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("criteria", C.c_uint32), ("colour_tol", C.c_float), ("depth_tol", C.c_float)]
+
+
+class rt_view_adaptive_info(C.Structure):
+    _fields_ = [("n_refined", C.c_uint32), ("n_live_rays", C.c_uint32), ("bytes", C.c_uint64), ("pass1_ms", C.c_double),
+                ("classify_ms", C.c_double), ("partition_ms", C.c_double), ("pass2_ms", C.c_double), ("resolve_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 RT_UPDATE_INVALIDATES_RECEIVER_TABLES, RT_UPDATE_INVALIDATES_TILE_COSTS, RT_UPDATE_INVALIDATES_QUEUE_SIZES = 1, 2, 4
 
 

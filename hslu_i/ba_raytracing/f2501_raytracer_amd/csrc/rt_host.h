@@ -396,6 +396,12 @@ int rt_trace_rays_enqueue(rt_scene* s, const rt_params* p, const RtRayArgs& r, h
 int rt_trace_rays_check(const rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, const char* fn);
 // the device memory an order holds (rt_ray_order_info.bytes), readable before the order was ever built (rt_rays.cpp)
 size_t rt_ray_order_bytes(const rt_ray_order* o);
+// the permutation a built or set order holds on its device, [n] (rt_rays.cpp)
+const uint32_t* rt_ray_order_perm(const rt_ray_order* o);
+// rt_trace_rays_ordered_device through a permutation the caller holds on the scene's device instead of an order handle
+// (perm == nullptr: rt_trace_rays_device): the partitioned orders of an adaptive view.  Same checks, same enqueue.
+int rt_trace_rays_perm_device(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const uint32_t* perm, const rt_ray_radiance* out,
+                              hipStream_t stream, const char* fn);
 // the ray counters of the frame that used frame slot `slot` of the scene last (rt_scene::cur_block right after a frame
 // was enqueued); the caller has waited for that frame
 int rt_collect_stats_slot(rt_scene* s, int slot, rt_stats* st);

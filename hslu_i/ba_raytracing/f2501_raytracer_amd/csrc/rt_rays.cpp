@@ -181,6 +181,20 @@ int rt_trace_rays_check(const rt_scene* s, const rt_params* p, const rt_ray_batc
 
 size_t rt_ray_order_bytes(const rt_ray_order* o) { return o ? o->buf.cap : 0; }
 
+const uint32_t* rt_ray_order_perm(const rt_ray_order* o) { return o ? o->ws.idx_b : nullptr; }
+
+int rt_trace_rays_perm_device(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const uint32_t* perm, const rt_ray_radiance* out,
+                              hipStream_t stream, const char* fn) {
+  rt_params q;
+  const int rc = check_call(s, p, b, out, fn, &q);
+  if (rc != RT_OK) return rc;
+  if (b->n_rays == 0) return RT_OK;
+  if (s->progress_active) return fail(RT_ERR_INVALID_ARG, "a progressive render owns this scene until rt_render_end");
+  RtRayArgs r = args_of(b, out, nullptr);
+  r.order = perm;
+  return rt_trace_rays_enqueue(s, &q, r, stream);
+}
+
 extern "C" {
 
 int rt_trace_rays_device(rt_scene* s, const rt_params* p, const rt_ray_batch* b, const rt_ray_radiance* out, void* hip_stream) {

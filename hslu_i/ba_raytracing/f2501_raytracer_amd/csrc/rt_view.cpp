@@ -5,13 +5,17 @@
 // A view is built ON TOP of the radiance queries: it makes a ray batch and hands it to rt_ray_order_build_device and
 // rt_trace_rays[_ordered]_device through their public entry points, so every blocking, validation and scene-state rule of a
 // frame is the trace's.
+//
+// Also the host side of adaptive frames (rt_view_enable_adaptive, rt_render_view_adaptive*): the second allocation and the
+// sequence pass 1 -> classify -> sparse generator -> partition -> pass 2 -> adaptive resolve.  Their arithmetic is in
+// rt_view_adapt.h, their kernels in rt_view_adapt.hip, their host models in rt_view_adapt.cpp.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cstring>
 
 #include "rt_host.h"
-#include "rt_view.h"
+#include "rt_view_adapt.h"
 
 struct rt_view {
   int device = 0;
@@ -31,6 +35,15 @@ struct rt_view {
   RtPending done;                // behind the last work enqueued for this view
   hipEvent_t ev[5] = {};         // host form: before / after the generator, after the order, before / after the resolve
   double rays_ms = 0.0, order_ms = 0.0, resolve_ms = 0.0;
+  // adaptive frames (rt_view_enable_adaptive): one more allocation, the plane-0 order's state, the stage events and times
+  bool adaptive = false;
+  DevBuf abuf;
+  RtViewAdaptWs aws{};
+  bool order0_built = false;     // aws.order0 is the plane-0 part of the order the view holds now
+  hipEvent_t aev[6] = {};        // host form: begin, after pass 1, the classify, the partition, pass 2, the resolve
+  uint32_t n_refined = 0;
+  bool n_refined_read = true;    // n_refined holds the word of the last adaptive frame
+  double astage_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
 int rt_view_check_desc(const rt_view_desc* d, const char* fn) {
@@ -102,6 +115,9 @@ void view_free(rt_view* v) {
   rt_ray_order_destroy(v->order);
   for (hipEvent_t e : v->ev)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : v->aev)
+    if (e) (void)hipEventDestroy(e);
+  v->abuf.release();
   v->buf.release();
   delete v;
 }
@@ -142,7 +158,7 @@ int render_enqueue(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_rad
   const bool build = v->order && (v->order_mode == RT_VIEW_ORDER_ALWAYS || !v->order_built);
   if (build) {
     if ((rc = rt_ray_order_build_device(v->order, &b, stream)) != RT_OK) return rc;
-    v->order_built = true;
+    v->order_built = true, v->order0_built = false;
   }
   if (timed) HIP_TRY(hipEventRecord(v->ev[2], stream));
   rt_ray_radiance rays{};
@@ -156,6 +172,84 @@ int render_enqueue(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_rad
   if (timed) v->order_ms = build ? -1.0 : 0.0;  // (-1: read from the events once the stream has drained)
   return v->done.mark(stream);
 }
+
+// ---- adaptive frames ------------------------------------------------------------------------------------------------------------
+#define ADAPT_TRY(what, expr)                                                                     \
+  do {                                                                                            \
+    const hipError_t e_ = (hipError_t)(expr);                                                     \
+    if (e_ != hipSuccess) return fail(RT_ERR_HIP, what " launch failed: %s", hipGetErrorString(e_)); \
+  } while (0)
+
+int check_render_adaptive(const rt_scene* s, const rt_view* v, const rt_params* p, const rt_view_refine* rf, const rt_ray_radiance* out, const char* fn) {
+  if (!s) return fail(RT_ERR_INVALID_ARG, "%s: null scene", fn);
+  if (!v) return fail(RT_ERR_INVALID_ARG, "%s: null view", fn);
+  int rc = rt_view_check_refine(rf, fn);
+  if (rc != RT_OK) return rc;
+  if ((rc = check_render(s, v, p, out, fn)) != RT_OK) return rc;
+  if (!v->adaptive) return fail(RT_ERR_INVALID_ARG, "%s: the view has no adaptive workspace (rt_view_enable_adaptive)", fn);
+  return RT_OK;
+}
+
+// pass 1 -> classify -> sparse generator -> partition -> pass 2 -> adaptive resolve on `stream`; `out`, mask_out: DEVICE.
+// timed: record the stage events.  pass1_stats (host form): the stream is drained behind pass 1 and its counters are read,
+// because pass 2 may take the same frame slot of the scene.
+int adaptive_enqueue(rt_scene* s, rt_view* v, const rt_params* p, const rt_view_refine* rf, const rt_ray_radiance* out, uint8_t* mask_out,
+                     hipStream_t stream, bool timed, rt_stats* pass1_stats, const char* fn) {
+  int rc;
+  const RtViewAdaptWs& w = v->aws;
+  const bool planes = v->n_distinct > 1u;
+  if (timed) HIP_TRY(hipEventRecord(v->aev[0], stream));
+  // the order: built from one complete run of the full generator (which makes plane 0 as well); its plane-0 part when it changed
+  const bool build = v->order && (v->order_mode == RT_VIEW_ORDER_ALWAYS || !v->order_built);
+  if (build) {
+    if ((rc = rays_enqueue(v, v->origin, v->direction, stream)) != RT_OK) return rc;
+    rt_ray_batch all{};
+    all.abi_version = RT_ABI_VERSION, all.n_rays = v->n_rays, all.origin = v->origin, all.direction = v->direction;
+    if ((rc = rt_ray_order_build_device(v->order, &all, stream)) != RT_OK) return rc;
+    v->order_built = true, v->order0_built = false;
+  } else {
+    ADAPT_TRY("view ray generator", rt_launch_view_rays(v->cam, v->distinct_dev, 1u, v->origin, v->direction, stream));
+  }
+  const uint32_t* order = v->order ? rt_ray_order_perm(v->order) : nullptr;
+  if (order && planes && !v->order0_built) {
+    ADAPT_TRY("view flags", rt_launch_view_flags(order, v->n_rays, v->n_pixels, nullptr, w.flags, stream));
+    ADAPT_TRY("partition", rt_launch_partition(order, w.flags, v->n_rays, v->n_pixels, w.counts, w.sums, w.order0, stream));
+    v->order0_built = true;
+  }
+  // pass 1: plane 0 = the first n_pixels rays of the layout, into the base planes
+  rt_ray_batch b0{};
+  b0.abi_version = RT_ABI_VERSION, b0.n_rays = v->n_pixels, b0.origin = v->origin, b0.direction = v->direction;
+  rt_ray_radiance base{};
+  base.rgb = w.rgb0, base.valid = w.valid0, base.id = w.id0, base.t = w.t0;
+  if ((rc = rt_trace_rays_perm_device(s, p, &b0, order ? (planes ? w.order0 : order) : nullptr, &base, stream, fn)) != RT_OK) return rc;
+  if (pass1_stats) {
+    HIP_TRY(hipStreamSynchronize(stream));
+    if ((rc = rt_render_collect_stats(s, pass1_stats)) != RT_OK) return rc;
+  }
+  if (timed) HIP_TRY(hipEventRecord(v->aev[1], stream));
+  HIP_TRY(hipMemsetAsync(w.n_refined, 0, 4, stream));
+  ADAPT_TRY("view classify", rt_launch_view_classify(v->width, v->height, rf->criteria, rf->colour_tol, rf->depth_tol, w, mask_out, stream));
+  v->n_refined_read = false;
+  if (timed) HIP_TRY(hipEventRecord(v->aev[2], stream));
+  if (planes) {
+    ADAPT_TRY("sparse view ray generator", rt_launch_view_sparse_rays(v->cam, v->distinct_dev, v->n_distinct, w.mask, v->origin, v->direction, stream));
+    ADAPT_TRY("view flags", rt_launch_view_flags(order, v->n_rays, v->n_pixels, w.mask, w.flags, stream));
+    ADAPT_TRY("partition", rt_launch_partition(order, w.flags, v->n_rays, v->n_rays, w.counts, w.sums, w.perm2, stream));
+  }
+  if (timed) HIP_TRY(hipEventRecord(v->aev[3], stream));
+  if (planes) {
+    rt_ray_batch b{};
+    b.abi_version = RT_ABI_VERSION, b.n_rays = v->n_rays, b.origin = v->origin, b.direction = v->direction;
+    rt_ray_radiance rays{};
+    rays.rgb = v->rgb, rays.valid = v->valid;  // (id and t are plane 0's)
+    if ((rc = rt_trace_rays_perm_device(s, p, &b, w.perm2, &rays, stream, fn)) != RT_OK) return rc;
+  }
+  if (timed) HIP_TRY(hipEventRecord(v->aev[4], stream));
+  ADAPT_TRY("adaptive view resolve", rt_launch_view_resolve_adaptive(v->n_pixels, v->n_samples, v->plane_of_dev, w, v->rgb, v->valid, *out, stream));
+  if (timed) HIP_TRY(hipEventRecord(v->aev[5], stream));
+  return v->done.mark(stream);
+}
+#undef ADAPT_TRY
 
 }  // namespace
 
@@ -253,6 +347,98 @@ int rt_render_view(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_rad
     stats->kernel_ms = ms;  // generator .. resolve (with secondary rays: every attempt of the batch, as rt_trace_rays)
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
+  return RT_OK;
+}
+
+int rt_view_enable_adaptive(rt_view* v) {
+  if (!v) return fail(RT_ERR_INVALID_ARG, "rt_view_enable_adaptive: null view");
+  if (v->adaptive) return RT_OK;
+  HIP_TRY(hipSetDevice(v->device));
+  int rc = v->done.wait();
+  if (rc != RT_OK) return rc;
+  RtArena lay;
+  rt_view_adapt_ws_add(lay, v->n_pixels, v->n_rays, RT_ORDER_SCAN_BLOCKS, &v->aws);
+  if ((rc = v->abuf.ensure(lay.total())) != RT_OK) return rc;
+  lay.bind(v->abuf.p);
+  for (hipEvent_t& e : v->aev)
+    if (!e) HIP_TRY(hipEventCreate(&e));
+  v->adaptive = true;
+  return RT_OK;
+}
+
+int rt_render_view_adaptive_device(rt_scene* s, rt_view* v, const rt_params* p, const rt_view_refine* rf, const rt_ray_radiance* out,
+                                   uint8_t* mask_dev, void* hip_stream) {
+  const char* fn = "rt_render_view_adaptive_device";
+  const int rc = check_render_adaptive(s, v, p, rf, out, fn);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  for (double& ms : v->astage_ms) ms = 0.0;
+  return adaptive_enqueue(s, v, p, rf, out, mask_dev, (hipStream_t)hip_stream, false, nullptr, fn);
+}
+
+int rt_render_view_adaptive(rt_scene* s, rt_view* v, const rt_params* p, const rt_view_refine* rf, const rt_ray_radiance* out, uint8_t* mask,
+                            rt_stats* stats) {
+  const char* fn = "rt_render_view_adaptive";
+  int rc = check_render_adaptive(s, v, p, rf, out, fn);
+  if (rc != RT_OK) return rc;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = v->done.wait()) != RT_OK) return rc;
+  const auto t_begin = std::chrono::steady_clock::now();
+  const size_t n = v->n_pixels;
+  rt_ray_radiance dev = *out;
+  HostCall c;
+  c.out(&dev.rgb, n * 12), c.out(&dev.valid, n), c.out(&dev.id, n * 4), c.out(&dev.t, n * 4), c.out(&dev.argb, n * 4, true);
+  c.out(&mask, n);
+  Forget forget{s, c};
+  if ((rc = c.begin()) != RT_OK) return rc;
+  rt_stats pass1;
+  memset(&pass1, 0, sizeof(pass1));
+  if ((rc = adaptive_enqueue(s, v, p, rf, &dev, mask, c.stream, true, stats ? &pass1 : nullptr, fn)) != RT_OK) return rc;
+  if ((rc = c.finish()) != RT_OK) return rc;
+  v->done.clear();
+  for (int k = 0; k < 5; k++) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, v->aev[k], v->aev[k + 1]));
+    v->astage_ms[k] = ms;
+  }
+  if (stats) {
+    if (v->n_distinct > 1u) {
+      if ((rc = rt_render_collect_stats(s, stats)) != RT_OK) return rc;
+      stats->rays_primary += pass1.rays_primary, stats->rays_reflection += pass1.rays_reflection, stats->rays_refraction += pass1.rays_refraction;
+      stats->rays_shadow += pass1.rays_shadow, stats->pixels_written += pass1.pixels_written, stats->rays_traced += pass1.rays_traced;
+      stats->wave_ray_passes += pass1.wave_ray_passes, stats->wave_ray_lanes += pass1.wave_ray_lanes;
+      stats->wave_nearest_nodes += pass1.wave_nearest_nodes, stats->wave_nearest_tris += pass1.wave_nearest_tris;
+      stats->wave_shadow_nodes += pass1.wave_shadow_nodes, stats->wave_shadow_tris += pass1.wave_shadow_tris;
+      stats->wave_shadow_passes += pass1.wave_shadow_passes, stats->wave_nearest_tris_exact += pass1.wave_nearest_tris_exact;
+      stats->wave_shadow_tris_exact += pass1.wave_shadow_tris_exact;
+      stats->notes |= pass1.notes;
+    } else {
+      *stats = pass1;
+    }
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, v->aev[0], v->aev[5]));
+    stats->kernel_ms = ms;  // pass 1 .. resolve (the host form drains the stream behind pass 1 to read its counters: that wait is in here)
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+
+int rt_view_adaptive_read(rt_view* v, rt_view_adaptive_info* info) {
+  if (!v) return fail(RT_ERR_INVALID_ARG, "rt_view_adaptive_read: null view");
+  if (!info) return fail(RT_ERR_INVALID_ARG, "rt_view_adaptive_read: null info");
+  if (!v->adaptive) return fail(RT_ERR_INVALID_ARG, "rt_view_adaptive_read: the view has no adaptive workspace (rt_view_enable_adaptive)");
+  HIP_TRY(hipSetDevice(v->device));
+  const int rc = v->done.wait();
+  if (rc != RT_OK) return rc;
+  if (!v->n_refined_read) {
+    HIP_TRY(hipMemcpy(&v->n_refined, v->aws.n_refined, 4, hipMemcpyDeviceToHost));
+    v->n_refined_read = true;
+  }
+  *info = rt_view_adaptive_info{};
+  info->n_refined = v->n_refined, info->n_live_rays = v->n_refined * (v->n_distinct - 1u), info->bytes = v->abuf.cap;
+  info->pass1_ms = v->astage_ms[0], info->classify_ms = v->astage_ms[1], info->partition_ms = v->astage_ms[2];
+  info->pass2_ms = v->astage_ms[3], info->resolve_ms = v->astage_ms[4];
   return RT_OK;
 }
 

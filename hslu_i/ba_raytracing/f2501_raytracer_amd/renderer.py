@@ -71,6 +71,38 @@ class Radiance(NamedTuple):
     t: Any
 
 
+class AdaptiveRadiance(NamedTuple):
+    """The pixel planes of an adaptive view frame (`DeviceScene.render_view(refine=...)`): a Radiance and the mask of the
+    pixels that were refined with all their samples."""
+    rgb: Any
+    valid: Any
+    id: Any
+    t: Any
+    mask: Any
+
+
+class Refine(NamedTuple):
+    """The refine rule of an adaptive view frame (`rt_view_refine`): a pixel takes all its samples when sample 0 differs from a
+    neighbour's by more than the tolerances -- criteria: a combination of "id", "depth", "colour", "every" (a string, an
+    iterable of them, or the RT_REFINE_* bits); depth_tol relative to the nearer hit, colour_tol per linear RGB channel."""
+    criteria: Any = ("depth", "colour")
+    colour_tol: float = 0.05
+    depth_tol: float = 0.05
+
+    BITS = {"id": _abi.RT_REFINE_ID, "depth": _abi.RT_REFINE_DEPTH, "colour": _abi.RT_REFINE_COLOUR, "every": _abi.RT_REFINE_EVERY}
+
+    def struct(self) -> "_abi.rt_view_refine":
+        c = self.criteria
+        if not isinstance(c, int):
+            bits = 0
+            for name in ((c,) if isinstance(c, str) else c):
+                if name not in self.BITS:
+                    raise ValueError(f"criteria must be among {sorted(self.BITS)}, got {name!r}")
+                bits |= self.BITS[name]
+            c = bits
+        return _abi.rt_view_refine(_abi.RT_ABI_VERSION, int(c), float(self.colour_tol), float(self.depth_tol))
+
+
 class RayOrder:
     """Owns an `rt_ray_order*`: a permutation of one batch's rays on one device, which `DeviceScene.trace_rays(order=...)`
     reads the batch through so that rays which are neighbours in space share a wavefront.  The results are those of the
@@ -194,6 +226,19 @@ class DeviceView:
         """rt_view_info: pixels, samples, distinct samples, rays, device bytes, and the stage times of the last host-form frame."""
         info = _abi.rt_view_info()
         _lib.check(_lib.load().rt_view_read(self.handle, None, C.byref(info)))
+        return info.as_dict()
+
+    def enable_adaptive(self) -> "DeviceView":
+        """Allocates the workspace adaptive frames need (`rt_view_enable_adaptive`; idempotent)."""
+        _lib.check(_lib.load().rt_view_enable_adaptive(self.handle))
+        return self
+
+    @property
+    def adaptive_info(self) -> Dict:
+        """rt_view_adaptive_info of the last adaptive frame: refined pixels, live rays of pass 2, workspace bytes, and the
+        stage times of the last host-form frame."""
+        info = _abi.rt_view_adaptive_info()
+        _lib.check(_lib.load().rt_view_adaptive_read(self.handle, C.byref(info)))
         return info.as_dict()
 
     def plane_of(self) -> np.ndarray:
@@ -476,17 +521,24 @@ class DeviceScene:
         return out
 
     def render_view(self, view: DeviceView, cfg: RenderConfig, tuning: Optional[Dict] = None, traversal: int = _abi.RT_TRAVERSAL_BVH,
-                    argb=None, torch_out: bool = False) -> "Radiance":
+                    argb=None, torch_out: bool = False, refine: Optional[Refine] = None) -> "Radiance":
         """A frame of `view` (`rt_render_view*`): its rays are made on the device, traced as `trace_rays` traces them --
         shaded with `cfg`, whose own camera and anti-aliasing are not used: the view's samples are the anti-aliasing -- and
         resolved into pixels with the reference's accumulation.  Returns the per-pixel Radiance planes (rgb, valid, and the id
         and t of sample 0), row-major with row 0 at the top.  argb: optional packed pixels as in trace_rays; pixels without a
         valid sample keep their value.  numpy results (the host entry point; `last_trace_stats` is filled), or with
         torch_out=True (or an argb tensor) tensors on this scene's device, enqueued on torch.cuda.current_stream().
-        With soft shadows every distinct sample of a pixel draws its own light-cloud set."""
+        With soft shadows every distinct sample of a pixel draws its own light-cloud set.
+        refine: a Refine -> an adaptive frame (`rt_render_view_adaptive*`; the view needs `enable_adaptive()`): sample 0 of
+        every pixel, all samples only where the rule finds an edge.  Returns an AdaptiveRadiance: the planes plus `.mask`."""
         p = self._shading_params(cfg, traversal, tuning)
         n = view.width * view.height
         lib = _lib.load()
+        spec = (("rgb", "float32", 3), ("valid", "bool", 1), ("id", "int32", 1), ("t", "float32", 1))
+        result = Radiance
+        if refine is not None:
+            rf = refine.struct()
+            spec, result = spec + (("mask", "bool", 1),), AdaptiveRadiance
         if torch_out or (argb is not None and not isinstance(argb, np.ndarray)):
             import torch
 
@@ -495,16 +547,23 @@ class DeviceScene:
                                          tuple(argb.shape) == (n,) and argb.is_contiguous()):
                 raise ValueError(f"argb must be a contiguous int32 tensor of shape ({n},) on {dev}")
             like = torch.empty(0, device=dev)
-            out, ptr = self._planes(Radiance, like, n, ("rgb", "float32", 3), ("valid", "bool", 1), ("id", "int32", 1), ("t", "float32", 1))
+            out, ptr = self._planes(result, like, n, *spec)
             r = _abi.rt_ray_radiance(ptr(out.rgb), ptr(out.valid), ptr(out.id), ptr(out.t), ptr(argb) if argb is not None else None)
-            _lib.check(lib.rt_render_view_device(self.handle, view.handle, C.byref(p), C.byref(r), self._stream_of(like)))
+            if refine is not None:
+                _lib.check(lib.rt_render_view_adaptive_device(self.handle, view.handle, C.byref(p), C.byref(rf), C.byref(r), ptr(out.mask),
+                                                              self._stream_of(like)))
+            else:
+                _lib.check(lib.rt_render_view_device(self.handle, view.handle, C.byref(p), C.byref(r), self._stream_of(like)))
             return out
         if argb is not None and not (argb.dtype == np.uint32 and argb.shape == (n,) and argb.flags["C_CONTIGUOUS"]):
             raise ValueError(f"argb must be a contiguous uint32 array of shape ({n},)")
-        out, ptr = self._planes(Radiance, np.empty(0), n, ("rgb", "float32", 3), ("valid", "bool", 1), ("id", "int32", 1), ("t", "float32", 1))
+        out, ptr = self._planes(result, np.empty(0), n, *spec)
         r = _abi.rt_ray_radiance(ptr(out.rgb), ptr(out.valid), ptr(out.id), ptr(out.t), ptr(argb) if argb is not None else None)
         st = _abi.rt_stats()
-        _lib.check(lib.rt_render_view(self.handle, view.handle, C.byref(p), C.byref(r), C.byref(st)))
+        if refine is not None:
+            _lib.check(lib.rt_render_view_adaptive(self.handle, view.handle, C.byref(p), C.byref(rf), C.byref(r), ptr(out.mask), C.byref(st)))
+        else:
+            _lib.check(lib.rt_render_view(self.handle, view.handle, C.byref(p), C.byref(r), C.byref(st)))
         self.last_trace_stats = st.as_dict()
         return out
 
@@ -845,7 +904,8 @@ class RaytracerRenderer:
         self.last_stats = st.as_dict()
         return planes
 
-    def render_camera(self, buffer: ImageBuffer, scene, camera, tuning: Optional[Dict] = None, order=False, samples=None) -> Radiance:
+    def render_camera(self, buffer: ImageBuffer, scene, camera, tuning: Optional[Dict] = None, order=False, samples=None,
+                      refine: Optional[Refine] = None) -> Radiance:
         """Renders `scene` as `camera` sees it (anything with width, height and rays() -> (origins, directions), row-major
         with row 0 at the top: camera.PinholeCamera) into `buffer`: the rays go through DeviceScene.trace_rays with this
         renderer's configuration, hit pixels are written, misses keep the buffer's fill.  One ray per pixel -- the
@@ -854,7 +914,10 @@ class RaytracerRenderer:
         (of a camera that does not move relative to its rays' pattern) is reused.  The image is the same.
         samples: None = that path, one ray per pixel made on the host.  "config" (the configuration's anti-aliasing table,
         `camera.view_samples`) or an (n, 2) array of offsets in pixels: the frame goes through a DeviceView (camera needs
-        view_camera()) -- rays made, traced in a device-built order (order=False: none) and resolved on the device."""
+        view_camera()) -- rays made, traced in a device-built order (order=False: none) and resolved on the device.
+        refine: with samples, a Refine: an adaptive frame (all samples only at edges); returns an AdaptiveRadiance."""
+        if refine is not None and samples is None:
+            raise ValueError("refine needs samples: there is nothing to refine with one ray per pixel")
         if buffer.width != camera.width or buffer.height != camera.height:
             raise ValueError(f"buffer is {buffer.width}x{buffer.height}, the camera renders {camera.width}x{camera.height}")
         ds = self.device_scene(scene)
@@ -866,7 +929,9 @@ class RaytracerRenderer:
             smp = _camera.view_samples(self.cfg, _abi.RT_VIEW_PINHOLE) if isinstance(samples, str) and samples == "config" else samples
             view = DeviceView(ds.device, camera.width, camera.height, smp, order="once" if order else "none", camera=camera.view_camera())
             try:
-                out = ds.render_view(view, self.cfg, tuning=tuning, traversal=self.traversal, argb=buffer.buffer)
+                if refine is not None:
+                    view.enable_adaptive()
+                out = ds.render_view(view, self.cfg, tuning=tuning, traversal=self.traversal, argb=buffer.buffer, refine=refine)
             finally:
                 view.close()
             self.last_stats = ds.last_trace_stats

@@ -692,6 +692,72 @@ int rt_view_rays_model(const rt_view_desc* desc, const rt_view_camera* camera, f
 int rt_view_resolve_model(uint32_t n_pixels, uint32_t n_samples, const uint8_t* plane_of, const rt_ray_radiance* rays,
                           const rt_ray_radiance* pixels);
 
+/* ---- adaptive camera views: all samples only where sample 0 shows an edge ----------------------------------------------------
+ *
+ * rt_render_view_adaptive_device traces sample 0 of every pixel (plane 0), picks the pixels to refine from what plane 0 saw,
+ * and traces the other distinct samples of those pixels only.  All on the caller's stream, nothing allocated or read back:
+ *   1. pass 1: the generator for plane 0 and a trace of its width * height rays -- batch indices, hence light-cloud keys,
+ *      those of the full view -- through the plane-0 part of the view's order, into base planes the view owns,
+ *   2. classify: one thread per pixel applies the refine rule -> mask,
+ *   3. the sparse generator: ray (u, p) with u >= 1 and mask[p] set as rt_render_view makes it, every other ray dead
+ *      (direction 0),
+ *   4. a stable partition of the view's order by liveness: live rays first, in the order they had,
+ *   5. pass 2: a trace of all n_rays rays through that permutation (dead rays are misses, in whole wavefronts at the tail),
+ *   6. the adaptive resolve.
+ * n_distinct == 1: steps 3 to 5 are skipped.  RT_VIEW_ORDER_ONCE: the first frame builds the order from one run of the full
+ * generator; ALWAYS does so every frame; NONE partitions the identity.
+ *
+ * The refine rule.  Pixel p is refined iff criteria has RT_REFINE_EVERY, or for one of its up to 8 neighbours q in the frame
+ *   any of ID / DEPTH / COLOUR is set and valid0[p] != valid0[q], or
+ *   RT_REFINE_ID      and id0[p] != id0[q]  (ids are canonical object indices: inside a mesh every triangle edge is one), or
+ *   RT_REFINE_DEPTH   and both are valid and NOT |t_p - t_q| <= depth_tol * min(t_p, t_q), or
+ *   RT_REFINE_COLOUR  and both are valid and, in some channel, NOT |c_p - c_q| <= colour_tol
+ * (negated comparisons: a NaN refines; criteria == 0 refines nothing; symmetric: both sides of an edge refine).
+ *
+ * Pixels.  A refined pixel is rt_render_view's pixel, bit for bit.  An unrefined pixel is the resolve formula above with every
+ * sample reading plane 0 (n_samples and scale unchanged): what the full resolve gives a pixel whose samples all agree.  id and
+ * t are those of plane 0; argb is untouched when no contributing sample is valid.  A feature thinner than a pixel that sample
+ * 0 of the pixel and of all its neighbours misses is not found: the method's limit.
+ * Host models, compiled from the kernels' source (csrc/rt_view_adapt.h): rt_view_refine_model, rt_view_resolve_adaptive_model.
+ *
+ * Blocking, validation of `shading`, the one-render-call-per-scene rule and the behaviour with REFLECTIONS / REFRACTIONS are
+ * the trace's, twice.  rt_stats of the host form: the two traces summed.
+ * Refused with RT_ERR_INVALID_ARG before any HIP call: a NULL pointer or wrong abi_version; unknown criteria bits; a
+ * tolerance that is negative or NaN; a view without rt_view_enable_adaptive; everything rt_render_view refuses. */
+#define RT_REFINE_ID 1u
+#define RT_REFINE_DEPTH 2u
+#define RT_REFINE_COLOUR 4u
+#define RT_REFINE_EVERY 8u
+typedef struct rt_view_refine {
+  uint32_t abi_version; /* RT_ABI_VERSION */
+  uint32_t criteria;    /* RT_REFINE_* */
+  float colour_tol, depth_tol;
+} rt_view_refine;
+typedef struct rt_view_adaptive_info {
+  uint32_t n_refined, n_live_rays; /* of the last adaptive frame: refined pixels; live rays of pass 2 */
+  uint64_t bytes;                  /* the adaptive workspace (beside rt_view_info.bytes) */
+  double pass1_ms, classify_ms, partition_ms, pass2_ms, resolve_ms; /* rt_render_view_adaptive: device time per stage (partition: with the sparse generator) */
+} rt_view_adaptive_info;
+/* allocates the workspace: base planes (21 bytes per pixel), mask, a second permutation (4 bytes per ray), the plane-0 order,
+ * flags and scan arrays; blocks; idempotent */
+int rt_view_enable_adaptive(rt_view* view);
+/* pixels_dev as rt_render_view_device; mask_dev: [width * height] bytes on the device, nullable */
+int rt_render_view_adaptive_device(rt_scene* scene, rt_view* view, const rt_params* shading, const rt_view_refine* refine,
+                                   const rt_ray_radiance* pixels_dev, uint8_t* mask_dev, void* hip_stream);
+/* HOST planes and mask (nullable); blocks.  stats may be NULL. */
+int rt_render_view_adaptive(rt_scene* scene, rt_view* view, const rt_params* shading, const rt_view_refine* refine,
+                            const rt_ray_radiance* pixels_host, uint8_t* mask_host, rt_stats* stats);
+/* waits for the view's device work */
+int rt_view_adaptive_read(rt_view* view, rt_view_adaptive_info* info);
+/* The host models (no device needed).  plane0: the rgb, valid, id and t of sample 0 of every pixel (all four required);
+ * mask_out [width * height] and n_refined_out nullable. */
+int rt_view_refine_model(uint32_t width, uint32_t height, const rt_view_refine* refine, const rt_ray_radiance* plane0, uint8_t* mask_out,
+                         uint32_t* n_refined_out);
+/* base: plane 0 (all four planes); rays: per-ray rgb and valid of n_distinct * n_pixels rays, plane 0 of them not read (NULL
+ * allowed when every plane_of is 0); pixels as rt_view_resolve_model */
+int rt_view_resolve_adaptive_model(uint32_t n_pixels, uint32_t n_samples, const uint8_t* plane_of, const uint8_t* mask,
+                                   const rt_ray_radiance* base, const rt_ray_radiance* rays, const rt_ray_radiance* pixels);
+
 /* thread-local message for the last non-RT_OK return on this thread */
 const char* rt_last_error(void);
 

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Renders semesterbild on GPU 0 from a viewpoint of the caller's choosing (the reference has one, fixed at compile
 time) and writes a PNG: camera.PinholeCamera -> RaytracerRenderer.render_camera -> rt_trace_rays, or with --aa through a
-device-side view (rt_render_view: rays made, traced and resolved on the device, the configuration's anti-aliasing table).
+device-side view (rt_render_view: rays made, traced and resolved on the device, the configuration's anti-aliasing table);
+--aa --adaptive takes all samples only where the first sample of neighbouring pixels differs (rt_render_view_adaptive).
 
-    render_view.py OUT.png [--eye X,Y,Z] [--target X,Y,Z] [--fov DEG] [--size WxH] [--features f,g] [--model text|text_lowres] [--order] [--aa]
+    render_view.py OUT.png [--eye X,Y,Z] [--target X,Y,Z] [--fov DEG] [--size WxH] [--features f,g] [--model text|text_lowres] [--order] [--aa [--adaptive [--colour-tol X] [--depth-tol X]]]
 
 eye / target are in units of the scene's width, height and depth (the reference's own focus is 0.5,0.5,-1.9; image y points
 down, so the camera's up vector is (0, -1, 0))."""
@@ -16,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from PIL import Image  # noqa: E402
 
 from hslu_i.ba_raytracing.f2501_raytracer_amd import RenderConfig, camera, scenes  # noqa: E402
-from hslu_i.ba_raytracing.f2501_raytracer_amd.renderer import ImageBuffer, RaytracerRenderer  # noqa: E402
+from hslu_i.ba_raytracing.f2501_raytracer_amd.renderer import ImageBuffer, RaytracerRenderer, Refine  # noqa: E402
 
 
 def main():
@@ -31,7 +32,13 @@ def main():
     ap.add_argument("--fill", default="0xFF101010")
     ap.add_argument("--order", action="store_true", help="pack the camera's rays into coherent wavefronts (a ray order built on the device)")
     ap.add_argument("--aa", action="store_true", help="anti-aliased: the configuration's sample table through a device-side view")
+    ap.add_argument("--adaptive", action="store_true", help="with --aa: refine only edge pixels (depth and colour criteria)")
+    ap.add_argument("--colour-tol", type=float, default=Refine().colour_tol, help="largest step of a linear RGB channel between neighbours that is not an edge")
+    ap.add_argument("--depth-tol", type=float, default=Refine().depth_tol, help="largest step of the hit distance, relative to the nearer hit, that is not an edge")
     args = ap.parse_args()
+    if args.adaptive and not args.aa:
+        ap.error("--adaptive needs --aa")
+    refine = Refine(colour_tol=args.colour_tol, depth_tol=args.depth_tol) if args.adaptive else None
     cfg = RenderConfig.from_features([f for f in args.features.split(",") if f])
     scale = (float(cfg.scene_width), float(cfg.scene_height), float(cfg.scene_depth))
     eye = [float(v) * s for v, s in zip(args.eye.split(","), scale)]
@@ -42,8 +49,9 @@ def main():
     buf = ImageBuffer.new_with_color(w, h, int(args.fill, 0))
     r = RaytracerRenderer(cfg)
     t = time.time()
-    out = r.render_camera(buf, scene, cam, order=args.order, samples="config" if args.aa else None)
-    print(f"semesterbild {w}x{h} from eye={eye} features={sorted(cfg.features)} order={args.order} aa={args.aa} valid={float(out.valid.mean()):.3f} "
+    out = r.render_camera(buf, scene, cam, order=args.order, samples="config" if args.aa else None, refine=refine)
+    refined = f" refined={float(out.mask.mean()):.3f}" if args.adaptive else ""
+    print(f"semesterbild {w}x{h} from eye={eye} features={sorted(cfg.features)} order={args.order} aa={args.aa}{refined} valid={float(out.valid.mean()):.3f} "
           f"wall={time.time() - t:.3f}s stats={r.last_stats}")
     Image.fromarray(buf.as_rgb8()).save(args.out)
 

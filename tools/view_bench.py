@@ -10,10 +10,19 @@ text.obj) and config 3's frame shape, 1620 x 1350, one GPU, every figure from th
                             (the reference's camera; merged levels, one set of light clouds per pixel)
       host_rays_1           today's host path for one sample: numpy rays + upload + trace_rays, wall time to a synchronise
 
+  with --adaptive, beside view_16 (order mode once, the steady frame, against once_ms of the same build):
+      adaptive_ms           rt_render_view_adaptive_device end to end with Refine's default rule (DEPTH | COLOUR, 0.05 / 0.05)
+      refined               the fraction of pixels that rule refines
+      adaptive_stages_ms    device time of pass 1, classify, partition (with the sparse generator), pass 2 and the adaptive
+                            resolve (the view's own events, host form, median of 5 frames)
+      sweep / break_even    adaptive_ms over the refined fraction -- criteria 0, colour_tol from loose to tight, EVERY -- and the
+                            fraction at which the adaptive frame costs what the full frame costs (linear between sweep points;
+                            null: adaptive wins, or loses, at every fraction)
+
 Every shape is warmed up, then timed with device events over repeated calls until at least --seconds of work.  The three
 order modes are compared (equal bits) before anything is timed.  Prints one JSON line; two runs give the spread.
 
-    python tools/view_bench.py [--device 0] [--seconds 1.0] [--only direct,soft] [--size 1620x1350]
+    python tools/view_bench.py [--device 0] [--seconds 1.0] [--only direct,soft] [--size 1620x1350] [--adaptive]
 """
 from __future__ import annotations
 
@@ -32,7 +41,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from hslu_i.ba_raytracing.f2501_raytracer_amd import RenderConfig, _abi, _lib, camera, scenes  # noqa: E402
-from hslu_i.ba_raytracing.f2501_raytracer_amd.renderer import DeviceScene, DeviceView  # noqa: E402
+from hslu_i.ba_raytracing.f2501_raytracer_amd.renderer import DeviceScene, DeviceView, Refine  # noqa: E402
 
 
 def time_it(fn, seconds):
@@ -58,12 +67,48 @@ def same(a, b):
     return all(torch.equal(x, y) for x, y in zip(a, b))
 
 
+SWEEP = (("none", Refine(criteria=0)), ("0.5", Refine(colour_tol=0.5)), ("0.2", Refine(colour_tol=0.2)), ("0.1", Refine(colour_tol=0.1)),
+         ("0.05", Refine()), ("0.02", Refine(colour_tol=0.02)), ("0.005", Refine(colour_tol=0.005, depth_tol=0.005)), ("every", Refine(criteria="every")))
+
+
+def adaptive_columns(ds, cfg, view, full_ms, full_frame, seconds):
+    """the three columns of --adaptive for one (shading, camera): `view` is the order-once view that has been timed"""
+    view.enable_adaptive()
+    n = view.width * view.height
+    e = {}
+    every = ds.render_view(view, cfg, torch_out=True, refine=Refine(criteria="every"))
+    e["every_equals_full"] = bool(same(every[:4], full_frame))
+    e["adaptive_ms"] = time_it(lambda: ds.render_view(view, cfg, torch_out=True, refine=Refine()), seconds)
+    info = view.adaptive_info
+    e["refined"] = round(info["n_refined"] / n, 4)
+    e["adaptive_bytes"] = info["bytes"]
+    stages = []
+    for _ in range(6):  # (host form: the view records its stage events; the first frame warms the staging up)
+        ds.render_view(view, cfg, refine=Refine())
+        i = view.adaptive_info
+        stages.append([i[k] for k in ("pass1_ms", "classify_ms", "partition_ms", "pass2_ms", "resolve_ms")])
+    med = np.median(np.array(stages[1:]), axis=0)
+    e["adaptive_stages_ms"] = dict(zip(("pass1", "classify", "partition", "pass2", "resolve"), (round(float(x), 4) for x in med)))
+    sweep = []
+    for label, rf in SWEEP:
+        ms = time_it(lambda: ds.render_view(view, cfg, torch_out=True, refine=rf), seconds / 2)
+        sweep.append((label, round(view.adaptive_info["n_refined"] / n, 4), ms))
+    e["sweep"] = sweep
+    pts = sorted((f, ms) for _, f, ms in sweep)
+    e["break_even"] = None
+    for (f0, m0), (f1, m1) in zip(pts, pts[1:]):
+        if m0 <= full_ms < m1 and f1 > f0:
+            e["break_even"] = round(f0 + (f1 - f0) * (full_ms - m0) / (m1 - m0), 4)
+    return e
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--only", default="direct,soft")
     ap.add_argument("--size", default="1620x1350")
+    ap.add_argument("--adaptive", action="store_true", help="add the adaptive frame, the refined fraction and the stage times beside view_16")
     args = ap.parse_args()
     only = set(args.only.split(","))
     w, h = (int(v) for v in args.size.split("x"))
@@ -94,6 +139,7 @@ def main():
                 info = views["always"].info
                 e = dict(rays=info["n_rays"], distinct=info["n_distinct"], view_bytes=info["bytes"],
                          modes_equal=bool(same(frames["none"], frames["once"]) and same(frames["none"], frames["always"])))
+                full_frame = frames["once"]
                 del frames
                 for mode, v in views.items():
                     e[f"{mode}_ms"] = time_it(lambda: ds.render_view(v, cfg, torch_out=True), args.seconds)
@@ -104,6 +150,9 @@ def main():
                     stages.append((i["rays_ms"], i["order_ms"], st["kernel_ms"] - i["rays_ms"] - i["order_ms"] - i["resolve_ms"], i["resolve_ms"]))
                 med = np.median(np.array(stages[1:]), axis=0)
                 e["stages_ms"] = dict(zip(("generator", "order", "trace", "resolve"), (round(float(x), 4) for x in med)))
+                if args.adaptive and smp is not None:
+                    e.update(adaptive_columns(ds, cfg, views["once"], e["once_ms"], full_frame, args.seconds))
+                del full_frame
                 for v in views.values():
                     v.close()
                 c[label] = e
