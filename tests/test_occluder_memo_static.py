@@ -7,17 +7,11 @@ v_rndne_f32 and no multiply by 2^24 (0x4b800000, RT_FILT_SCALE) in it.  Those co
 refilled, next to the v_readfirstlane_b32 that move the results to scalar registers.  rt_primary_kernel, which keeps no
 memo, still has them in its accumulate blocks (which also shows that the test can see them).  And the kernels keep their
 register budget."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_asm import basic_blocks, compiled
 
 GENERIC = "rt_primary_kernel"
 MEMO = tuple(f"rt_primary_soft{n}_kernel" for n in (10, 19, 28))
@@ -30,22 +24,10 @@ FILT_SCALE = "0x4b800000"
 
 
 @pytest.fixture(scope="module")
-def build(tmp_path_factory):
-    """make asm with an ASM_OUT of its own: (resource remarks per kernel, basic blocks per kernel)"""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    asm = tmp_path_factory.mktemp("memo_asm") / "rt_kernels.s"
-    r = subprocess.run(["make", "-C", CSRC, "asm", "ASM_OUT=" + str(asm)], check=True, capture_output=True, text=True, timeout=900)
-    remarks = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_ZN12_GLOBAL__N_1\d+(\w+?)E", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-    blocks = {}
-    for m in re.finditer(r"^(_ZN12_GLOBAL__N_1\d+(\w+?)E\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1", asm.read_text(), re.S | re.M):
-        # a basic block starts at a label or at a `; %bb.N:` comment
-        blocks[m.group(2)] = re.split(r"^(?:\.LBB\d+_\d+:|; %bb\.\d+:).*$", m.group(3), flags=re.M)
-    return remarks, blocks
+def build():
+    """(resource remarks per kernel, basic blocks per kernel)"""
+    c = compiled("rt_kernels")
+    return c.remarks, {name: basic_blocks(body) for name, body in c.bodies.items()}
 
 
 def accumulate_blocks(blocks):

@@ -1,14 +1,14 @@
 """The kernels of a PLOC rebuild (csrc/rt_ploc.hip) checked on the CPU: hipcc cross-compiles gfx950 here, with the Makefile's
-flags (make asm-ploc).  Every kernel exists, uses no scratch and spills nothing; the distance's floats come from plain
+flags (make asm UNIT=rt_ploc).  Every kernel exists, uses no scratch and spills nothing; the distance's floats come from plain
 multiplies and adds, never from a fused or packed form; no kernel waits for another workgroup; and the sources hold no
 inline assembly."""
 import os
 import re
-import subprocess
 
 import pytest
 
-from test_view_static import CSRC, FUSED, HIPCC
+import kernel_asm
+from kernel_asm import CSRC, FUSED
 
 KERNELS = ("rt_ploc_leaves_kernel", "rt_ploc_nearest_kernel", "rt_ploc_flags_kernel", "rt_ploc_merge_kernel", "rt_ploc_climb_kernel",
            "rt_ploc_gather_kernel", "rt_ploc_emit_kernel")
@@ -17,23 +17,9 @@ COUNTING = ("rt_ploc_climb_kernel", "rt_ploc_emit_kernel")  # leaves, the depth 
 
 
 @pytest.fixture(scope="module")
-def build(tmp_path_factory):
+def build():
     """(resource remarks per kernel, assembly body per kernel, kernel descriptor per kernel)"""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    asm = tmp_path_factory.mktemp("ploc_asm") / "rt_ploc.s"
-    r = subprocess.run(["make", "-C", CSRC, "asm-ploc", "PLOC_ASM_OUT=" + str(asm)], check=True, capture_output=True, text=True, timeout=900)
-    remarks = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_Z\d+(rt_ploc_[a-z]+_kernel)", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-    text = asm.read_text()
-    assert ".amdgcn_target" in text and "gfx950" in text
-    bodies, descriptors = {}, {}
-    for m in re.finditer(r"^(_Z\d+(rt_ploc_[a-z]+_kernel)\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M):
-        bodies[m.group(2)], descriptors[m.group(2)] = m.group(3), m.group(4)
-    return remarks, bodies, descriptors
+    return kernel_asm.build("rt_ploc")
 
 
 def test_every_ploc_kernel_is_built(build):

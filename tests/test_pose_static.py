@@ -1,39 +1,22 @@
 """The kernels of part poses and of the SAH report (csrc/rt_pose.hip, csrc/rt_sah.hip) checked on the CPU: hipcc cross-compiles
-gfx950 here, with the Makefile's flags (make asm-pose).  Both kernels exist, use no scratch and spill nothing; the pose
+gfx950 here, with the Makefile's flags (make asm UNIT=rt_pose, UNIT=rt_sah).  Both kernels exist, use no scratch and spill nothing; the pose
 kernel's float results come from single multiplies and adds and one correctly rounded division, never from a fused or packed
 form the source does not name; and no loop ends on a per-lane condition."""
 import os
 import re
-import subprocess
 
 import pytest
 
-from test_view_static import CSRC, FUSED, HIPCC, division_steps, loops_and_exits
+import kernel_asm
+from kernel_asm import CSRC, FUSED, division_steps, loops_and_exits
 
 KERNELS = {"rt_pose_kernel": "pose", "rt_sah_kernel": "sah"}
 
 
 @pytest.fixture(scope="module")
-def build(tmp_path_factory):
+def build():
     """(resource remarks per kernel, assembly body per kernel, kernel descriptor per kernel)"""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    d = tmp_path_factory.mktemp("pose_asm")
-    out = {"pose": d / "rt_pose.s", "sah": d / "rt_sah.s"}
-    r = subprocess.run(["make", "-C", CSRC, "asm-pose", "POSE_ASM_OUT=" + str(out["pose"]), "SAH_ASM_OUT=" + str(out["sah"])],
-                       check=True, capture_output=True, text=True, timeout=900)
-    remarks = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_Z\d+(rt_[a-z]+_kernel)\w*", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-    bodies, descriptors = {}, {}
-    for which in out.values():
-        text = which.read_text()
-        assert ".amdgcn_target" in text and "gfx950" in text
-        for m in re.finditer(r"^(_Z\d+(rt_[a-z]+_kernel)\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M):
-            bodies[m.group(2)], descriptors[m.group(2)] = m.group(3), m.group(4)
-    return remarks, bodies, descriptors
+    return kernel_asm.build("rt_pose", "rt_sah")
 
 
 def test_both_kernels_are_built(build):
@@ -77,7 +60,7 @@ def test_sah_kernel_adds_once_per_sum_and_workgroup(build):
 
 def test_pose_kernel_fuses_nothing_outside_its_one_division(build):
     """1 / r' is the compiler's correctly rounded division: v_div_scale x 2, v_rcp, Newton steps fused by construction,
-    v_div_fmas, v_div_fixup.  Membership is decided by data flow (test_view_static.division_steps): every fused instruction
+    v_div_fmas, v_div_fixup.  Membership is decided by data flow (kernel_asm.division_steps): every fused instruction
     of the kernel is a step of that division, and no packed float instruction exists."""
     _, bodies, _ = build
     lines = [ln.strip() for ln in bodies["rt_pose_kernel"].splitlines()]

@@ -4,18 +4,16 @@ import ctypes as C
 import os
 import re
 import subprocess
-import tempfile
 
 import numpy as np
-import pytest
 
 from hslu_i.ba_raytracing.f2501_raytracer_amd import _abi, _lib
 
+import kernel_asm
 import ray_query_cases as rq
 
 ROOT = rq.ROOT
 HEADER = os.path.join(ROOT, "include", "rt_hip.h")
-CSRC = os.path.join(ROOT, "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csrc")
 QUERY_FUNCS = ("rt_cast_rays", "rt_cast_rays_device", "rt_any_intersection", "rt_any_intersection_device")
 QUERY_KERNELS = ("rt_query_nearest_kernel", "rt_query_any_kernel")
 
@@ -104,19 +102,7 @@ def test_query_example_links_against_the_abi(tmp_path):
 
 
 def test_query_kernels_compile_without_scratch_and_one_walk_each():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "rt_kernels.s")
-        r = subprocess.run(["make", "-C", CSRC, "asm", "ASM_OUT=" + asm], check=True, capture_output=True, text=True, timeout=900)
-        text = open(asm).read()
-    bodies = {m.group(2): m.group(3) for m in re.finditer(
-        r"^(_ZN12_GLOBAL__N_1\d+(\w+?)E\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1", text, re.S | re.M)}
-    remarks = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_ZN12_GLOBAL__N_1\d+(\w+?)E", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
+    remarks, bodies, _ = kernel_asm.build("rt_kernels")
     for name in QUERY_KERNELS:
         assert name in bodies, (name, sorted(bodies))
         assert len(re.findall(r"s_andn2_b64 exec, exec,", bodies[name])) <= 1, name

@@ -1,14 +1,14 @@
 """The kernels of a device-side BVH rebuild (csrc/rt_rebuild.hip) checked on the CPU: hipcc cross-compiles gfx950 here, with the
-Makefile's flags (make asm-rebuild).  Every kernel exists, uses no scratch and spills nothing; the key kernel's floats come
+Makefile's flags (make asm UNIT=rt_rebuild).  Every kernel exists, uses no scratch and spills nothing; the key kernel's floats come
 from single multiplies, adds and one correctly rounded division per axis, never from a fused or packed form the source does
 not name; no kernel waits for another workgroup; and the sources hold no inline assembly."""
 import os
 import re
-import subprocess
 
 import pytest
 
-from test_view_static import CSRC, FUSED, HIPCC, division_steps
+import kernel_asm
+from kernel_asm import CSRC, FUSED, division_steps
 
 KERNELS = ("rt_lbvh_frame_kernel", "rt_lbvh_keys_kernel", "rt_lbvh_karras_kernel", "rt_lbvh_depth_kernel", "rt_lbvh_gather_kernel",
            "rt_lbvh_emit_kernel", "rt_lbvh_single_kernel")
@@ -16,23 +16,9 @@ SOURCES = ("rt_rebuild.hip", "rt_rebuild.cpp", "rt_lbvh.h")
 
 
 @pytest.fixture(scope="module")
-def build(tmp_path_factory):
+def build():
     """(resource remarks per kernel, assembly body per kernel, kernel descriptor per kernel)"""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    asm = tmp_path_factory.mktemp("rebuild_asm") / "rt_rebuild.s"
-    r = subprocess.run(["make", "-C", CSRC, "asm-rebuild", "REBUILD_ASM_OUT=" + str(asm)], check=True, capture_output=True, text=True, timeout=900)
-    remarks = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_Z\d+(rt_lbvh_[a-z]+_kernel)", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-    text = asm.read_text()
-    assert ".amdgcn_target" in text and "gfx950" in text
-    bodies, descriptors = {}, {}
-    for m in re.finditer(r"^(_Z\d+(rt_lbvh_[a-z]+_kernel)\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M):
-        bodies[m.group(2)], descriptors[m.group(2)] = m.group(3), m.group(4)
-    return remarks, bodies, descriptors
+    return kernel_asm.build("rt_rebuild")
 
 
 def test_every_rebuild_kernel_is_built(build):
@@ -56,7 +42,7 @@ def test_kernel_uses_no_scratch_and_spills_nothing(build, name):
 def test_key_kernel_has_no_fused_multiply_add_of_its_own(build):
     """centre = 0.5 (min + max) and cell = (c - lo) / extent * 1024: adds, multiplies and, once per axis, the compiler's
     correctly rounded division -- v_div_scale x 2, v_rcp, Newton steps fused by construction, v_div_fmas, v_div_fixup.
-    Membership is decided by data flow (test_view_static.division_steps): every fused instruction of the kernel is a step
+    Membership is decided by data flow (kernel_asm.division_steps): every fused instruction of the kernel is a step
     of one of the three divisions, and no packed float instruction exists.  The frame kernel divides nothing and fuses nothing."""
     _, bodies, _ = build
     lines = [ln.strip() for ln in bodies["rt_lbvh_keys_kernel"].splitlines()]

@@ -5,16 +5,7 @@ registers, and what does not fit goes to scratch (HBM write-back) or, for SGPRs,
 with one v_readlane per value.  The kernel arguments are re-read from the kernarg segment where the loops use them
 (kernarg_fresh in rt_kernels.hip), and the view direction waits in the LDS stash; this test holds the resulting budget, so
 that a change that adds pressure to the light loop fails here, at build time, rather than as a slower frame on the GPU."""
-import os
-import re
-import shutil
-import subprocess
-import tempfile
-
-import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csrc")
+from kernel_asm import compiled
 
 # kernel -> (occupancy in waves per SIMD, SGPR spills, VGPR spills, scratch bytes per lane: each at most).
 # Before this budget existed: 6 / 169 / 49 / 108.  The SGPRs still spilled sit in lanes 0-16 of one VGPR (v79); by where
@@ -33,26 +24,9 @@ BUDGET = {
 OCCUPANCY = {"rt_primary_stream_kernel": 6, "rt_primary_pre_kernel": 6, "rt_shade_kernel": 6}
 
 
-def _remarks():
-    if not shutil.which("hipcc") and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc")
-    # make asm: the same flags as the library, plus -Rpass-analysis=kernel-resource-usage (the remarks go to stderr); the
-    # assembly goes to a file of its own, not to csrc/rt_kernels.s, which test_isa_invariants.py reads
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["make", "-C", CSRC, "asm", "ASM_OUT=" + os.path.join(tmp, "rt_kernels.s")], check=True,
-                           capture_output=True, text=True, timeout=900)
-    out = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_ZN12_GLOBAL__N_1\d+(\w+?)E", block)
-        if not m:
-            continue
-        fields = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-        out[m.group(1)] = fields
-    return out
-
-
 def test_primary_kernel_register_budget():
-    res = _remarks()
+    # make asm: the same flags as the library, plus -Rpass-analysis=kernel-resource-usage (the remarks go to stderr)
+    res = compiled("rt_kernels").remarks
     for name, (occ, sgpr_spill, vgpr_spill, scratch) in BUDGET.items():
         assert name in res, (name, sorted(res))
         f = res[name]

@@ -1,38 +1,24 @@
 """The kernels of skinned meshes (csrc/rt_skin.hip) checked on the CPU: hipcc cross-compiles gfx950 here, with the Makefile's
-flags (make asm-skin).  The three kernels exist, use no scratch, no LDS and no atomics, spill nothing and contain no loop
+flags (make asm UNIT=rt_skin).  The three kernels exist, use no scratch, no LDS and no atomics, spill nothing and contain no loop
 (the influence loop is unrolled); the vertex kernel and the vertex-normal triangle kernel contain no fused or packed float
 instruction.  The face kernel is exempt from that one check: its normal is specified with two fma, a division and a square
 root.  Nothing else about the instruction stream is asserted."""
 import os
 import re
-import subprocess
 
 import pytest
 
-from test_view_static import CSRC, FUSED, HIPCC, loops_and_exits
+import kernel_asm
+from kernel_asm import CSRC, FUSED, loops_and_exits
 
 KERNELS = ("rt_skin_vertex_kernel", "rt_skin_triangle_kernel", "rt_skin_face_kernel")
 UNFUSED = ("rt_skin_vertex_kernel", "rt_skin_triangle_kernel")
 
 
 @pytest.fixture(scope="module")
-def build(tmp_path_factory):
+def build():
     """(resource remarks per kernel, assembly body per kernel, kernel descriptor per kernel)"""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    asm = tmp_path_factory.mktemp("skin_asm") / "rt_skin.s"
-    r = subprocess.run(["make", "-C", CSRC, "asm-skin", "SKIN_ASM_OUT=" + str(asm)], check=True, capture_output=True, text=True, timeout=900)
-    remarks = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_Z\d+(rt_skin_[a-z]+_kernel)\w*", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-    text = asm.read_text()
-    assert ".amdgcn_target" in text and "gfx950" in text
-    bodies, descriptors = {}, {}
-    for m in re.finditer(r"^(_Z\d+(rt_skin_[a-z]+_kernel)\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M):
-        bodies[m.group(2)], descriptors[m.group(2)] = m.group(3), m.group(4)
-    return remarks, bodies, descriptors
+    return kernel_asm.build("rt_skin")
 
 
 def test_the_three_kernels_are_built(build):

@@ -7,39 +7,23 @@ only, the scalar 64-byte node fetch.  And the host must send a frame to one only
 with holds for that frame (rt_primary_variant, rt_internal.h): the rule is compiled into a small host-only probe here."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
 
 import pytest
 
 from hslu_i.ba_raytracing.f2501_raytracer_amd import RenderConfig, scenes
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_asm import CSRC, HIPCC, ROOT, compiled, divergent_loops
 
 GENERIC = "rt_primary_kernel"
 SPECIALISED = tuple(f"rt_primary_soft{n}{t}_kernel" for n in (10, 19, 28) for t in ("", "_flags"))
 
 
 @pytest.fixture(scope="module")
-def build(tmp_path_factory):
-    """make asm with an ASM_OUT of its own: (resource remarks per kernel, assembly body per kernel)"""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    asm = tmp_path_factory.mktemp("spec_asm") / "rt_kernels.s"
-    r = subprocess.run(["make", "-C", CSRC, "asm", "ASM_OUT=" + str(asm)], check=True, capture_output=True, text=True, timeout=900)
-    remarks = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_ZN12_GLOBAL__N_1\d+(\w+?)E", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-    bodies = {}
-    for m in re.finditer(r"^(_ZN12_GLOBAL__N_1\d+(\w+?)E\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1", asm.read_text(), re.S | re.M):
-        bodies[m.group(2)] = m.group(3)
-    return remarks, bodies
+def build():
+    """(resource remarks per kernel, assembly body per kernel)"""
+    c = compiled("rt_kernels")
+    return c.remarks, c.bodies
 
 
 def test_every_specialised_kernel_is_built(build):
@@ -61,7 +45,7 @@ def test_specialised_kernel_keeps_occupancy_and_spills_no_more_than_the_generic(
 @pytest.mark.parametrize("name", SPECIALISED)
 def test_specialised_kernel_has_uniform_loops_and_scalar_node_fetches(build, name):
     _, bodies = build
-    n = len(re.findall(r"s_andn2_b64 exec, exec,", bodies[name]))
+    n = divergent_loops(bodies[name])
     assert n == 0, f"{name}: {n} divergent loops: some walk or sample loop branches on a per-lane value"
     assert "s_load_dwordx16" in bodies[name], f"{name}: no 64-byte scalar node fetch (a walk lost its uniformity)"
 

@@ -5,20 +5,19 @@ import ctypes as C
 import os
 import re
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from hslu_i.ba_raytracing.f2501_raytracer_amd import RenderConfig, _abi, _lib, camera, scenes
 
+import kernel_asm
 import oracle_lib
 import ray_query_cases as rq
 import trace_rays_cases as tr
 
 ROOT = rq.ROOT
 HEADER = os.path.join(ROOT, "include", "rt_hip.h")
-CSRC = os.path.join(ROOT, "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csrc")
 TRACE_FUNCS = ("rt_trace_rays", "rt_trace_rays_device")
 RAY_KERNELS = ("rt_rays_kernel", "rt_rays_stream_kernel")
 
@@ -252,20 +251,8 @@ PINNED = {
 @pytest.fixture(scope="module")
 def compiled():
     """(kernel -> assembly body, kernel -> mangled symbol, kernel -> resource-usage fields) of one `make asm`."""
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "rt_kernels.s")
-        r = subprocess.run(["make", "-C", CSRC, "asm", "ASM_OUT=" + asm], check=True, capture_output=True, text=True, timeout=900)
-        text = open(asm).read()
-    bodies, symbols, remarks = {}, {}, {}
-    for m in re.finditer(r"^(_ZN12_GLOBAL__N_1\d+(\w+?)E\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1", text, re.S | re.M):
-        bodies[m.group(2)], symbols[m.group(2)] = m.group(3), m.group(1)
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_ZN12_GLOBAL__N_1\d+(\w+?)E", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-    return bodies, symbols, remarks
+    c = kernel_asm.compiled("rt_kernels")
+    return c.bodies, c.symbols, c.remarks
 
 
 def test_ray_kernels_are_uniform_walks_at_six_waves(compiled):

@@ -1,22 +1,16 @@
 """The kernels of adaptive camera views (csrc/rt_view_adapt.hip) checked on the CPU: hipcc cross-compiles gfx950 here, with
-the Makefile's flags (make asm-view-adapt).  Held to the bar tests/test_view_static.py sets for the view kernels: every
+the Makefile's flags (make asm UNIT=rt_view_adapt).  Held to the bar tests/test_view_static.py sets for the view kernels: every
 kernel exists, uses no scratch and spills nothing; its VGPRs allow 8 waves per SIMD (at most 64: streaming kernels that hide
 memory latency with occupancy); no loop ends on a per-lane condition; the float results of the classify and the resolve come
 from single multiplies and adds.  What differs from the view kernels is stated per kernel: the partition ranks across the
 four wavefronts of a workgroup through 16 bytes of LDS, and the classify adds one word per wavefront with one atomic."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-from test_view_static import FUSED, loops_and_exits
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+import kernel_asm
+from kernel_asm import CSRC, FUSED, loops_and_exits
 
 KERNELS = ("rt_view_classify_kernel", "rt_view_sparse_rays_kernel", "rt_view_flags_kernel", "rt_partition_count_kernel",
            "rt_partition_scatter_kernel", "rt_view_resolve_adaptive_kernel")
@@ -25,23 +19,9 @@ MAX_VGPRS = 64  # 512 / 64 = 8 waves per SIMD
 
 
 @pytest.fixture(scope="module")
-def build(tmp_path_factory):
+def build():
     """(resource remarks per kernel, assembly body per kernel, kernel descriptor per kernel)"""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    asm = tmp_path_factory.mktemp("view_adapt_asm") / "rt_view_adapt.s"
-    r = subprocess.run(["make", "-C", CSRC, "asm-view-adapt", "VIEW_ADAPT_ASM_OUT=" + str(asm)], check=True, capture_output=True, text=True, timeout=900)
-    remarks = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_ZN12_GLOBAL__N_1\d+(rt_[a-z_]+_kernel)E", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-    text = asm.read_text()
-    assert ".amdgcn_target" in text and "gfx950" in text
-    bodies, descriptors = {}, {}
-    for m in re.finditer(r"^(_ZN12_GLOBAL__N_1\d+(rt_[a-z_]+_kernel)E\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M):
-        bodies[m.group(2)], descriptors[m.group(2)] = m.group(3), m.group(4)
-    return remarks, bodies, descriptors
+    return kernel_asm.build("rt_view_adapt")
 
 
 def test_all_adaptive_kernels_are_built(build):

@@ -1,42 +1,22 @@
 """The kernels of camera views (csrc/rt_view.hip) checked on the CPU: hipcc cross-compiles gfx950 here, with the Makefile's
-flags (make asm-view).  Both kernels exist, use no scratch and spill nothing; their float results come from single
+flags (make asm UNIT=rt_view).  Both kernels exist, use no scratch and spill nothing; their float results come from single
 multiplies, adds and correctly rounded divisions, never from a fused or packed form the source does not name; and no loop
 ends on a per-lane condition."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+import kernel_asm
+from kernel_asm import CSRC, FUSED, division_steps, loops_and_exits
 
 KERNELS = ("rt_view_rays_kernel", "rt_view_resolve_kernel")
-# float forms that fuse or pack (v_mad_u64_u32 and its kin are address arithmetic: only float forms count)
-FUSED = r"\b(v_(?:fma|fmac|mad|mac|madak|madmk|fmaak|fmamk|dot\d)_(?:legacy_)?f\d+\w*|v_pk_\w+)"
 
 
 @pytest.fixture(scope="module")
-def build(tmp_path_factory):
+def build():
     """(resource remarks per kernel, assembly body per kernel, kernel descriptor per kernel)"""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    asm = tmp_path_factory.mktemp("view_asm") / "rt_view.s"
-    r = subprocess.run(["make", "-C", CSRC, "asm-view", "VIEW_ASM_OUT=" + str(asm)], check=True, capture_output=True, text=True, timeout=900)
-    remarks = {}
-    for block in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_ZN12_GLOBAL__N_1\d+(rt_view_[a-z]+_kernel)E", block)
-        if m:
-            remarks[m.group(1)] = dict((k.strip(), int(v)) for k, v in re.findall(r"remark:\s+([\w /\[\]]+?): (\d+) \[", block))
-    text = asm.read_text()
-    assert ".amdgcn_target" in text and "gfx950" in text
-    bodies, descriptors = {}, {}
-    for m in re.finditer(r"^(_ZN12_GLOBAL__N_1\d+(rt_view_[a-z]+_kernel)E\w*):.*?\n(.*?)^\s*\.amdhsa_kernel \1\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M):
-        bodies[m.group(2)], descriptors[m.group(2)] = m.group(3), m.group(4)
-    return remarks, bodies, descriptors
+    return kernel_asm.build("rt_view")
 
 
 def test_both_view_kernels_are_built(build):
@@ -66,26 +46,6 @@ def test_resolve_kernel_has_no_fused_or_packed_arithmetic(build):
     assert not re.search(r"\bv_div_|\bv_rcp_f32", bodies["rt_view_resolve_kernel"]), "the sample weight is computed on the host"
 
 
-def division_steps(lines, fmas_at):
-    """The instructions that compute the quotient a v_div_fmas_f32 at line `fmas_at` finishes: its operands' definitions
-    followed backwards, register by register, up to and including the v_div_scale_f32 that start the sequence (what those
-    read -- numerator and denominator -- is not part of the division).  -> sorted line numbers"""
-    regs = lambda ln: re.findall(r"\bv\d+\b", ln.split(None, 1)[1]) if " " in ln else []  # noqa: E731
-    steps, todo = set(), [(fmas_at, r) for r in regs(lines[fmas_at])[1:]]
-    while todo:
-        before, reg = todo.pop()
-        at = next((k for k in range(before - 1, -1, -1) if lines[k].startswith("v_") and regs(lines[k])[:1] == [reg]), None)
-        assert at is not None, (lines[before], reg)
-        if at in steps:
-            continue
-        steps.add(at)
-        if not lines[at].startswith("v_div_scale_f32"):
-            # (v_fmac and v_div_fmas accumulate into their destination: it is an operand too)
-            srcs = regs(lines[at]) if lines[at].startswith("v_fmac") else regs(lines[at])[1:]
-            todo.extend((at, r) for r in srcs)
-    return sorted(steps)
-
-
 def test_rays_kernel_fuses_nothing_outside_its_two_divisions(build):
     """The generator divides twice (a and b, by the image height).  The compiler's correctly rounded division is a sequence
     v_div_scale x 2, v_rcp, Newton steps, v_div_fmas, v_div_fixup whose Newton steps are fused by construction; every other
@@ -111,55 +71,6 @@ def test_rays_kernel_fuses_nothing_outside_its_two_divisions(build):
     assert not set(divisions[0]) & set(divisions[1])
     outside = [(i, f) for i, f in fused if i not in divisions[0] and i not in divisions[1]]
     assert not outside, outside
-
-
-def loops_and_exits(body):
-    """The control-flow graph of a kernel's assembly -- blocks end at labels and behind branches -- and its loops: the sets of
-    blocks that reach one another.  -> [(blocks of the loop, the conditional branches that can leave it)]"""
-    blocks, cur = [], {"label": None, "ops": []}
-    for ln in body.splitlines():
-        m = re.match(r"^(\.LBB\d+_\d+):", ln)
-        if m:
-            blocks.append(cur)
-            cur = {"label": m.group(1), "ops": []}
-            continue
-        m = re.match(r"^\s*(s_cbranch_\w+|s_branch|s_endpgm)\b\s*(\.LBB\d+_\d+)?", ln)
-        if m:
-            cur["ops"].append((m.group(1), m.group(2)))
-            blocks.append(cur)
-            cur = {"label": None, "ops": []}
-    blocks.append(cur)
-    index = {b["label"]: i for i, b in enumerate(blocks) if b["label"]}
-    succ = []
-    for i, b in enumerate(blocks):
-        last = b["ops"][-1] if b["ops"] else (None, None)
-        out = set()
-        if last[0] not in ("s_branch", "s_endpgm") and i + 1 < len(blocks):
-            out.add(i + 1)
-        if last[1]:
-            out.add(index[last[1]])
-        succ.append(out)
-
-    def reach(i):
-        seen, todo = set(), list(succ[i])
-        while todo:
-            j = todo.pop()
-            if j not in seen:
-                seen.add(j)
-                todo.extend(succ[j])
-        return seen
-
-    reached = [reach(i) for i in range(len(blocks))]
-    loops, done = [], set()
-    for i in range(len(blocks)):
-        if i in done or i not in reached[i]:
-            continue
-        members = {j for j in reached[i] if i in reached[j]}
-        done |= members
-        exits = [blocks[j]["ops"][-1][0] for j in members if blocks[j]["ops"] and blocks[j]["ops"][-1][0].startswith("s_cbranch") and
-                 not succ[j] <= members]
-        loops.append((members, exits))
-    return loops
 
 
 def test_no_loop_ends_on_a_per_lane_condition(build):
