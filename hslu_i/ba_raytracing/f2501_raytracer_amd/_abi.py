@@ -197,6 +197,14 @@ class rt_view_adaptive_info(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+RT_VIEW_LENS_MAX_SPREAD = 16
+
+
+class rt_view_lens(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("spread", C.c_uint32), ("aperture", C.c_float), ("focus_distance", C.c_float),
+                ("coc_tol", C.c_float), ("reserved", C.c_uint32)]
+
+
 RT_UPDATE_INVALIDATES_RECEIVER_TABLES, RT_UPDATE_INVALIDATES_TILE_COSTS, RT_UPDATE_INVALIDATES_QUEUE_SIZES = 1, 2, 4
 
 

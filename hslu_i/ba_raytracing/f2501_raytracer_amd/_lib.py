@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
-                   rt_bvh_quality, rt_pose_desc, rt_rebuild_desc, rt_rebuild_info, rt_rebuild_report, rt_skin_desc, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_adaptive_info, rt_view_camera, rt_view_desc, rt_view_info, rt_view_refine)
+                   rt_bvh_quality, rt_pose_desc, rt_rebuild_desc, rt_rebuild_info, rt_rebuild_report, rt_skin_desc, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_adaptive_info, rt_view_camera, rt_view_desc, rt_view_info, rt_view_lens, rt_view_refine)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_HIP_LIB selects a diagnostic build of the same library (tools/, A/B timing); default: in-tree
@@ -24,6 +24,7 @@ EXPORTS = (
     "rt_view_read", "rt_view_rays_model", "rt_view_resolve_model",
     "rt_view_enable_adaptive", "rt_render_view_adaptive_device", "rt_render_view_adaptive", "rt_view_adaptive_read", "rt_view_refine_model",
     "rt_view_resolve_adaptive_model",
+    "rt_view_create_lens", "rt_view_set_lens", "rt_view_lens_rays_model", "rt_view_defocus_model",
     "rt_pose_create", "rt_pose_destroy", "rt_pose_geometry_device", "rt_pose_apply_device", "rt_pose_apply", "rt_pose_read", "rt_pose_model",
     "rt_skin_create", "rt_skin_destroy", "rt_skin_geometry_device", "rt_skin_apply_device", "rt_skin_apply", "rt_skin_read", "rt_skin_model",
     "rt_scene_bvh_quality", "rt_scene_rebuild", "rt_scene_rebuild_device", "rt_scene_rebuild_with", "rt_scene_rebuild_with_device",
@@ -159,6 +160,16 @@ def load():
     lib.rt_view_resolve_adaptive_model.restype = C.c_int
     lib.rt_view_resolve_adaptive_model.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(rt_ray_radiance), C.POINTER(rt_ray_radiance),
                                                    C.POINTER(rt_ray_radiance)]
+    lib.rt_view_create_lens.restype = C.c_int
+    lib.rt_view_create_lens.argtypes = [C.POINTER(rt_view_desc), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.rt_view_set_lens.restype = C.c_int
+    lib.rt_view_set_lens.argtypes = [C.c_void_p, C.POINTER(rt_view_lens)]
+    lib.rt_view_lens_rays_model.restype = C.c_int
+    lib.rt_view_lens_rays_model.argtypes = [C.POINTER(rt_view_desc), C.c_void_p, C.POINTER(rt_view_camera), C.POINTER(rt_view_lens), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.rt_view_defocus_model.restype = C.c_int
+    lib.rt_view_defocus_model.argtypes = [C.POINTER(rt_view_desc), C.POINTER(rt_view_camera), C.POINTER(rt_view_lens), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(C.c_uint32)]
     lib.rt_pose_create.restype = C.c_int
     lib.rt_pose_create.argtypes = [C.POINTER(rt_pose_desc), C.c_int, C.POINTER(C.c_void_p)]
     lib.rt_pose_destroy.restype = None

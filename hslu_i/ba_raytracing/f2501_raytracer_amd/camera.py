@@ -61,6 +61,33 @@ def view_samples(cfg: RenderConfig, kind: int) -> np.ndarray:
     return np.ascontiguousarray(off / np.array([cfg.fw, cfg.fh], np.float32), np.float32)
 
 
+def lens_samples(n: int) -> np.ndarray:
+    """The (n, 2) float32 lens offsets of a thin-lens DeviceView, in unit-disk coordinates: sample 0 at the lens centre -- so
+    that plane 0 of an adaptive frame is the view through it --, sample k at radius sqrt(k / n) and k golden angles: a fixed
+    spiral that covers the disk evenly for every n.  Deterministic."""
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    k = np.arange(n, dtype=np.float64)
+    r, phi = np.sqrt(k / n), k * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.ascontiguousarray(np.stack([r * np.cos(phi), r * np.sin(phi)], axis=1), np.float32)
+
+
+@dataclass(frozen=True)
+class ThinLens:
+    """The lens of a thin-lens DeviceView (`rt_view_lens`): aperture is the lens radius in scene units (0: no lens),
+    focus_distance the distance of the plane in focus, measured along the camera's forward axis.  coc_tol and spread belong to
+    adaptive frames: a pixel whose circle of confusion exceeds coc_tol pixels is refined, together with the pixels its blur
+    reaches, up to `spread` (0 .. 16) pixels away -- wider blur is cut off; coc_tol = inf leaves the mask to the refine rule."""
+
+    aperture: float
+    focus_distance: float
+    coc_tol: float = float("inf")
+    spread: int = 8
+
+    def struct(self) -> "_abi.rt_view_lens":
+        return _abi.rt_view_lens(_abi.RT_ABI_VERSION, int(self.spread), float(self.aperture), float(self.focus_distance), float(self.coc_tol), 0)
+
+
 @dataclass(frozen=True)
 class PinholeCamera:
     """A pinhole at `eye` looking at `target`; `fov_y_deg` is the angle between the top and the bottom EDGE of the image,

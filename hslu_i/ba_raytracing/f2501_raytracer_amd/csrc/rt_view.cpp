@@ -9,13 +9,17 @@
 // Also the host side of adaptive frames (rt_view_enable_adaptive, rt_render_view_adaptive*): the second allocation and the
 // sequence pass 1 -> classify -> sparse generator -> partition -> pass 2 -> adaptive resolve.  Their arithmetic is in
 // rt_view_adapt.h, their kernels in rt_view_adapt.hip, their host models in rt_view_adapt.cpp.
+//
+// And of thin-lens views (rt_view_create_lens, rt_view_set_lens): the lens table and the coc plane in the view's allocation,
+// the choice of the generator (A > 0: the lens generators of rt_view_lens.hip) and the two defocus launches behind the
+// classify.  Their arithmetic is in rt_view_lens.h, their checks and host models in rt_view_lens.cpp.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cstring>
 
 #include "rt_host.h"
-#include "rt_view_adapt.h"
+#include "rt_view_lens.h"
 
 struct rt_view {
   int device = 0;
@@ -44,6 +48,13 @@ struct rt_view {
   uint32_t n_refined = 0;
   bool n_refined_read = true;    // n_refined holds the word of the last adaptive frame
   double astage_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  // a thin lens (rt_view_create_lens): `distinct` holds the pixel offset of every 4-tuple plane, lens_tab its lens offset;
+  // both tables and the coc plane (4 bytes per pixel) are parts of `buf`
+  bool lens = false;
+  float lens_tab[2 * RT_VIEW_MAX_SAMPLES] = {};
+  float *lens_dev = nullptr, *coc = nullptr;
+  float aperture = 0.0f, focus_distance = 1.0f, coc_tol = INFINITY;  // (rt_view_set_lens; A == 0: the pinhole generator)
+  uint32_t spread = 0;
 };
 
 int rt_view_check_desc(const rt_view_desc* d, const char* fn) {
@@ -93,11 +104,13 @@ int view_alloc(rt_view* v) {
   lay.add(n * 12, &v->origin), lay.add(n * 12, &v->direction), lay.add(n * 12, &v->rgb);
   lay.add(n * 4, &v->id), lay.add(n * 4, &v->t), lay.add(n, &v->valid);
   lay.add(sizeof(v->distinct), &v->distinct_dev), lay.add(sizeof(v->plane_of), &v->plane_of_dev);
+  if (v->lens) lay.add(sizeof(v->lens_tab), &v->lens_dev), lay.add((size_t)v->n_pixels * 4, &v->coc);
   int rc = v->buf.ensure(lay.total());
   if (rc != RT_OK) return rc;
   lay.bind(v->buf.p);
   HIP_TRY(hipMemcpy(v->distinct_dev, v->distinct, sizeof(v->distinct), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(v->plane_of_dev, v->plane_of, sizeof(v->plane_of), hipMemcpyHostToDevice));
+  if (v->lens) HIP_TRY(hipMemcpy(v->lens_dev, v->lens_tab, sizeof(v->lens_tab), hipMemcpyHostToDevice));
   if ((rc = v->done.create()) != RT_OK) return rc;
   for (hipEvent_t& e : v->ev) HIP_TRY(hipEventCreate(&e));
   if (v->order_mode != RT_VIEW_ORDER_NONE) {
@@ -122,8 +135,21 @@ void view_free(rt_view* v) {
   delete v;
 }
 
-int rays_enqueue(rt_view* v, float* origin, float* direction, hipStream_t stream) {
-  const hipError_t e = (hipError_t)rt_launch_view_rays(v->cam, v->distinct_dev, v->n_distinct, origin, direction, stream);
+// is the lens on?  (a lens view with A > 0: the lens generators; else the pinhole generator on the planes' pixel offsets)
+bool lens_on(const rt_view* v) { return v->lens && v->aperture > 0.0f; }
+
+// what every call that makes rays refuses for a lens view, before any HIP call
+int check_lens_camera(const rt_view* v, const char* fn) {
+  if (lens_on(v) && v->cam.kind != RT_VIEW_PINHOLE)
+    return fail(RT_ERR_INVALID_ARG, "%s: an RT_VIEW_REFERENCE camera has no lens (aperture %g)", fn, (double)v->aperture);
+  return RT_OK;
+}
+
+// the generator for the first n_planes planes of the view
+int rays_enqueue(rt_view* v, uint32_t n_planes, float* origin, float* direction, hipStream_t stream) {
+  const hipError_t e = (hipError_t)(lens_on(v) ? rt_launch_view_lens_rays(v->cam, v->distinct_dev, v->lens_dev, n_planes, v->aperture,
+                                                                          v->focus_distance, origin, direction, stream)
+                                               : rt_launch_view_rays(v->cam, v->distinct_dev, n_planes, origin, direction, stream));
   if (e != hipSuccess) return fail(RT_ERR_HIP, "view ray generator launch failed: %s", hipGetErrorString(e));
   return RT_OK;
 }
@@ -144,14 +170,14 @@ int check_render(const rt_scene* s, const rt_view* v, const rt_params* p, const 
   // (the trace refuses this too, but behind the generator's launch: a refusal comes before any HIP call)
   if (s->progress_active) return fail(RT_ERR_INVALID_ARG, "%s: a progressive render owns this scene until rt_render_end", fn);
   if (v->device != s->device) return fail(RT_ERR_INVALID_ARG, "%s: the view lives on device %d, the scene on device %d", fn, v->device, s->device);
-  return RT_OK;
+  return check_lens_camera(v, fn);
 }
 
 // generator -> order -> trace -> resolve on `stream`; `out`: DEVICE pixel planes.  timed: record the view's stage events.
 int render_enqueue(rt_scene* s, rt_view* v, const rt_params* p, const rt_ray_radiance* out, hipStream_t stream, bool timed) {
   int rc;
   if (timed) HIP_TRY(hipEventRecord(v->ev[0], stream));
-  if ((rc = rays_enqueue(v, v->origin, v->direction, stream)) != RT_OK) return rc;
+  if ((rc = rays_enqueue(v, v->n_distinct, v->origin, v->direction, stream)) != RT_OK) return rc;
   if (timed) HIP_TRY(hipEventRecord(v->ev[1], stream));
   rt_ray_batch b{};
   b.abi_version = RT_ABI_VERSION, b.n_rays = v->n_rays, b.origin = v->origin, b.direction = v->direction;
@@ -202,13 +228,13 @@ int adaptive_enqueue(rt_scene* s, rt_view* v, const rt_params* p, const rt_view_
   // the order: built from one complete run of the full generator (which makes plane 0 as well); its plane-0 part when it changed
   const bool build = v->order && (v->order_mode == RT_VIEW_ORDER_ALWAYS || !v->order_built);
   if (build) {
-    if ((rc = rays_enqueue(v, v->origin, v->direction, stream)) != RT_OK) return rc;
+    if ((rc = rays_enqueue(v, v->n_distinct, v->origin, v->direction, stream)) != RT_OK) return rc;
     rt_ray_batch all{};
     all.abi_version = RT_ABI_VERSION, all.n_rays = v->n_rays, all.origin = v->origin, all.direction = v->direction;
     if ((rc = rt_ray_order_build_device(v->order, &all, stream)) != RT_OK) return rc;
     v->order_built = true, v->order0_built = false;
-  } else {
-    ADAPT_TRY("view ray generator", rt_launch_view_rays(v->cam, v->distinct_dev, 1u, v->origin, v->direction, stream));
+  } else if ((rc = rays_enqueue(v, 1u, v->origin, v->direction, stream)) != RT_OK) {
+    return rc;
   }
   const uint32_t* order = v->order ? rt_ray_order_perm(v->order) : nullptr;
   if (order && planes && !v->order0_built) {
@@ -230,9 +256,18 @@ int adaptive_enqueue(rt_scene* s, rt_view* v, const rt_params* p, const rt_view_
   HIP_TRY(hipMemsetAsync(w.n_refined, 0, 4, stream));
   ADAPT_TRY("view classify", rt_launch_view_classify(v->width, v->height, rf->criteria, rf->colour_tol, rf->depth_tol, w, mask_out, stream));
   v->n_refined_read = false;
+  if (v->lens && rt_view_defocus_active(v->aperture, v->coc_tol)) {
+    // the defocus criterion: the out-of-focus pixels of plane 0, and the pixels their blur reaches, join the mask
+    ADAPT_TRY("view coc", rt_launch_view_coc(v->cam, v->distinct_dev, v->aperture, v->focus_distance, w.valid0, w.t0, v->coc, stream));
+    ADAPT_TRY("view defocus spread", rt_launch_view_defocus_spread(v->width, v->height, v->spread, v->coc_tol, v->coc, w.mask, mask_out, w.n_refined, stream));
+  }
   if (timed) HIP_TRY(hipEventRecord(v->aev[2], stream));
   if (planes) {
-    ADAPT_TRY("sparse view ray generator", rt_launch_view_sparse_rays(v->cam, v->distinct_dev, v->n_distinct, w.mask, v->origin, v->direction, stream));
+    if (lens_on(v))
+      ADAPT_TRY("sparse lens ray generator", rt_launch_view_lens_sparse_rays(v->cam, v->distinct_dev, v->lens_dev, v->n_distinct, v->aperture,
+                                                                             v->focus_distance, w.mask, v->origin, v->direction, stream));
+    else
+      ADAPT_TRY("sparse view ray generator", rt_launch_view_sparse_rays(v->cam, v->distinct_dev, v->n_distinct, w.mask, v->origin, v->direction, stream));
     ADAPT_TRY("view flags", rt_launch_view_flags(order, v->n_rays, v->n_pixels, w.mask, w.flags, stream));
     ADAPT_TRY("partition", rt_launch_partition(order, w.flags, v->n_rays, v->n_rays, w.counts, w.sums, w.perm2, stream));
   }
@@ -255,23 +290,40 @@ int adaptive_enqueue(rt_scene* s, rt_view* v, const rt_params* p, const rt_view_
 
 extern "C" {
 
-int rt_view_create(const rt_view_desc* d, int device, rt_view** out) {
-  if (!d || !out) return fail(RT_ERR_INVALID_ARG, "rt_view_create: null argument");
+// rt_view_create (lens_samples == nullptr) and rt_view_create_lens
+static int view_create(const rt_view_desc* d, const float* lens_samples, bool lens, int device, rt_view** out, const char* fn) {
+  if (!d || !out) return fail(RT_ERR_INVALID_ARG, "%s: null argument", fn);
   *out = nullptr;
-  int rc = rt_view_check_desc(d, "rt_view_create");
+  int rc = lens ? rt_view_lens_check_desc(d, lens_samples, fn) : rt_view_check_desc(d, fn);
   if (rc != RT_OK) return rc;
   if ((rc = rt_open_device(device)) != RT_OK) return rc;
   rt_view* v = new rt_view();
   v->device = device, v->width = d->width, v->height = d->height, v->n_pixels = d->width * d->height, v->n_samples = d->n_samples;
-  v->order_mode = d->order;
+  v->order_mode = d->order, v->lens = lens;
   v->desc = *d, v->desc.samples = nullptr;
-  v->n_distinct = rt_view_dedup(d->samples, d->n_samples, v->distinct, v->plane_of);
+  v->n_distinct = lens ? rt_view_lens_dedup(d->samples, lens_samples, d->n_samples, v->distinct, v->lens_tab, v->plane_of)
+                       : rt_view_dedup(d->samples, d->n_samples, v->distinct, v->plane_of);
   v->n_rays = v->n_distinct * v->n_pixels;
   if ((rc = view_alloc(v)) != RT_OK) {
     view_free(v);
     return rc;
   }
   *out = v;
+  return RT_OK;
+}
+
+int rt_view_create(const rt_view_desc* d, int device, rt_view** out) { return view_create(d, nullptr, false, device, out, "rt_view_create"); }
+
+int rt_view_create_lens(const rt_view_desc* d, const float* lens_samples, int device, rt_view** out) {
+  return view_create(d, lens_samples, true, device, out, "rt_view_create_lens");
+}
+
+int rt_view_set_lens(rt_view* v, const rt_view_lens* l) {
+  if (!v) return fail(RT_ERR_INVALID_ARG, "rt_view_set_lens: null view");
+  const int rc = rt_view_check_lens(l, "rt_view_set_lens");
+  if (rc != RT_OK) return rc;
+  if (!v->lens) return fail(RT_ERR_INVALID_ARG, "rt_view_set_lens: the view has no lens table (rt_view_create_lens)");
+  v->aperture = l->aperture, v->focus_distance = l->focus_distance, v->coc_tol = l->coc_tol, v->spread = l->spread;
   return RT_OK;
 }
 
@@ -290,8 +342,10 @@ int rt_view_rays_device(rt_view* v, float* origin, float* direction, void* hip_s
   if (!v) return fail(RT_ERR_INVALID_ARG, "%s: null view", fn);
   if (!origin || !direction) return fail(RT_ERR_INVALID_ARG, "%s: origin / direction missing", fn);
   if (!v->has_camera) return fail(RT_ERR_INVALID_ARG, "%s: the view has no camera yet (rt_view_set_camera)", fn);
+  int rc = check_lens_camera(v, fn);
+  if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(v->device));
-  const int rc = rays_enqueue(v, origin, direction, (hipStream_t)hip_stream);
+  rc = rays_enqueue(v, v->n_distinct, origin, direction, (hipStream_t)hip_stream);
   return rc != RT_OK ? rc : v->done.mark((hipStream_t)hip_stream);
 }
 
@@ -300,12 +354,13 @@ int rt_view_rays(rt_view* v, float* origin, float* direction) {
   if (!v) return fail(RT_ERR_INVALID_ARG, "%s: null view", fn);
   if (!origin || !direction) return fail(RT_ERR_INVALID_ARG, "%s: origin / direction missing", fn);
   if (!v->has_camera) return fail(RT_ERR_INVALID_ARG, "%s: the view has no camera yet (rt_view_set_camera)", fn);
+  int rc = check_lens_camera(v, fn);
+  if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(v->device));
   HostCall c;
   c.out(&origin, (size_t)v->n_rays * 12), c.out(&direction, (size_t)v->n_rays * 12);
-  int rc = c.begin();
-  if (rc != RT_OK) return rc;
-  if ((rc = rays_enqueue(v, origin, direction, c.stream)) != RT_OK) return rc;
+  if ((rc = c.begin()) != RT_OK) return rc;
+  if ((rc = rays_enqueue(v, v->n_distinct, origin, direction, c.stream)) != RT_OK) return rc;
   return c.finish();
 }
 

@@ -192,11 +192,15 @@ class DeviceView:
     samples: (n, 2) float32 offsets (None: one ray through the pixel centre) -- pixels from the pixel centre for a pinhole
     camera, the units of `sampling.aa_offsets` for the reference's (`camera.view_samples`).  order: "once" (the first frame
     builds the ray order, later frames reuse it), "always" or "none"; the image is the same.  camera: an `rt_view_camera`
-    (`PinholeCamera.view_camera()`, `camera.reference_view_camera(cfg)`); `set_camera` moves it between frames."""
+    (`PinholeCamera.view_camera()`, `camera.reference_view_camera(cfg)`); `set_camera` moves it between frames.
+
+    lens_samples: (n, 2) float32 lens offsets in unit-disk coordinates, one per sample (`camera.lens_samples(n)`) -> a
+    thin-lens view (`rt_view_create_lens`): `set_lens(camera.ThinLens(aperture, focus_distance))` opens the lens, frames then
+    have depth of field.  lens: a ThinLens set at once.  Without `set_lens`, or with aperture 0, the view is a pinhole's."""
 
     ORDERS = {"once": _abi.RT_VIEW_ORDER_ONCE, "always": _abi.RT_VIEW_ORDER_ALWAYS, "none": _abi.RT_VIEW_ORDER_NONE}
 
-    def __init__(self, device: int, width: int, height: int, samples=None, order: str = "once", camera=None):
+    def __init__(self, device: int, width: int, height: int, samples=None, order: str = "once", camera=None, lens_samples=None, lens=None):
         if order not in self.ORDERS:
             raise ValueError(f"order must be one of {sorted(self.ORDERS)}")
         smp = np.zeros((1, 2), np.float32) if samples is None else np.ascontiguousarray(samples, np.float32)
@@ -205,11 +209,21 @@ class DeviceView:
         lib = _lib.load()
         desc = _abi.rt_view_desc(_abi.RT_ABI_VERSION, int(width), int(height), int(smp.shape[0]), smp.ctypes.data, self.ORDERS[order])
         h = C.c_void_p()
-        _lib.check(lib.rt_view_create(C.byref(desc), int(device), C.byref(h)))
+        if lens_samples is None:
+            if lens is not None:
+                raise ValueError("a lens needs lens_samples")
+            _lib.check(lib.rt_view_create(C.byref(desc), int(device), C.byref(h)))
+        else:
+            ls = np.ascontiguousarray(lens_samples, np.float32)
+            if ls.shape != smp.shape:
+                raise ValueError(f"lens_samples must be {smp.shape} as the samples, got {ls.shape}")
+            _lib.check(lib.rt_view_create_lens(C.byref(desc), ls.ctypes.data, int(device), C.byref(h)))
         self._h = h
         self.device, self.width, self.height, self.n_samples = int(device), int(width), int(height), int(smp.shape[0])
         if camera is not None:
             self.set_camera(camera)
+        if lens is not None:
+            self.set_lens(lens)
 
     @property
     def handle(self) -> C.c_void_p:
@@ -219,6 +233,12 @@ class DeviceView:
 
     def set_camera(self, camera: "_abi.rt_view_camera") -> "DeviceView":
         _lib.check(_lib.load().rt_view_set_camera(self.handle, C.byref(camera)))
+        return self
+
+    def set_lens(self, lens) -> "DeviceView":
+        """The lens of the next frames: a `camera.ThinLens` (or an `rt_view_lens`); a view made with lens_samples only."""
+        st = lens.struct() if hasattr(lens, "struct") else lens
+        _lib.check(_lib.load().rt_view_set_lens(self.handle, C.byref(st)))
         return self
 
     @property
@@ -905,7 +925,7 @@ class RaytracerRenderer:
         return planes
 
     def render_camera(self, buffer: ImageBuffer, scene, camera, tuning: Optional[Dict] = None, order=False, samples=None,
-                      refine: Optional[Refine] = None) -> Radiance:
+                      refine: Optional[Refine] = None, lens=None) -> Radiance:
         """Renders `scene` as `camera` sees it (anything with width, height and rays() -> (origins, directions), row-major
         with row 0 at the top: camera.PinholeCamera) into `buffer`: the rays go through DeviceScene.trace_rays with this
         renderer's configuration, hit pixels are written, misses keep the buffer's fill.  One ray per pixel -- the
@@ -915,9 +935,13 @@ class RaytracerRenderer:
         samples: None = that path, one ray per pixel made on the host.  "config" (the configuration's anti-aliasing table,
         `camera.view_samples`) or an (n, 2) array of offsets in pixels: the frame goes through a DeviceView (camera needs
         view_camera()) -- rays made, traced in a device-built order (order=False: none) and resolved on the device.
-        refine: with samples, a Refine: an adaptive frame (all samples only at edges); returns an AdaptiveRadiance."""
+        refine: with samples, a Refine: an adaptive frame (all samples only at edges); returns an AdaptiveRadiance.
+        lens: with samples, a `camera.ThinLens`: depth of field -- sample k leaves the lens at `camera.lens_samples(n)[k]`; with
+        refine, the lens's coc_tol and spread add the out-of-focus pixels to the refined ones."""
         if refine is not None and samples is None:
             raise ValueError("refine needs samples: there is nothing to refine with one ray per pixel")
+        if lens is not None and samples is None:
+            raise ValueError("a lens needs samples: one ray per pixel goes through the lens centre")
         if buffer.width != camera.width or buffer.height != camera.height:
             raise ValueError(f"buffer is {buffer.width}x{buffer.height}, the camera renders {camera.width}x{camera.height}")
         ds = self.device_scene(scene)
@@ -927,7 +951,8 @@ class RaytracerRenderer:
             if isinstance(order, RayOrder):
                 raise ValueError("a view builds its own ray order: order must be True or False with samples")
             smp = _camera.view_samples(self.cfg, _abi.RT_VIEW_PINHOLE) if isinstance(samples, str) and samples == "config" else samples
-            view = DeviceView(ds.device, camera.width, camera.height, smp, order="once" if order else "none", camera=camera.view_camera())
+            view = DeviceView(ds.device, camera.width, camera.height, smp, order="once" if order else "none", camera=camera.view_camera(),
+                              lens_samples=None if lens is None else _camera.lens_samples(len(smp)), lens=lens)
             try:
                 if refine is not None:
                     view.enable_adaptive()

@@ -758,6 +758,63 @@ int rt_view_refine_model(uint32_t width, uint32_t height, const rt_view_refine* 
 int rt_view_resolve_adaptive_model(uint32_t n_pixels, uint32_t n_samples, const uint8_t* plane_of, const uint8_t* mask,
                                    const rt_ray_radiance* base, const rt_ray_radiance* rays, const rt_ray_radiance* pixels);
 
+/* ---- thin-lens camera views: depth of field from a table of lens offsets, adaptive frames included -----------------------------
+ *
+ * No reference counterpart: its camera is a compile-time pinhole (renderer/mod.rs, raytracer_renderer.rs).  A lens view is a
+ * view with a second table beside the pixel offsets: n_samples lens offsets (lx, ly) in unit-disk coordinates (finite, not
+ * otherwise constrained).  Per frame rt_view_set_lens gives an aperture radius A in scene units and a focus distance F
+ * measured along `forward`.  With a, b and d0 = forward + a right + b up as RT_VIEW_PINHOLE makes them from (sx, sy):
+ *   off[k] = (A lx) right[k] + (A ly) up[k],   origin[k] = eye[k] + off[k],   direction[k] = F d0[k] - off[k]
+ * every operation one correctly rounded fp32 operation, evaluated as written, left to right.  All lens samples of a pixel
+ * offset meet at eye + F d0: the plane at distance F along `forward` is in focus.  RT_VIEW_REFERENCE cameras have no lens.
+ *
+ * Planes.  Two samples share a plane only if all four floats (sx, sy, lx, ly) are bit-identical; the planes are in
+ * first-occurrence order, as those of rt_view_create.  Ray index, layout and light-cloud key stay u * width * height + p; the
+ * 2^27-ray limit counts these planes.  The ray order is still built once (RT_VIEW_ORDER_ONCE) and reused while camera,
+ * aperture and focus change.
+ * A == 0 switches the lens off: the view runs the pinhole generator on the pixel offsets of its planes (any camera kind).  A
+ * lens view without rt_view_set_lens behaves as A == 0.  Every call that takes a view takes a lens view.
+ *
+ * Adaptive frames.  The refine rule above looks for edges in sample 0 and never refines a smooth out-of-focus region, which
+ * then comes out sharp.  With A > 0 and a finite coc_tol a lens view therefore runs the defocus criterion behind the classify
+ * step, on plane 0 -- sample 0 should have lens offset (0, 0), so that plane 0 is the view through the lens centre (not
+ * required).  The circle of confusion of pixel p, in pixels:
+ *   len = sqrt((dx dx + dy dy) + dz dz) of d0 through plane 0's pixel offset,   z = t0[p] / len,
+ *   coc[p] = ((A |z - F|) / (z F)) * (H / (2 tan_half_fov_y)),   0 where plane 0 missed
+ * and pixel p is added to the mask iff some pixel q of the frame with max(|dx|, |dy|) <= spread has
+ *   NOT coc[q] <= coc_tol   and   NOT coc[q] < max(|dx|, |dy|)        (q = p included; negated comparisons: a NaN refines)
+ * -- q is out of focus and its blur reaches p.  n_refined counts every pixel once.  Everything behind the mask is unchanged:
+ * a refined pixel is the full lens frame's pixel bit for bit, an unrefined one reads plane 0 for every sample.
+ * coc_tol = +inf turns the criterion off (the mask is the refine rule's alone).  Blur wider than `spread` pixels (0 .. 16) is
+ * cut off: the method's limit.  The coc plane costs 4 bytes per pixel, allocated by rt_view_create_lens (rt_view_info.bytes).
+ * Host models, compiled from the kernels' source (csrc/rt_view_lens.h): rt_view_lens_rays_model, rt_view_defocus_model.
+ *
+ * Refused with RT_ERR_INVALID_ARG (+ rt_last_error) before any HIP call: a NULL pointer or wrong abi_version; a non-finite
+ * lens offset; more than 2^27 rays; rt_view_set_lens on a view made by rt_view_create; an aperture that is negative, NaN or
+ * inf; a focus_distance that is not finite and positive; a coc_tol that is NaN or negative; spread > 16; a non-zero
+ * `reserved`; rays or a render with A > 0 and an RT_VIEW_REFERENCE camera; everything rt_view_create / rt_render_view refuse. */
+typedef struct rt_view_lens {
+  uint32_t abi_version; /* RT_ABI_VERSION */
+  uint32_t spread;      /* 0 .. 16 pixels: how far the defocus criterion lets a blur reach */
+  float aperture;       /* A: the lens radius in scene units; 0: no lens */
+  float focus_distance; /* F: along `forward`; finite and positive */
+  float coc_tol;        /* pixels; a circle of confusion above it refines; +inf: the criterion is off */
+  uint32_t reserved;    /* 0 */
+} rt_view_lens;
+/* rt_view_create with a lens table: lens_samples [desc->n_samples][2] */
+int rt_view_create_lens(const rt_view_desc* desc, const float* lens_samples, int device, rt_view** out);
+/* validates and stores the lens of the next frames; no allocation, no HIP call */
+int rt_view_set_lens(rt_view* view, const rt_view_lens* lens);
+/* The host models (no device needed).  rt_view_rays_model for a lens view: plane_of and n_distinct count 4-tuples. */
+int rt_view_lens_rays_model(const rt_view_desc* desc, const float* lens_samples, const rt_view_camera* camera, const rt_view_lens* lens,
+                            float* origin, float* direction, uint8_t* plane_of, uint32_t* n_distinct);
+/* The defocus criterion on plane 0 of a desc->width x desc->height frame (desc->samples[0]: its pixel offset; an RT_VIEW_PINHOLE
+ * camera): valid0 and t0 [width * height] are required; coc_out receives the coc plane, mask_inout [width * height] bytes the
+ * pixels the criterion picks (set to 1, the others left alone), n_added_out how many of them were 0 before -- all three
+ * nullable.  With A == 0 or coc_tol = +inf the criterion is off: coc_out is zeroed and nothing is added. */
+int rt_view_defocus_model(const rt_view_desc* desc, const rt_view_camera* camera, const rt_view_lens* lens, const uint8_t* valid0,
+                          const float* t0, float* coc_out, uint8_t* mask_inout, uint32_t* n_added_out);
+
 /* thread-local message for the last non-RT_OK return on this thread */
 const char* rt_last_error(void);
 

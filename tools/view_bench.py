@@ -19,10 +19,23 @@ text.obj) and config 3's frame shape, 1620 x 1350, one GPU, every figure from th
                             fraction at which the adaptive frame costs what the full frame costs (linear between sweep points;
                             null: adaptive wins, or loses, at every fraction)
 
+  with --lens, for the pinhole camera (a reference camera has no lens), the configuration's 16 pixel offsets and
+  `camera.lens_samples(16)` -- 16 planes where view_16 has 9 --, order mode once:
+      plain_config16        view_16 again (the configuration's table on a plain view: 9 planes), timed beside the others
+      plain_16_planes       a plain view of 16 distinct pixel offsets: frame and generator time -- the parent's pinhole path at
+                            the lens view's ray count
+      lens_off / lens_on    the lens view with A == 0 (the pinhole generator on its planes) and with the lens open: frame time,
+                            generator time (the view's own events, host form, median of 5 frames)
+      adaptive              per aperture (0.5 % and 2 % of the focus distance, focused on the camera's target): the adaptive
+                            lens frame with coc_tol 1 pixel and spread 8 against the full lens frame, its refined share, the
+                            share the refine rule alone gives (coc_tol = inf), and the classify stage with and without the coc
+                            and spread kernels (their cost is the difference), and that stage at spread 0, 4, 8 and 16
+  --lens-only skips every column but these (a short run for the lens figures alone).
+
 Every shape is warmed up, then timed with device events over repeated calls until at least --seconds of work.  The three
 order modes are compared (equal bits) before anything is timed.  Prints one JSON line; two runs give the spread.
 
-    python tools/view_bench.py [--device 0] [--seconds 1.0] [--only direct,soft] [--size 1620x1350] [--adaptive]
+    python tools/view_bench.py [--device 0] [--seconds 1.0] [--only direct,soft] [--size 1620x1350] [--adaptive] [--lens [--lens-only]]
 """
 from __future__ import annotations
 
@@ -102,6 +115,71 @@ def adaptive_columns(ds, cfg, view, full_ms, full_frame, seconds):
     return e
 
 
+def stage_medians(ds, cfg, view, keys, adaptive=False, refine=None):
+    """median over 5 host-form frames (after one that warms the staging up) of the view's own stage times"""
+    rows = []
+    for _ in range(6):
+        ds.render_view(view, cfg, refine=refine)
+        i = view.adaptive_info if adaptive else view.info
+        rows.append([i[k] for k in keys])
+    return [round(float(x), 4) for x in np.median(np.array(rows[1:]), axis=0)]
+
+
+def lens_columns(ds, cfg, device, w, h, pin, base, seconds):
+    """the columns of --lens for one shading: plain and lens views of 16 planes on the pinhole camera"""
+    cam = pin.view_camera()
+    smp = camera.view_samples(base, _abi.RT_VIEW_PINHOLE)
+    ls = camera.lens_samples(smp.shape[0])
+    focus = float(np.linalg.norm(np.asarray(pin.target, np.float64) - np.asarray(pin.eye, np.float64)))
+    rng = np.random.default_rng(1)
+    distinct16 = (smp + rng.uniform(-1e-3, 1e-3, smp.shape)).astype(np.float32)  # (no repeated pixel offset: 16 planes)
+    out = dict(focus_distance=round(focus, 4))
+    nine = DeviceView(device, w, h, smp, order="once", camera=cam)  # (view_16 of the other columns: 9 distinct pixel offsets)
+    out["plain_config16"] = dict(rays=nine.info["n_rays"], frame_ms=time_it(lambda: ds.render_view(nine, cfg, torch_out=True), seconds),
+                                 generator_ms=stage_medians(ds, cfg, nine, ("rays_ms",))[0])
+    nine.close()
+    plain = DeviceView(device, w, h, distinct16, order="once", camera=cam)
+    out["plain_16_planes"] = dict(rays=plain.info["n_rays"], frame_ms=time_it(lambda: ds.render_view(plain, cfg, torch_out=True), seconds),
+                                  generator_ms=stage_medians(ds, cfg, plain, ("rays_ms",))[0])
+    plain.close()
+    view = DeviceView(device, w, h, smp, order="once", camera=cam, lens_samples=ls)
+    out["rays"], out["view_bytes"] = view.info["n_rays"], view.info["bytes"]
+    out["lens_off"] = dict(frame_ms=time_it(lambda: ds.render_view(view, cfg, torch_out=True), seconds),
+                           generator_ms=stage_medians(ds, cfg, view, ("rays_ms",))[0])
+    view.enable_adaptive()
+    n = w * h
+    adaptive = {}
+    for share in (0.005, 0.02):
+        A = share * focus
+        view.set_lens(camera.ThinLens(A, focus, coc_tol=1.0, spread=8))
+        e = dict(aperture=round(A, 5), full_ms=time_it(lambda: ds.render_view(view, cfg, torch_out=True), seconds),
+                 generator_ms=stage_medians(ds, cfg, view, ("rays_ms",))[0])
+        full = ds.render_view(view, cfg, torch_out=True)
+        every = ds.render_view(view, cfg, torch_out=True, refine=Refine(criteria="every"))
+        e["every_equals_full"] = bool(same(every[:4], full))
+        del full, every
+        e["adaptive_ms"] = time_it(lambda: ds.render_view(view, cfg, torch_out=True, refine=Refine()), seconds)
+        e["refined"] = round(view.adaptive_info["n_refined"] / n, 4)
+        keys = ("pass1_ms", "classify_ms", "partition_ms", "pass2_ms", "resolve_ms")
+        e["stages_ms"] = dict(zip(keys, stage_medians(ds, cfg, view, keys, adaptive=True, refine=Refine())))
+        view.set_lens(camera.ThinLens(A, focus, coc_tol=float("inf"), spread=8))
+        e["adaptive_rule_only_ms"] = time_it(lambda: ds.render_view(view, cfg, torch_out=True, refine=Refine()), seconds)
+        e["refined_rule_only"] = round(view.adaptive_info["n_refined"] / n, 4)
+        e["classify_rule_only_ms"] = stage_medians(ds, cfg, view, ("classify_ms",), adaptive=True, refine=Refine())[0]
+        e["coc_and_spread_ms"] = round(e["stages_ms"]["classify_ms"] - e["classify_rule_only_ms"], 4)
+        sweep = {}
+        for spread in (0, 4, 8, 16):  # (the classify stage with the coc kernel and a spread kernel of that halo)
+            view.set_lens(camera.ThinLens(A, focus, coc_tol=1.0, spread=spread))
+            sweep[str(spread)] = [stage_medians(ds, cfg, view, ("classify_ms",), adaptive=True, refine=Refine())[0], round(view.adaptive_info["n_refined"] / n, 4)]
+        e["classify_ms_and_refined_by_spread"] = sweep
+        adaptive[f"{share:g}"] = e
+        if "lens_on" not in out:
+            out["lens_on"] = dict(frame_ms=e["full_ms"], generator_ms=e["generator_ms"])
+    out["adaptive"] = adaptive
+    view.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--device", type=int, default=0)
@@ -109,6 +187,8 @@ def main():
     ap.add_argument("--only", default="direct,soft")
     ap.add_argument("--size", default="1620x1350")
     ap.add_argument("--adaptive", action="store_true", help="add the adaptive frame, the refined fraction and the stage times beside view_16")
+    ap.add_argument("--lens", action="store_true", help="add the thin-lens columns (pinhole camera, 16 planes) per shading")
+    ap.add_argument("--lens-only", action="store_true", help="with --lens: skip every other column")
     args = ap.parse_args()
     only = set(args.only.split(","))
     w, h = (int(v) for v in args.size.split("x"))
@@ -131,6 +211,11 @@ def main():
             continue
         cfg = RenderConfig.from_features(features, **size)
         r = {}
+        if args.lens:
+            r["lens"] = lens_columns(ds, cfg, args.device, w, h, pin, base, args.seconds)
+        if args.lens and args.lens_only:
+            res[name] = r
+            continue
         for cam_name, (kind, cam) in cams.items():
             c = {}
             for label, smp in (("view_1", None), ("view_16", camera.view_samples(base, kind))):
