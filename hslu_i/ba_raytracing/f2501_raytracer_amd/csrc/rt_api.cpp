@@ -18,7 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "rt_cell_prune.h"
+#include "rt_cell_resolve.h"
 #include "rt_host.h"
 
 static void trace_point(hipStream_t stream, const char* what, uint32_t a = 0, uint32_t b = 0, uint32_t c = 0);  // RT_TRACE_LAUNCHES
@@ -81,7 +81,7 @@ void rt_scene_destroy(rt_scene* s) {
       for (DevBuf* b : {&l.queues, &l.qcount, &l.trace_ws, &l.hard, &l.hitrec, &l.sets}) b->release();
     }
   }
-  for (DevBuf* b : {&s->blob, &s->aa, &s->cloud, &s->counters, &s->suplist, &s->fb, &s->aux_rgb, &s->costmap, &s->aux_id, &s->aux_t, &s->flag_geo, &s->flags, &s->cell_lists, &s->progress_fb, &s->rays_argb})
+  for (DevBuf* b : {&s->blob, &s->aa, &s->cloud, &s->counters, &s->suplist, &s->fb, &s->aux_rgb, &s->costmap, &s->aux_id, &s->aux_t, &s->flag_geo, &s->flags, &s->cell_lists, &s->resolve_work, &s->progress_fb, &s->rays_argb})
     b->release();
   rt_scene_release_update(s);
   delete s;
@@ -151,7 +151,7 @@ int rt_scene_memory_info(const rt_scene* s, rt_scene_info* out) {
   out->bytes_bvh = s->bytes_bvh;
   out->bytes_geometry = s->blob.cap > s->bytes_bvh ? s->blob.cap - s->bytes_bvh : 0;
   out->bytes_flags = s->flags.cap + s->flag_geo.cap;
-  out->bytes_cell_lists = s->cell_lists.cap;
+  out->bytes_cell_lists = s->cell_lists.cap + s->resolve_work.cap;
   out->bytes_tables = s->aa.cap + s->cloud.cap + s->counters.cap + s->suplist.cap + s->costmap.cap;
   for (const auto& w : s->ws) {
     out->bytes_workspace += w.bytes();
@@ -352,7 +352,25 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
         e = (hipError_t)rt_launch_cell_prune(s->dev, a, stream);
         if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_cell_prune_kernel launch failed: %s", hipGetErrorString(e));
         trace_point(stream, "rt_cell_prune_kernel: cells, lights", s->n_cells, s->dev.n_lights, 0u);
+        // lists that overflowed under the fat beam, enumerated again under the sharper rule (rt_cell_resolve.h): a third stage
+        // behind the same key.  Its work list counts against the budget as the lists do; RT_CELL_RESOLVE=0 (read once per
+        // process) leaves it out, and so does RT_CELL_PRUNE=0.
+        static const char* const resolve_env = getenv("RT_CELL_RESOLVE");
+        static const bool resolve_off = resolve_env && *resolve_env == '0';
+        RtCellResolveArgs r{};
+        const size_t temp_bytes = resolve_off ? 0 : rt_cell_resolve_temp_bytes(s->n_cells, s->budget - flag_bytes - list_bytes, &r.chunk_cells);
+        if (temp_bytes && s->resolve_work.ensure(temp_bytes) == RT_OK) {
+          r.cell = a;
+          r.eps_push = P->beam_eps_push, r.eps_ulp = P->beam_eps_ulp;
+          r.work = (uint32_t*)s->resolve_work.p;
+          e = (hipError_t)rt_launch_cell_resolve(s->dev, r, stream);
+          if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_cell_resolve_kernel launch failed: %s", hipGetErrorString(e));
+          trace_point(stream, "rt_cell_resolve_kernel: cells, lights, cells per chunk", s->n_cells, s->dev.n_lights, r.chunk_cells);
+        } else {
+          s->resolve_work.release();
+        }
       }
+      if (!s->cell_lists_built) s->resolve_work.release();
       memcpy(s->flags_key, key, sizeof(key));
     }
     P->recv_flags = (const uint16_t*)s->flags.p;

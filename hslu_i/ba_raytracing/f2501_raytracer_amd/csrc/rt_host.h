@@ -317,6 +317,7 @@ struct rt_scene {
   // receiver flags (rt_flags_kernel): cell tables built with the scene, flags rebuilt when the beam constants change
   DevBuf flag_geo, flags;
   DevBuf cell_lists;     // per (receiver cell, light): 8 x uint16 leaf slots surviving the cell's fat beam (rt_flags_kernel)
+  DevBuf resolve_work;   // work list of rt_cell_resolve_kernel (at most 64 MiB, counted with the lists)
   bool cell_lists_built = false;
   uint32_t n_cells = 0, n_tri_cells = 0;
   float flags_key[8] = {-1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // beam_delta, eps, cloud centre: what the flags were built for

@@ -1,10 +1,14 @@
-"""What rt_cell_prune_kernel removes from the per-cell shadow candidate lists of a scene, counted on the GPU.
+"""What rt_cell_prune_kernel removes from the per-cell shadow candidate lists of a scene and what rt_cell_resolve_kernel
+makes of the overflowed ones, counted on the GPU.
 
 Packs the scene with the library's own packer under --budget (default 2 GiB: bench.py's, the per-cell lists fit), runs
 rt_flags_kernel with lists, reads lists and flags back, runs rt_cell_prune_kernel and reads them back again.  Reports, before
 and after pruning: listed slots, non-empty lists, lists emptied, triangle-clear bits gained per light, and the overflowed
-lists (more than 8 candidates: left alone, the render walks the tree for such a cell).  A probe compiled on the fly links
-against the built librt_hip.so, so the kernels counted here are the ones that ship.  Prints one JSON line.
+lists (more than 8 candidates: left alone by that kernel, the render walks the tree for such a cell).  Then it runs
+rt_cell_resolve_kernel with survivor counts and reports the overflowed lists before and after it, a histogram of the
+survivors per formerly overflowed list (0, 1-4, 5-8, 9-16, more) and the stage's device time (timed in a run of its own
+without the counts, as the render launches it).  A probe compiled on the fly links against the built librt_hip.so, so the
+kernels counted here are the ones that ship.  Prints one JSON line.
 
     python tools/cell_list_stats.py [--scene semesterbild] [--model text] [--budget BYTES]
 """
@@ -30,7 +34,7 @@ CSRC = os.path.join(ROOT, "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csr
 PROBE = r'''
 #include <hip/hip_runtime_api.h>
 #include <cstring>
-#include "rt_cell_prune.h"
+#include "rt_cell_resolve.h"
 #include "rt_scene_pack.h"
 static RtPackedScene g;
 #define TRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return 1000 + (int)e_; } while (0)
@@ -41,9 +45,11 @@ int probe_pack(const rt_scene_desc* d, uint64_t budget, uint32_t* out) {
   out[0] = g.n_cells, out[1] = g.n_tri_cells, out[2] = g.dev.n_lights, out[3] = g.dev.n_slots;
   return rc;
 }
-// lists [n_cells][n_lights][8] and flags [n_cells]: raw_* as rt_flags_kernel leaves them, out_* after rt_cell_prune_kernel
-int probe_run(const float* cloud, uint64_t n_floats, const float* f, float eps, uint16_t* raw_lists, uint16_t* raw_flags, uint16_t* out_lists,
-              uint16_t* out_flags, float* ms) {
+// lists [n_cells][n_lights][8] and flags [n_cells]: raw_* as rt_flags_kernel leaves them, out_* after rt_cell_prune_kernel,
+// res_* after rt_cell_resolve_kernel; counts [n_cells][n_lights]: survivors of every formerly overflowed list (capped at 255);
+// ms = {-, prune, resolve as the render launches it, resolve with counts}
+int probe_run(const float* cloud, uint64_t n_floats, const float* f, float eps, uint64_t budget, uint16_t* raw_lists, uint16_t* raw_flags, uint16_t* out_lists,
+              uint16_t* out_flags, uint16_t* res_lists, uint16_t* res_flags, uint8_t* counts, float* ms) {
   if (!g.n_cells || g.dev.n_lights > 8u || g.dev.n_slots > 65533u) return -100;
   std::vector<float> scaled;
   float ball[4];
@@ -89,8 +95,34 @@ int probe_run(const float* cloud, uint64_t n_floats, const float* f, float eps, 
   TRY(hipDeviceSynchronize());
   TRY(hipMemcpy(out_lists, lists, list_bytes, hipMemcpyDeviceToHost));
   TRY(hipMemcpy(out_flags, flags, flag_bytes, hipMemcpyDeviceToHost));
-  ms[0] = ms[1] = 0.f;
+  ms[0] = ms[1] = ms[2] = ms[3] = 0.f;
   TRY(hipEventElapsedTime(&ms[1], e[1], e[2]));
+  // the third stage, twice from the same input: as the render launches it (timed), then with survivor counts
+  RtCellResolveArgs r{};
+  r.cell = a;
+  r.eps_push = P.beam_eps_push, r.eps_ulp = P.beam_eps_ulp;
+  const size_t used = list_bytes + flag_bytes + g.flag_geo.size() * 4;
+  const size_t temp = rt_cell_resolve_temp_bytes(g.n_cells, budget > used ? budget - used : 0, &r.chunk_cells);
+  if (!temp) return -101;
+  uint8_t* dcounts = nullptr;
+  TRY(hipMalloc((void**)&r.work, temp));
+  TRY(hipMalloc((void**)&dcounts, (size_t)g.n_cells * g.dev.n_lights + 64));
+  TRY(hipMemset(dcounts, 0, (size_t)g.n_cells * g.dev.n_lights));
+  for (int pass = 0; pass < 2; pass++) {
+    TRY(hipMemcpy(lists, out_lists, list_bytes, hipMemcpyHostToDevice));
+    TRY(hipMemcpy(flags, out_flags, flag_bytes, hipMemcpyHostToDevice));
+    r.counts = pass ? dcounts : nullptr;
+    TRY(hipEventRecord(e[1], nullptr));
+    TRY((hipError_t)rt_launch_cell_resolve(sc, r, nullptr));
+    TRY(hipEventRecord(e[2], nullptr));
+    TRY(hipDeviceSynchronize());
+    TRY(hipEventElapsedTime(&ms[2 + pass], e[1], e[2]));
+  }
+  TRY(hipMemcpy(res_lists, lists, list_bytes, hipMemcpyDeviceToHost));
+  TRY(hipMemcpy(res_flags, flags, flag_bytes, hipMemcpyDeviceToHost));
+  TRY(hipMemcpy(counts, dcounts, (size_t)g.n_cells * g.dev.n_lights, hipMemcpyDeviceToHost));
+  TRY(hipFree(r.work));
+  TRY(hipFree(dcounts));
   TRY(hipFree(blob));
   TRY(hipFree(geo));
   TRY(hipFree(lists));
@@ -103,6 +135,22 @@ int probe_run(const float* cloud, uint64_t n_floats, const float* f, float eps, 
 
 def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def resolve_report(over, new_l, res_l, new_f, res_f, counts, nl):
+    """rt_cell_resolve_kernel: overflowed lists before and after, survivors per formerly overflowed list, what else changed"""
+    still = res_l[:, :, 0] == 0xFFFE
+    n = counts[over]
+    same = (new_l == res_l).all(2)
+    return {"overflowed_lists_before": int(over.sum()), "overflowed_lists_after": int(still.sum()),
+            "cells_with_an_overflowed_list_before": int(over.any(1).sum()), "cells_with_an_overflowed_list_after": int(still.any(1).sum()),
+            "overflowed_lists_after_per_light": [int(v) for v in still.sum(0)],
+            "survivors_per_formerly_overflowed_list": {"0": int((n == 0).sum()), "1-4": int(((n >= 1) & (n <= 4)).sum()), "5-8": int(((n >= 5) & (n <= 8)).sum()),
+                                                       "9-16": int(((n >= 9) & (n <= 16)).sum()), ">16": int((n > 16).sum())},
+            "slots_listed_by_the_stage": int(((res_l < 0xFFFE) & (over & ~still)[:, :, None]).sum()),
+            "clear_bits_gained_per_light": [int((((res_f & ~new_f) >> l) & 1).sum()) for l in range(nl)],
+            "lists_that_were_not_overflowed_and_changed": int((~same & ~over).sum()),
+            "resolved_lists_that_disagree_with_their_count": int(((counts <= 8) & over & still).sum() + ((counts > 8) & over & ~still).sum())}
 
 
 def main():
@@ -130,10 +178,12 @@ def main():
     n_cells, n_tri_cells, nl, ns = (int(v) for v in out)
     cs = np.ascontiguousarray(sampling.cloud_sets(cfg), np.float32)
     f = np.array([cfg.fw, cfg.fh, cfg.fd], np.float32)
-    raw_l, new_l = (np.zeros((n_cells, nl, 8), np.uint16) for _ in range(2))
-    raw_f, new_f = (np.zeros(n_cells, np.uint16) for _ in range(2))
-    ms = np.zeros(2, np.float32)
-    rc = probe.probe_run(ptr(cs), C.c_uint64(cs.size), ptr(f), C.c_float(cfg.eps_distance), ptr(raw_l), ptr(raw_f), ptr(new_l), ptr(new_f), ptr(ms))
+    raw_l, new_l, res_l = (np.zeros((n_cells, nl, 8), np.uint16) for _ in range(3))
+    raw_f, new_f, res_f = (np.zeros(n_cells, np.uint16) for _ in range(3))
+    counts = np.zeros((n_cells, nl), np.uint8)
+    ms = np.zeros(4, np.float32)
+    rc = probe.probe_run(ptr(cs), C.c_uint64(cs.size), ptr(f), C.c_float(cfg.eps_distance), C.c_uint64(args.budget), ptr(raw_l), ptr(raw_f), ptr(new_l), ptr(new_f),
+                         ptr(res_l), ptr(res_f), ptr(counts), ptr(ms))
     assert rc == 0, f"probe_run: {rc}"
     over = raw_l[:, :, 0] == 0xFFFE
     usable = ~over
@@ -154,7 +204,9 @@ def main():
            "clear_bits_gained_per_light": [a - b for a, b in zip(after["triangle_clear_bits_per_light"], before["triangle_clear_bits_per_light"])],
            "slots_removed": before["listed_slots"] - after["listed_slots"],
            "slots_removed_fraction": (before["listed_slots"] - after["listed_slots"]) / max(1, before["listed_slots"]),
-           "prune_kernel_ms": float(ms[1]), "build_id": _lib.load().rt_build_id().decode()}
+           "prune_kernel_ms": float(ms[1]),
+           "resolve": resolve_report(over, new_l, res_l, new_f, res_f, counts, nl), "resolve_stage_ms": float(ms[2]), "resolve_stage_with_counts_ms": float(ms[3]),
+           "build_id": _lib.load().rt_build_id().decode()}
     print(json.dumps(res))
 
 
