@@ -129,6 +129,15 @@ class rt_ray_occlusion(C.Structure):
                 ("color_filter", C.c_void_p)]
 
 
+class rt_point_batch(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("n_points", C.c_uint32), ("point", C.c_void_p), ("max_distance", C.c_void_p)]
+
+
+class rt_point_hits(C.Structure):
+    _fields_ = [("id", C.c_void_p), ("distance", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("bary", C.c_void_p),
+                ("material", C.c_void_p)]
+
+
 class rt_ray_radiance(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("valid", C.c_void_p), ("id", C.c_void_p), ("t", C.c_void_p), ("argb", C.c_void_p)]
 

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_closest.h"     // (RtClosestArgs, rt_launch_closest: the kernel of rt_closest_points*, rt_closest.hip)
 #include "rt_ray_key.h"     // (RtOrderWs)
 #include "rt_scene_pack.h"  // (rt_internal.h; rt_fail; the device-free scene packer and table builders)
 

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <string>
 
+#include "rt_closest.h"
 #include "rt_lbvh.h"
 #include "rt_refit.h"
 #include "rt_ploc.h"
@@ -458,6 +459,16 @@ void rt_sah_packed(const RtPackedScene& pk, uint64_t sums[2], uint32_t* n_bad) {
     for (uint32_t i = 0; i < pk.dev.n_nodes; i++) rt_sah_node(nodes[i], a_root, sums, &bad);
   }
   if (n_bad) *n_bad = bad;
+}
+
+void rt_closest_packed(const RtPackedScene& pk, const RtClosestArgs& a) {
+  const char* base = (const char*)pk.blob.data();
+  for (size_t i = 0; i < a.n; i++) {
+    const float p[3] = {a.point[3 * i], a.point[3 * i + 1], a.point[3 * i + 2]};
+    RtClosestHit h;
+    rt_closest_query(pk.dev, base, p, a.max_distance ? a.max_distance[i] : INFINITY, true, h);
+    rt_closest_store(a, i, h);
+  }
 }
 
 int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {

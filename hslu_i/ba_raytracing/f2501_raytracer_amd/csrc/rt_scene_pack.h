@@ -98,6 +98,13 @@ int rt_rebuild_ploc_packed(RtPackedScene* pk, uint32_t max_leaf, uint32_t radius
 // the number of refused ratios.  The specification of rt_scene_bvh_quality, checked on the CPU; all zero without triangles.
 void rt_sah_packed(const RtPackedScene& pk, uint64_t sums[2], uint32_t* n_bad);
 
+// ---- closest-point queries (rt_closest_points*; the arithmetic and the walk: rt_closest.h) ----------------------------------
+// The KERNEL's walk -- spheres, seed descent, threaded walk with rt_closest_may_skip -- over the packed blob for a batch of
+// HOST arrays: the same functions rt_closest_kernel is made of, so the pruning is checked on the CPU against the linear scan
+// of rt_closest_points_model.
+struct RtClosestArgs;
+void rt_closest_packed(const RtPackedScene& pk, const RtClosestArgs& a);
+
 // ---- parameter tables of a frame -----------------------------------------------------------------------------------------
 // AA samples: the distinct offsets in first-occurrence order (compared as values; `dedup` off: every sample is distinct),
 // their multiplicities and the sample -> thread map, as the device image [2U offsets (float bits) | U | n].  Returns U.

@@ -54,6 +54,18 @@ class RayHits(NamedTuple):
     material: Any
 
 
+class ClosestPoints(NamedTuple):
+    """Nearest surface point per query point (`rt_point_hits`): canonical object id (-1 = miss), distance (+inf on a miss),
+    the point, the normal there, the barycentric weights of e1 and e2 (0 for spheres) -- all 0 on a miss -- and the material row
+    (0xFFFFFFFF on a miss; -1 in an int32 tensor)."""
+    id: Any
+    distance: Any
+    point: Any
+    normal: Any
+    bary: Any
+    material: Any
+
+
 class IntersectionTest(NamedTuple):
     """`IntersectionTest` (raytracer.rs:17-22) per segment.  color_filter is unspecified where completely_occluded."""
     has_intersection: Any
@@ -458,6 +470,24 @@ class DeviceScene:
             _lib.check(lib.rt_any_intersection_device(self.handle, C.byref(b), C.byref(oc), self._stream_of(o)))
         else:
             _lib.check(lib.rt_any_intersection(self.handle, C.byref(b), C.byref(oc)))
+        return out
+
+    def closest_points(self, points, max_distance=None) -> "ClosestPoints":
+        """`rt_closest_points` for a batch of points: the nearest point of the scene's surface to each, within max_distance
+        (None = +inf; a scalar or (n,) array with numpy points, an (n,) tensor with tensors).  On equal distance the larger
+        canonical id wins; a non-finite point is a miss.  Same input kinds as cast_rays: numpy arrays (the host entry point;
+        numpy results) or torch tensors on this scene's device (the _device entry point on torch.cuda.current_stream(); tensor
+        results, no synchronisation)."""
+        torch_in, n, p, _, m = self._batch(points, points, max_distance)
+        out, ptr = self._planes(ClosestPoints, p, n, ("id", "int32", 1), ("distance", "float32", 1), ("point", "float32", 3),
+                                ("normal", "float32", 3), ("bary", "float32", 2), ("material", "int32" if torch_in else "uint32", 1))
+        b = _abi.rt_point_batch(_abi.RT_ABI_VERSION, int(n), ptr(p), ptr(m) if m is not None else None)
+        h = _abi.rt_point_hits(ptr(out.id), ptr(out.distance), ptr(out.point), ptr(out.normal), ptr(out.bary), ptr(out.material))
+        lib = _lib.load()
+        if torch_in:
+            _lib.check(lib.rt_closest_points_device(self.handle, C.byref(b), C.byref(h), self._stream_of(p)))
+        else:
+            _lib.check(lib.rt_closest_points(self.handle, C.byref(b), C.byref(h)))
         return out
 
     def ray_order(self, origins, directions, origin_bits: int = 0) -> RayOrder:

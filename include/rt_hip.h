@@ -29,6 +29,8 @@
  *   rt_any_intersection          <- Raytracer::has_any_intersection, raytracer.rs:24-106 (IntersectionTest,
  *                                   raytracer.rs:17-22), for a batch of HOST segments; blocks
  *   rt_any_intersection_device   <- same, DEVICE arrays, enqueued on the caller's stream
+ *   rt_closest_points[_device]   <- none (the reference has no point query): the nearest surface point per query
+ *                                   point, Embree's rtcPointQuery; rt_closest_points_model is its specification
  *   rt_trace_rays     <- RaytracerRenderer::single_raytrace, src/renderer/raytracer_renderer.rs:147-264 (the colour of
  *                        a ray: nearest hit, the lights' shadow and transmittance rays, soft-shadow clouds, attenuation,
  *                        reflection and refraction trees), for a batch of HOST rays; blocks
@@ -461,6 +463,61 @@ int rt_any_intersection(rt_scene* scene, const rt_ray_batch* batch, const rt_ray
  * nothing and returns once the work is enqueued. */
 int rt_cast_rays_device(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_hits* hits, void* hip_stream);
 int rt_any_intersection_device(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_occlusion* out, void* hip_stream);
+
+/* ---- closest-point queries: the nearest point of the scene's surface per query point -----------------------------------------
+ *
+ * The third query on a scene that is already on the device (Embree's rtcPointQuery, Open3D's compute_closest_points): for each
+ * point p, the object whose SURFACE comes nearest, the nearest point q on it and the distance |q - p|.  It works on whatever
+ * the handle holds after rt_scene_update*, rt_pose_apply*, rt_skin_apply* and rt_scene_rebuild*.
+ *
+ * Definition (csrc/rt_closest.h holds the formulas; every float operation is a single correctly rounded one):
+ *   triangle  the nearest of four candidates relative to p (v1 - p is formed first): the clamped projections onto its three
+ *             edges and, where it falls inside, the projection onto its plane.  Finite for every triangle with finite vertices:
+ *             a zero-area triangle is its longest segment, three equal vertices are that point, and no candidate divides by
+ *             zero.  A triangle farther than 1.8e19 from p overflows its squared distance and never wins.
+ *   sphere    r = sqrt(r_sq); distance | |p - c| - r |, point c + (p - c) (r / |p - c|); for p == c the direction is (1, 0, 0).
+ *   Both are surfaces, not solids: inside and outside are treated alike, and there is no sign.
+ * One fp32 distance per object.  The smaller distance wins; on EQUAL distance the LARGER canonical id wins (spheres, then
+ * triangles, each in insertion order: the "later object wins" of rt_cast_rays).  The result is therefore a function of the
+ * scene description and the point alone, not of the tree or of the order a walk meets candidates in.  An object counts only
+ * when its distance <= max_distance (the test is <=; a NaN or negative max_distance admits nothing; NULL = +inf).
+ *
+ * Dead queries: a point with a non-finite coordinate is a miss.  A miss returns id -1, distance +inf, point, normal and bary 0,
+ * material 0xFFFFFFFF, as rt_ray_hits does.
+ *
+ * Validation (RT_ERR_INVALID_ARG + rt_last_error, before any HIP call): NULL scene (or description), batch or output struct;
+ * wrong abi_version; NULL point with n_points > 0; every output plane NULL.
+ *
+ * A query reads only the scene's data: it may run on any stream beside renders and ray queries of the same scene, and must
+ * have finished before rt_scene_update* / rt_scene_rebuild* (and the pose and skin calls, which update), exactly as the ray
+ * queries.
+ *
+ * Not offered: signed distance and inside tests (the meshes need not be closed), the k nearest objects, a walk shared by the
+ * wavefront for coherent point sets such as grids, and an ordered variant. */
+typedef struct rt_point_batch {
+  uint32_t abi_version;      /* RT_ABI_VERSION */
+  uint32_t n_points;         /* 0 is a valid no-op */
+  const float* point;        /* [n_points][3] */
+  const float* max_distance; /* [n_points] search radius; NULL = +inf */
+} rt_point_batch;
+
+/* nearest surface point per query point.  Every member nullable, at least one non-NULL: a NULL plane is not written. */
+typedef struct rt_point_hits {
+  int32_t* id;        /* canonical object index, -1 on a miss */
+  float* distance;    /* |q - p| as defined above; +inf on a miss */
+  float* point;       /* [n][3] q; 0 on a miss */
+  float* normal;      /* [n][3] sphere: normalize(q - c), computed as (p - c) / |p - c|; triangle: its stored face normal; 0 on a miss */
+  float* bary;        /* [n][2] weights of e1 and e2 at q (q = v1 + bary0 e1 + bary1 e2 up to rounding); 0 for spheres and misses */
+  uint32_t* material; /* material row; 0xFFFFFFFF on a miss */
+} rt_point_hits;
+
+/* HOST arrays: staged through device memory allocated for the call; returns when the results are in host memory. */
+int rt_closest_points(rt_scene* scene, const rt_point_batch* batch, const rt_point_hits* hits);
+/* DEVICE arrays on the scene's device: enqueued on `hip_stream` (NULL = default stream); allocates nothing. */
+int rt_closest_points_device(rt_scene* scene, const rt_point_batch* batch, const rt_point_hits* hits, void* hip_stream);
+/* The specification, without a device or a tree: a LINEAR scan of `desc` with the same arithmetic.  HOST arrays; no HIP call.
+ * The two calls above return the same bits. */
+int rt_closest_points_model(const rt_scene_desc* desc, const rt_point_batch* batch, const rt_point_hits* hits);
 
 /* ---- radiance queries: Whitted shading of caller-supplied rays -------------------------------------------------------------
  *
