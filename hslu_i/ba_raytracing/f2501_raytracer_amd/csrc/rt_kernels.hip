@@ -1023,7 +1023,10 @@ __device__ __forceinline__ CandList collect_light_candidates(const RtDevScene& s
   // (receiver cell: the largest coordinate of any point of it; a hit point the cell stands for lies off the triangle's
   // plane by the rounding of p = o + t d, hence the doubled ulp term; origins lie within eps_o + r of the cell's centre)
   const float p_max = fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fabsf(p.z)) + (MODE == COLLECT_FLAGS ? fb->r : 0.0f);
-  const float p_ulp = __builtin_fmaf(MODE == COLLECT_FLAGS ? 4e-7f : 1.3e-7f, p_max, P.beam_eps_ulp);  // 1.3e-7 (|p| + eps) + 2.5e-6 eps
+  // (receiver cell: that rounding moves a hit point by up to 4e-7 |p|_1 ALONG THE NORMAL, whichever way it points -- the 1-norm
+  // of the point, not its largest coordinate: a floor at z = 0.7 seen at (2.9, 2.9, 0.7) is left by 2.6e-6, not by 1.2e-6)
+  const float p_off = MODE == COLLECT_FLAGS ? fabsf(p.x) + fabsf(p.y) + fabsf(p.z) + fb->r : p_max;
+  const float p_ulp = __builtin_fmaf(MODE == COLLECT_FLAGS ? 4e-7f : 1.3e-7f, p_off, P.beam_eps_ulp);  // 1.3e-7 (|p| + eps) + 2.5e-6 eps
   // (p_ulp also carries G*eps_d for sum|x b_j| vs sum|x b0| and the rounding of the unit direction)
   const float eps_o = __builtin_fmaf(2.6e-7f, p_max, P.beam_eps_o) + (MODE == COLLECT_FLAGS ? fb->r + 4e-7f * p_max : 0.0f);  // 1.01 eps + 2 p_ulp >= |so_j - p|
   // returns true when NO lane in `lanes` can be hit by any of its samples (wave-uniform result); staged so

@@ -139,6 +139,7 @@ def probe(tmp_path_factory):
 @pytest.mark.parametrize("name, work_cells", [("synthetic", 0), ("sphere_receiver", 0), ("semesterbild", 0), ("semesterbild", 300), ("fan_behind", 0),
                                               ("fan_mixed", 0), ("fan_between", 0)])
 def test_kernel_writes_the_host_models_words(probe, name, work_cells):
+    import flags_cases
     import test_cell_resolve_host as rh
     from test_scene_pack_host import ptr
     from hslu_i.ba_raytracing.f2501_raytracer_amd import _abi, sampling
@@ -162,6 +163,7 @@ def test_kernel_writes_the_host_models_words(probe, name, work_cells):
     clear = lambda a: int(sum(bin(int(v) & 0xFF).count("1") for v in a))  # noqa: E731
     print(f"{name}: {n_cells} cells, {nl} lights, work list of {work_cells or 'all'} cells; overflowed lists {int(over2.sum())} -> {int(over3.sum())} "
           f"({int((over2 & ~over3 & (dev_l[:, :, 0] == host.END)).sum())} emptied), triangle-clear bits {clear(two_f)} -> {clear(dev_f)}")
+    assert sum(flags_cases.check_shape(raw_l, None, ns)) > 0, "rt_flags_kernel listed something, in well-formed lists"
     assert np.array_equal(raw_l[:, :, 0] == host.OVERFLOW, over2), "stage two leaves overflowed lists alone"
     assert np.array_equal(dev_l, host_l), f"{int((dev_l != host_l).sum())} list words differ"
     assert np.array_equal(dev_f, host_f), f"{int((dev_f != host_f).sum())} flag words differ"
