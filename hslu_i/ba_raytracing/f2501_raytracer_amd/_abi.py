@@ -138,6 +138,14 @@ class rt_point_hits(C.Structure):
                 ("material", C.c_void_p)]
 
 
+RT_MAX_HITS_PER_RAY = 16
+
+
+class rt_ray_hit_lists(C.Structure):
+    _fields_ = [("max_hits", C.c_uint32), ("after_t", C.c_void_p), ("after_id", C.c_void_p), ("count", C.c_void_p), ("total", C.c_void_p),
+                ("id", C.c_void_p), ("t", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("material", C.c_void_p)]
+
+
 class rt_ray_radiance(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("valid", C.c_void_p), ("id", C.c_void_p), ("t", C.c_void_p), ("argb", C.c_void_p)]
 

@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_point_batch, rt_point_hits, rt_ray_batch, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
+from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_point_batch, rt_point_hits, rt_ray_batch, rt_ray_hit_lists, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
                    rt_bvh_quality, rt_pose_desc, rt_rebuild_desc, rt_rebuild_info, rt_rebuild_report, rt_skin_desc, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_adaptive_info, rt_view_camera, rt_view_desc, rt_view_info, rt_view_lens, rt_view_refine)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,6 +18,7 @@ EXPORTS = (
     "rt_render_gather_device", "rt_comm_last_gather", "rt_render_begin", "rt_render_poll", "rt_render_end",
     "rt_cast_rays", "rt_cast_rays_device", "rt_any_intersection", "rt_any_intersection_device",
     "rt_closest_points", "rt_closest_points_device", "rt_closest_points_model",
+    "rt_list_intersections", "rt_list_intersections_device", "rt_list_intersections_model",
     "rt_trace_rays", "rt_trace_rays_device", "rt_scene_update", "rt_scene_update_device",
     "rt_ray_order_create", "rt_ray_order_destroy", "rt_ray_order_build", "rt_ray_order_build_device", "rt_ray_order_set", "rt_ray_order_read",
     "rt_trace_rays_ordered", "rt_trace_rays_ordered_device",
@@ -100,6 +101,12 @@ def load():
         getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(rt_ray_batch), C.POINTER(out)]
         getattr(lib, name + "_device").restype = C.c_int
         getattr(lib, name + "_device").argtypes = [C.c_void_p, C.POINTER(rt_ray_batch), C.POINTER(out), C.c_void_p]
+    lib.rt_list_intersections.restype = C.c_int
+    lib.rt_list_intersections.argtypes = [C.c_void_p, C.POINTER(rt_ray_batch), C.POINTER(rt_ray_hit_lists)]
+    lib.rt_list_intersections_device.restype = C.c_int
+    lib.rt_list_intersections_device.argtypes = [C.c_void_p, C.POINTER(rt_ray_batch), C.POINTER(rt_ray_hit_lists), C.c_void_p]
+    lib.rt_list_intersections_model.restype = C.c_int
+    lib.rt_list_intersections_model.argtypes = [C.POINTER(rt_scene_desc), C.POINTER(rt_ray_batch), C.POINTER(rt_ray_hit_lists)]
     lib.rt_closest_points.restype = C.c_int
     lib.rt_closest_points.argtypes = [C.c_void_p, C.POINTER(rt_point_batch), C.POINTER(rt_point_hits)]
     lib.rt_closest_points_device.restype = C.c_int

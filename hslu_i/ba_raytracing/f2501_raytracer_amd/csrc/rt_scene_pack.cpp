@@ -12,6 +12,7 @@
 
 #include "rt_closest.h"
 #include "rt_lbvh.h"
+#include "rt_multihit.h"
 #include "rt_refit.h"
 #include "rt_ploc.h"
 #include "rt_sah.h"
@@ -469,6 +470,11 @@ void rt_closest_packed(const RtPackedScene& pk, const RtClosestArgs& a) {
     rt_closest_query(pk.dev, base, p, a.max_distance ? a.max_distance[i] : INFINITY, true, h);
     rt_closest_store(a, i, h);
   }
+}
+
+void rt_multihit_packed(const RtPackedScene& pk, const RtMultiHitArgs& a) {
+  const RtMhBlob S = {pk.dev, (const char*)pk.blob.data()};
+  for (uint32_t i = 0; i < a.n; i++) rt_mh_query<RT_MH_KMAX>(S, RtMhArgsRef{a}, i, true);
 }
 
 int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {

@@ -105,6 +105,13 @@ void rt_sah_packed(const RtPackedScene& pk, uint64_t sums[2], uint32_t* n_bad);
 struct RtClosestArgs;
 void rt_closest_packed(const RtPackedScene& pk, const RtClosestArgs& a);
 
+// ---- multi-hit ray queries (rt_list_intersections*; the arithmetic and the walk: rt_multihit.h) -----------------------------
+// The KERNEL's walk -- spheres, threaded walk with rt_mh_box_enter, passes for `total` -- over the packed blob for a batch of
+// HOST arrays: the same functions rt_multihit_kernel is made of, so the pruning is checked on the CPU against the linear scan
+// of rt_list_intersections_model.
+struct RtMultiHitArgs;
+void rt_multihit_packed(const RtPackedScene& pk, const RtMultiHitArgs& a);
+
 // ---- parameter tables of a frame -----------------------------------------------------------------------------------------
 // AA samples: the distinct offsets in first-occurrence order (compared as values; `dedup` off: every sample is distinct),
 // their multiplicities and the sample -> thread map, as the device image [2U offsets (float bits) | U | n].  Returns U.

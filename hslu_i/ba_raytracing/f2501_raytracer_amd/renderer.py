@@ -66,6 +66,19 @@ class ClosestPoints(NamedTuple):
     material: Any
 
 
+class RayHitLists(NamedTuple):
+    """The first `max_hits` hits per ray (`rt_ray_hit_lists`): `count` (n,) entries are valid in row i of the (n, max_hits) planes
+    id, t, material and the (n, max_hits, 3) planes point, normal, ordered by t and on equal t by the larger id first; the entries
+    behind them hold the miss values of RayHits.  `total` (n,) is the number of objects hit in all, or None when it was not asked for."""
+    count: Any
+    id: Any
+    t: Any
+    point: Any
+    normal: Any
+    material: Any
+    total: Any
+
+
 class IntersectionTest(NamedTuple):
     """`IntersectionTest` (raytracer.rs:17-22) per segment.  color_filter is unspecified where completely_occluded."""
     has_intersection: Any
@@ -489,6 +502,62 @@ class DeviceScene:
         else:
             _lib.check(lib.rt_closest_points(self.handle, C.byref(b), C.byref(h)))
         return out
+
+    def list_intersections(self, origins, directions, max_hits: int = 8, max_distance=None, backface_culling: bool = False,
+                           total: bool = False, after=None) -> "RayHitLists":
+        """`rt_list_intersections` for a batch of rays: the first max_hits (1 .. 16) objects each ray passes through at
+        t <= max_distance (None = +inf), one hit per object, ordered by t and on equal t by the larger canonical id first -- entry 0
+        is cast_rays' answer.  total=True also counts every object hit (rays with max_hits hits or more walk again for it).
+        after=(t, id): a cursor per ray, (n,) float32 and (n,) int32 -- only hits strictly behind that key are returned; feeding
+        back the last key of each row pages through all hits.  Same input kinds as cast_rays."""
+        return self._list_intersections(origins, directions, int(max_hits), max_distance, backface_culling, total, after, True)
+
+    def count_intersections(self, origins, directions, max_distance=None, backface_culling: bool = False):
+        """`rt_list_intersections` with the `total` plane alone: the number of objects each ray passes through at
+        t <= max_distance, (n,) -- uint32 in numpy, int32 in a tensor."""
+        return self._list_intersections(origins, directions, _abi.RT_MAX_HITS_PER_RAY, max_distance, backface_culling, True, None, False).total
+
+    def _list_intersections(self, origins, directions, k, max_distance, backface_culling, total, after, planes):
+        torch_in, n, o, d, m = self._batch(origins, directions, max_distance)
+        if not 1 <= k <= _abi.RT_MAX_HITS_PER_RAY:
+            raise ValueError(f"max_hits must be 1 .. {_abi.RT_MAX_HITS_PER_RAY}, got {k}")
+        u32 = "int32" if torch_in else "uint32"  # (torch has no uint32 arithmetic; a miss's material is -1 = 0xFFFFFFFF)
+        cnt, ptr = self._planes(dict, o, n, ("count", u32, 1), ("total", u32, 1))
+        lists, _ = self._planes(dict, o, n * k, ("id", "int32", 1), ("t", "float32", 1), ("point", "float32", 3), ("normal", "float32", 3),
+                                ("material", u32, 1))
+        at = ai = None
+        if after is not None:
+            at, ai = after
+            if torch_in:
+                import torch
+
+                if not (isinstance(at, torch.Tensor) and isinstance(ai, torch.Tensor) and at.dtype == torch.float32 and ai.dtype == torch.int32
+                        and at.device == o.device and ai.device == o.device and tuple(at.shape) == (n,) and tuple(ai.shape) == (n,)):
+                    raise ValueError(f"after must be a float32 and an int32 tensor of shape ({n},) on the rays' device")
+                at, ai = at.contiguous(), ai.contiguous()
+            else:
+                at, ai = np.ascontiguousarray(at, np.float32), np.ascontiguousarray(ai, np.int32)
+                if at.shape != (n,) or ai.shape != (n,):
+                    raise ValueError(f"after must be two arrays of shape ({n},), got {at.shape} and {ai.shape}")
+        b = self._batch_struct(n, o, d, m, backface_culling, ptr)
+        h = _abi.rt_ray_hit_lists()
+        h.max_hits = k
+        if at is not None:
+            h.after_t, h.after_id = ptr(at), ptr(ai)
+        if total:
+            h.total = ptr(cnt["total"])
+        if planes:
+            h.count = ptr(cnt["count"])
+            h.id, h.t, h.point, h.normal, h.material = (ptr(lists[name]) for name in ("id", "t", "point", "normal", "material"))
+        lib = _lib.load()
+        if torch_in:
+            _lib.check(lib.rt_list_intersections_device(self.handle, C.byref(b), C.byref(h), self._stream_of(o)))
+        else:
+            _lib.check(lib.rt_list_intersections(self.handle, C.byref(b), C.byref(h)))
+        if not planes:
+            return RayHitLists(None, None, None, None, None, None, cnt["total"])
+        return RayHitLists(cnt["count"], lists["id"].reshape(n, k), lists["t"].reshape(n, k), lists["point"].reshape(n, k, 3),
+                           lists["normal"].reshape(n, k, 3), lists["material"].reshape(n, k), cnt["total"] if total else None)
 
     def ray_order(self, origins, directions, origin_bits: int = 0) -> RayOrder:
         """A RayOrder for these rays on this scene's device, sorted on the device by the Morton code of origin and

@@ -29,6 +29,9 @@
  *   rt_any_intersection          <- Raytracer::has_any_intersection, raytracer.rs:24-106 (IntersectionTest,
  *                                   raytracer.rs:17-22), for a batch of HOST segments; blocks
  *   rt_any_intersection_device   <- same, DEVICE arrays, enqueued on the caller's stream
+ *   rt_list_intersections[_device] <- none (has_any_intersection visits every hit at t <= max_distance; this returns them):
+ *                                   the first K hits per ray in order and their number; rt_list_intersections_model is
+ *                                   its specification
  *   rt_closest_points[_device]   <- none (the reference has no point query): the nearest surface point per query
  *                                   point, Embree's rtcPointQuery; rt_closest_points_model is its specification
  *   rt_trace_rays     <- RaytracerRenderer::single_raytrace, src/renderer/raytracer_renderer.rs:147-264 (the colour of
@@ -430,7 +433,8 @@ typedef struct rt_ray_batch {
   uint32_t n_rays;            /* 0 is a valid no-op */
   const float* origin;        /* [n_rays][3] */
   const float* direction;     /* [n_rays][3], any length (normalised as Ray::new_with_mask does, ray.rs:52-57) */
-  const float* max_distance;  /* [n_rays], rt_any_intersection* only (raytracer.rs:28); NULL = +inf */
+  const float* max_distance;  /* [n_rays], rt_any_intersection* and rt_list_intersections* (raytracer.rs:28); NULL = +inf;
+                                 rt_cast_rays* ignores it */
   uint32_t flags;             /* RT_FLAG_BACKFACE_CULLING or 0 (sphere.rs:137-151, triangle.rs:154-168) */
 } rt_ray_batch;
 
@@ -518,6 +522,64 @@ int rt_closest_points_device(rt_scene* scene, const rt_point_batch* batch, const
 /* The specification, without a device or a tree: a LINEAR scan of `desc` with the same arithmetic.  HOST arrays; no HIP call.
  * The two calls above return the same bits. */
 int rt_closest_points_model(const rt_scene_desc* desc, const rt_point_batch* batch, const rt_point_hits* hits);
+
+/* ---- multi-hit ray queries: the first K hits of each ray, and how many there are ------------------------------------------------
+ *
+ * Everything a ray passes through (Open3D's list_intersections / count_intersections, Embree's multi-hit, trimesh's
+ * multiple_hits): thickness and x-ray probes, layered picking, transparency ordering, crossing counts.  The call works on
+ * whatever the handle holds after rt_scene_update*, rt_pose_apply*, rt_skin_apply* and rt_scene_rebuild*.
+ *
+ * Definition (csrc/rt_multihit.h holds the formulas).  `batch` is an rt_ray_batch as above, max_distance honoured.  A HIT is
+ * what the reference's `intersect` returns for one object, so at most one per object: for a sphere the root
+ * SphereData::intersect picks (a ray from outside gets the entry point only), for a triangle the literal matrix-inverse test;
+ * RT_FLAG_BACKFACE_CULLING applies sphere.rs:137-151 / triangle.rs:154-168 exactly as rt_cast_rays does.  A hit counts when
+ * t <= max_distance as computed (NULL = +inf; a NaN or negative max_distance admits nothing; a NaN t never counts).
+ *
+ * Order and cursor.  Hits are ordered by the key (t ascending; on equal t the LARGER canonical id first): the "later object
+ * wins" of rt_cast_rays, so entry 0 of every list is rt_cast_rays' answer bit for bit.  The optional cursor (after_t[i],
+ * after_id[i]) admits only keys strictly after it: t > after_t, or t == after_t and id < after_id; a NaN after_t admits
+ * nothing.  Feeding the last returned key back pages through all hits with no epsilon and without losing or repeating
+ * coincident hits.
+ *
+ * Output per ray for max_hits = K: `count` entries (0 .. K) in row i of each plane [n][K]; entries from `count` on hold the
+ * miss values of rt_ray_hits (id -1, t +inf, point and normal 0, material 0xFFFFFFFF).  `total` is the number of distinct
+ * objects with an admitted hit, which may exceed K: count == min(total, K).  Asking for `total` makes a ray whose list came
+ * back full walk again behind its last key until it has counted everything; a ray with fewer than K hits costs one walk either
+ * way.  Dead rays (see above) give count 0 and total 0.
+ *
+ * The result is a function of the scene description and the ray alone: it does not depend on the tree, on slot order, on
+ * split-clipped duplicate references or on the order a walk meets hits in.
+ *
+ * Validation (RT_ERR_INVALID_ARG + rt_last_error, before any HIP call; nothing is written): as the ray queries, and max_hits
+ * outside 1 .. RT_MAX_HITS_PER_RAY; exactly one of after_t / after_id NULL; every output NULL.
+ *
+ * Streams and concurrency: as the ray queries above.
+ *
+ * Not offered: inside / occupancy tests and signed distance (a sphere gives one hit, so crossing parity needs a definition of
+ * its own), both roots of a sphere, K above RT_MAX_HITS_PER_RAY, an ordered or wave-cooperative variant. */
+#define RT_MAX_HITS_PER_RAY 16u
+
+/* request and output of rt_list_intersections*.  Every output member nullable, at least one non-NULL: a NULL plane is not written. */
+typedef struct rt_ray_hit_lists {
+  uint32_t max_hits;       /* K: 1 .. RT_MAX_HITS_PER_RAY entries per ray */
+  const float* after_t;    /* [n] cursor: only keys strictly after (after_t, after_id) are admitted; both NULL = from the start */
+  const int32_t* after_id; /* [n] */
+  uint32_t* count;         /* [n] entries written for the ray, 0 .. K */
+  uint32_t* total;         /* [n] distinct objects with an admitted hit (>= count) */
+  int32_t* id;             /* [n][K] canonical object index; -1 from `count` on */
+  float* t;                /* [n][K] distance along the normalised direction; +inf from `count` on */
+  float* point;            /* [n][K][3] fma(d, t, o); 0 from `count` on */
+  float* normal;           /* [n][K][3] sphere: normalize(p - centre); triangle: its stored face normal; 0 from `count` on */
+  uint32_t* material;      /* [n][K] material row; 0xFFFFFFFF from `count` on */
+} rt_ray_hit_lists;
+
+/* HOST arrays: staged through device memory allocated for the call; returns when the results are in host memory. */
+int rt_list_intersections(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_hit_lists* lists);
+/* DEVICE arrays on the scene's device: enqueued on `hip_stream` (NULL = default stream); allocates nothing. */
+int rt_list_intersections_device(rt_scene* scene, const rt_ray_batch* batch, const rt_ray_hit_lists* lists, void* hip_stream);
+/* The specification, without a device or a tree: a LINEAR scan of `desc` with the same arithmetic.  HOST arrays; no HIP call.
+ * The two calls above return the same bits. */
+int rt_list_intersections_model(const rt_scene_desc* desc, const rt_ray_batch* batch, const rt_ray_hit_lists* lists);
 
 /* ---- radiance queries: Whitted shading of caller-supplied rays -------------------------------------------------------------
  *
