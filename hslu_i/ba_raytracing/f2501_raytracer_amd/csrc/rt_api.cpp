@@ -81,7 +81,7 @@ void rt_scene_destroy(rt_scene* s) {
       for (DevBuf* b : {&l.queues, &l.qcount, &l.trace_ws, &l.hard, &l.hitrec, &l.sets}) b->release();
     }
   }
-  for (DevBuf* b : {&s->blob, &s->aa, &s->cloud, &s->counters, &s->suplist, &s->fb, &s->aux_rgb, &s->costmap, &s->aux_id, &s->aux_t, &s->flag_geo, &s->flags, &s->cell_lists, &s->resolve_work, &s->progress_fb, &s->rays_argb})
+  for (DevBuf* b : {&s->blob, &s->aa, &s->cloud, &s->counters, &s->suplist, &s->fb, &s->aux_rgb, &s->costmap, &s->aux_id, &s->aux_t, &s->flag_geo, &s->flags, &s->cell_lists, &s->resolve_work, &s->cell_wide, &s->progress_fb, &s->rays_argb})
     b->release();
   rt_scene_release_update(s);
   delete s;
@@ -151,7 +151,7 @@ int rt_scene_memory_info(const rt_scene* s, rt_scene_info* out) {
   out->bytes_bvh = s->bytes_bvh;
   out->bytes_geometry = s->blob.cap > s->bytes_bvh ? s->blob.cap - s->bytes_bvh : 0;
   out->bytes_flags = s->flags.cap + s->flag_geo.cap;
-  out->bytes_cell_lists = s->cell_lists.cap + s->resolve_work.cap;
+  out->bytes_cell_lists = s->cell_lists.cap + s->resolve_work.cap + s->cell_wide.cap;
   out->bytes_tables = s->aa.cap + s->cloud.cap + s->counters.cap + s->suplist.cap + s->costmap.cap;
   for (const auto& w : s->ws) {
     out->bytes_workspace += w.bytes();
@@ -322,6 +322,7 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
       // per-cell candidate lists, written by the same kernel: 16 bytes per cell and light (16-bit leaf slots), when the
       // scene allows it and a quarter of the free memory holds them
       s->cell_lists_built = false;
+      s->cell_wide_built = false;
       B.cell_list_out = nullptr;
       const size_t list_bytes = (size_t)s->n_cells * s->dev.n_lights * 16u;
       size_t free_b = 0, total_b = 0;
@@ -363,6 +364,20 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
           r.cell = a;
           r.eps_push = P->beam_eps_push, r.eps_ulp = P->beam_eps_ulp;
           r.work = (uint32_t*)s->resolve_work.p;
+          // lists with 9 to 32 survivors go to a pool of 64-byte records, sized from what the budget still leaves and counted
+          // with the lists; the stage empties it whenever it runs.  RT_CELL_WIDE=0 (read once per process) leaves it out.
+          static const char* const wide_env = getenv("RT_CELL_WIDE");
+          static const bool wide_off = wide_env && *wide_env == '0';
+          const size_t used = flag_bytes + list_bytes + temp_bytes;
+          const size_t wide_bytes = wide_off || used >= s->budget ? 0 : rt_cell_wide_pool_bytes(s->n_cells, s->dev.n_lights, s->budget - used, &r.wide_cap);
+          if (wide_bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && wide_bytes <= (free_b + s->cell_wide.cap) / 4 &&
+              s->cell_wide.ensure(wide_bytes) == RT_OK) {
+            r.wide = (uint16_t*)s->cell_wide.p;
+            r.wide_count = (uint32_t*)((char*)s->cell_wide.p + (size_t)r.wide_cap * 2u * RT_CELL_WIDE_SLOTS);
+            s->cell_wide_built = true;
+          } else {
+            r.wide_cap = 0u;
+          }
           e = (hipError_t)rt_launch_cell_resolve(s->dev, r, stream);
           if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_cell_resolve_kernel launch failed: %s", hipGetErrorString(e));
           trace_point(stream, "rt_cell_resolve_kernel: cells, lights, cells per chunk", s->n_cells, s->dev.n_lights, r.chunk_cells);
@@ -371,10 +386,12 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
         }
       }
       if (!s->cell_lists_built) s->resolve_work.release();
+      if (!s->cell_wide_built) s->cell_wide.release();
       memcpy(s->flags_key, key, sizeof(key));
     }
     P->recv_flags = (const uint16_t*)s->flags.p;
     if (s->cell_lists_built && !p->tuning.no_cell_lists) P->cell_lists = (const uint4*)s->cell_lists.p;
+    if (P->cell_lists && s->cell_wide_built) P->cell_wide = (const uint32_t*)s->cell_wide.p;
   }
   if (!P->cell_lists) s->notes |= RT_NOTE_CELL_LISTS_OFF;
   return RT_OK;

@@ -28,3 +28,16 @@ size_t rt_cell_resolve_temp_bytes(uint32_t n_cells, size_t budget_left, uint32_t
   *chunk_cells = (uint32_t)chunk;
   return 4096u + 4u * chunk;
 }
+
+// the records at 64 bytes each, then 64 bytes for the counter
+size_t rt_cell_wide_pool_bytes(uint32_t n_cells, uint32_t n_lights, size_t budget_left, uint32_t* wide_cap) {
+  *wide_cap = 0u;
+  const size_t rec = 2u * RT_CELL_WIDE_SLOTS;
+  if (n_cells == 0u || n_lights == 0u || budget_left < 2u * rec) return 0;
+  size_t cap = (budget_left - rec) / rec;
+  const size_t lists = (size_t)n_cells * n_lights;
+  if (cap > (lists + 7u) / 8u) cap = (lists + 7u) / 8u;
+  if (cap > RT_CELL_WIDE_MAX_RECORDS) cap = RT_CELL_WIDE_MAX_RECORDS;
+  *wide_cap = (uint32_t)cap;
+  return cap * rec + rec;
+}

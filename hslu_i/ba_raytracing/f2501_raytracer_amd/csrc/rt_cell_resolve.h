@@ -6,7 +6,14 @@
 // can only thin out what is listed).  This stage, right after it, walks the threaded tree once per overflowed (cell, light)
 // with the beam of rt_cell_prune_cell, offers every leaf slot it reaches to the near-side rule below and to rt_prune_rule,
 // and writes the survivors as a normal list when there are at most 8 of them (none: an empty list and the cell's
-// triangle-clear bit).  More than 8: the marker stays, the render keeps walking for that cell.
+// triangle-clear bit).  More than 8: the marker stays, the render keeps walking for that cell -- unless a pool of WIDE RECORDS
+// is given (RtCellResolveArgs::wide): then a list with 9 .. RT_CELL_WIDE_SLOTS survivors gets a record of the pool, 64 bytes
+// at a 64-byte boundary: RT_CELL_WIDE_SLOTS 16-bit slots, distinct, padded with RT_PRUNE_LIST_END.  Entry 0 of the 16-byte
+// list stays RT_PRUNE_LIST_OVERFLOW -- what follows the marker is read by nobody who does not know of the records, so every
+// such reader keeps walking, which gives what the record gives -- entry 1 becomes RT_CELL_WIDE_MARK (0xFFFD: no leaf slot, they
+// end at 65532, and neither of the two markers), entries 2 and 3 the record's index in two 15-bit digits, the rest
+// RT_PRUNE_LIST_END.  More than RT_CELL_WIDE_SLOTS survivors, or no record left in the pool: the list stays as it was.  Which
+// record a list gets depends on the order of the device's atomics; nothing that is rendered does.
 //
 // Compiled twice, as rt_cell_prune.h is: rt_cell_resolve_packed (rt_cell_resolve.cpp) calls rt_cell_resolve_cell in a loop on the
 // host, rt_cell_resolve_kernel (rt_cell_resolve.hip) is the same function with a thread index.  Every float operation is a
@@ -22,6 +29,11 @@
 #define RT_RESOLVE_NO_INFLATE 0x200u   // ABLATION (unsound): boxes are not inflated by max(rho, delta)
 #define RT_RESOLVE_NO_NEAR 0x400u      // counting only (sound, weaker): without the near-side rule
 
+// wide records: slots per record (64 bytes: one 64-byte scalar load in the render), the mark in entry 1 of the 16-byte list
+#define RT_CELL_WIDE_SLOTS 32u
+#define RT_CELL_WIDE_MARK 0xFFFDu
+#define RT_CELL_WIDE_MAX_RECORDS (1u << 30)  // two 15-bit digits
+
 // what the stage needs besides RtDevScene
 struct RtCellResolveArgs {
   RtCellPruneArgs cell;    // as the prune stage got it (flag_geo, lists, flags, cells, cloud centre, beam constants); mode: RT_PRUNE_* | RT_RESOLVE_*
@@ -30,7 +42,27 @@ struct RtCellResolveArgs {
   uint32_t chunk_cells;
   uint8_t* counts;         // optional, [n_cells][n_lights]: survivors of every formerly overflowed list, capped at 255 (the
                            // walk then does not stop at the ninth); nullptr in the render
+  // the pool of wide records; all zero: off, and the stage writes what it wrote before there were any
+  uint16_t* wide;          // [wide_cap][RT_CELL_WIDE_SLOTS], 64-byte aligned
+  uint32_t wide_cap;       // records in the pool, at most RT_CELL_WIDE_MAX_RECORDS
+  uint32_t* wide_count;    // records asked for so far (it runs past wide_cap when the pool is full); zero before the stage
 };
+
+// the index of the record the 16-byte list w points to, or ~0u: not a wide list
+RT_HD static inline uint32_t rt_cell_wide_index(const uint16_t* w) {
+  if (w[0] != RT_PRUNE_LIST_OVERFLOW || w[1] != RT_CELL_WIDE_MARK) return ~0u;
+  return (uint32_t)(w[2] & 0x7FFFu) | ((uint32_t)(w[3] & 0x7FFFu) << 15);
+}
+// the next free record of the pool, or ~0u: the pool is full (or off)
+RT_HD static inline uint32_t rt_cell_wide_take(const RtCellResolveArgs& a) {
+  if (!a.wide || !a.wide_count || a.wide_cap == 0u) return ~0u;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t at = __hip_atomic_fetch_add(a.wide_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (a builtin: no device header needed)
+#else
+  const uint32_t at = (*a.wide_count)++;
+#endif
+  return at < a.wide_cap && at < RT_CELL_WIDE_MAX_RECORDS ? at : ~0u;
+}
 
 // one cell as the stage sees it: hull, centre, and what does not depend on the light
 struct RtResolveCell {
@@ -207,16 +239,27 @@ RT_HD static inline void rt_cell_resolve_cell(const RtDevScene& sc, const char* 
     RtPruneBeam B;
     rt_resolve_beam(sc, base, a.cell, K, l, B);
     uint32_t n = 0;
-    uint16_t out[RT_PRUNE_LIST_SLOTS];
+    uint16_t out[RT_CELL_WIDE_SLOTS];
     const bool count_all = counts != nullptr;
+    const uint32_t room = a.wide ? RT_CELL_WIDE_SLOTS : RT_PRUNE_LIST_SLOTS;
     const bool ok = rt_resolve_walk(sc, base, a, K, B, [&](uint32_t slot) {
-      if (n < RT_PRUNE_LIST_SLOTS) out[n] = (uint16_t)slot;
+      if (n < room) out[n] = (uint16_t)slot;
       n++;
-      return n <= RT_PRUNE_LIST_SLOTS || count_all;  // the ninth survivor: the list stays overflowed
+      return n <= room || count_all;  // one survivor more than there is room for: the list stays overflowed
     });
     if (!ok) continue;
     if (counts) counts[l] = (uint8_t)(n < 255u ? n : 255u);
-    if (n > RT_PRUNE_LIST_SLOTS) continue;
+    if (n > room) continue;
+    if (n > RT_PRUNE_LIST_SLOTS) {  // 9 .. RT_CELL_WIDE_SLOTS: a wide record, if the pool has one left
+      const uint32_t at = rt_cell_wide_take(a);
+      if (at == ~0u) continue;
+      for (uint32_t k = n; k < RT_CELL_WIDE_SLOTS; k++) out[k] = (uint16_t)RT_PRUNE_LIST_END;
+      memcpy(__builtin_assume_aligned(a.wide + (size_t)at * RT_CELL_WIDE_SLOTS, 64), out, 2u * RT_CELL_WIDE_SLOTS);
+      const uint16_t mark[RT_PRUNE_LIST_SLOTS] = {(uint16_t)RT_PRUNE_LIST_OVERFLOW, (uint16_t)RT_CELL_WIDE_MARK, (uint16_t)(at & 0x7FFFu), (uint16_t)((at >> 15) & 0x7FFFu),
+                                                  (uint16_t)RT_PRUNE_LIST_END, (uint16_t)RT_PRUNE_LIST_END, (uint16_t)RT_PRUNE_LIST_END, (uint16_t)RT_PRUNE_LIST_END};
+      memcpy(__builtin_assume_aligned(w, 16), mark, 16);
+      continue;
+    }
     for (uint32_t k = n; k < RT_PRUNE_LIST_SLOTS; k++) out[k] = (uint16_t)RT_PRUNE_LIST_END;
     memcpy(__builtin_assume_aligned(w, 16), out, 16);
     if (n == 0u) fl |= 1u << l, fl_changed = true;  // no triangle can shadow this cell for light l
@@ -231,5 +274,9 @@ void rt_cell_resolve_packed(const RtPackedScene& pk, RtCellResolveArgs a);
 // the temporary memory of the device stage: bytes for a.work and (out) a.chunk_cells, given what the scene's budget leaves;
 // never more than 64 MiB.  0 = nothing useful fits, the stage is left out.
 size_t rt_cell_resolve_temp_bytes(uint32_t n_cells, size_t budget_left, uint32_t* chunk_cells);
+// the pool of wide records: bytes (the records, then 64 bytes that hold the counter) and (out) its capacity in records, given
+// what the budget leaves after flags, lists and work list: one record per eight lists at the most (half the lists' own
+// bytes).  0 = no pool.
+size_t rt_cell_wide_pool_bytes(uint32_t n_cells, uint32_t n_lights, size_t budget_left, uint32_t* wide_cap);
 // the kernels (rt_cell_resolve.hip); returns hipError_t as int
 int rt_launch_cell_resolve(const RtDevScene& sc, const RtCellResolveArgs& a, void* stream);

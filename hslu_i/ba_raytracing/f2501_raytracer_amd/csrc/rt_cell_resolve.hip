@@ -11,7 +11,8 @@
 //                                 covers the chunk; threads beyond the count the find kernel left on the device return at
 //                                 once, so the host never waits for the count.
 // They run once per scene and light-cloud size, right after rt_cell_prune_kernel on the same stream, and touch only the lists,
-// the flags and the temporary work list (at most 64 MiB, rt_cell_resolve_temp_bytes; larger scenes go chunk by chunk).
+// the flags, the temporary work list (at most 64 MiB, rt_cell_resolve_temp_bytes; larger scenes go chunk by chunk) and, when
+// there is one, the pool of wide records (one atomic on its counter per record).
 #include <hip/hip_runtime.h>
 
 #include "rt_cell_resolve.h"
@@ -49,6 +50,7 @@ int rt_launch_cell_resolve(const RtDevScene& sc, const RtCellResolveArgs& a, voi
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(a.work, 0, RT_CELL_RESOLVE_COUNTERS * 4u, st);
   if (e != hipSuccess) return (int)e;
+  if (a.wide && a.wide_count && (e = hipMemsetAsync(a.wide_count, 0, 4u, st)) != hipSuccess) return (int)e;  // the pool starts empty
   uint32_t* list = a.work + RT_CELL_RESOLVE_COUNTERS;
   uint32_t k = 0;
   for (uint32_t c0 = 0; c0 < n; k++) {

@@ -120,7 +120,15 @@ struct RtDevParams {
   // (receiver cell, light): what survives the cell's fat beam, written by rt_flags_kernel together with the flags.  The
   // union of the lists of a wavefront's cells replaces its candidate walk (nullptr = not in use).
   const uint4* cell_lists;
-  uint16_t* cell_list_out;
+  // Wide records of the lists (rt_cell_resolve.h): 16 dwords = 32 x 16-bit leaf slots each, distinct, padded with 0xFFFF.  A list
+  // {0xFFFE, 0xFFFD, i & 0x7FFF, i >> 15, ...} stands for record i; only rt_primary_soft*_kernel (the list kernels) follow it,
+  // every other reader sees an overflowed list and walks.  nullptr: no list carries the mark.  The pointer shares its place
+  // with cell_list_out, which rt_flags_kernel alone reads and no render launch sets: a field of its own moves the kernel
+  // arguments behind RtDevParams, and that alone changed the register allocation of rt_rays_stream_kernel.
+  union {
+    uint16_t* cell_list_out;
+    const uint32_t* cell_wide;
+  };
   uint16_t* flag_out;
   const float4* flag_geo;         // canonical triangles: {v1, bits(R)} {e1, bits(first cell)} {e2, 0}
   uint32_t n_cells;

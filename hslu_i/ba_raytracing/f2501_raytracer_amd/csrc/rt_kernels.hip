@@ -24,6 +24,10 @@
 //     candidate triangle list (beam-level conservative culling), kept in the lanes of a VGPR.  Wavefronts whose hit
 //     points are unrelated (the list overflows) defer their (hit point, light) pairs to rt_hard_kernel: N samples on
 //     N lanes, every lane walking a threaded (stackless) copy of the tree for its own ray;
+//   * per-cell candidate lists (8 x 16-bit leaf slots per receiver cell and light; 0xFFFF = end, entry 0 == 0xFFFE = more than
+//     8) replace that walk where every lane's cell has a complete one.  In the three list kernels rt_primary_soft*_kernel an
+//     overflowed list {0xFFFE, 0xFFFD, i & 0x7FFF, i >> 15, ...} stands for wide record i of P.cell_wide: 32 slots in 64 bytes,
+//     read through the scalar path; every other kernel sees the marker alone and walks;
 //   * BVH traversal is WAVE-COOPERATIVE: the 64 rays of a wavefront walk the tree together.  The
 //     current node index is wave-uniform, node / triangle / sphere / light records are fetched with
 //     scalar loads (constant address space -> s_load_dwordx4/x16), and the traversal stack is ONE
@@ -697,6 +701,7 @@ struct CfgGeneric {
   static constexpr bool FEW_SPHERES = false; // true: n_spheres < 32
   static constexpr bool FAR_ORIGINS = false; // true: rays may start far outside the scene (CfgRays)
   static constexpr bool OCC_MEMO = false;    // true: shadow_ray keeps the last transmissive occluder's constants (OccMemo)
+  static constexpr bool WIDE = false;        // true: a per-cell list may stand for a wide record of P.cell_wide (RT_CELL_WIDE_MARK)
 };
 template <uint32_t N_, int TABLES_>
 struct CfgSoft {
@@ -708,6 +713,8 @@ struct CfgSoft {
   static constexpr bool FAR_ORIGINS = false;
   // (the flags-only kernels keep no memo: its eight registers cost them a spilled SGPR, two VGPRs and 4 B of scratch)
   static constexpr bool OCC_MEMO = TABLES_ == CFG_TABLES_LISTS;
+  // (the list kernels alone follow the wide records; to every other kernel such a list is an overflowed one, and it walks)
+  static constexpr bool WIDE = TABLES_ == CFG_TABLES_LISTS;
 };
 // Rays the CALLER supplies (rt_rays.h).  The receiver tables stand for hit points that lie ON their surface to within the
 // rounding of p = o + t d for a ray that starts in or near the scene (collect_light_candidates, COLLECT_FLAGS: 4e-7 |p|).  A
@@ -947,6 +954,11 @@ struct FatBeam {
 #define RT_CELL_LIST_SLOTS 8u
 #define RT_CELL_LIST_END 0xFFFFu
 #define RT_CELL_LIST_OVERFLOW 0xFFFEu
+// Wide records (rt_cell_resolve.h, third stage): an overflowed list whose entry 1 is 0xFFFD stands for a 64-byte record of
+// P.cell_wide, 32 x 16-bit leaf slots, distinct, padded with RT_CELL_LIST_END; entries 2 and 3 are the record's index in two
+// 15-bit digits.  RT_CELL_WIDE_HEAD: the first dword of such a list.
+#define RT_CELL_WIDE_HEAD 0xFFFDFFFEu
+#define RT_CELL_WIDE_DWORDS 16u
 enum { COLLECT_OWN = 0, COLLECT_FLAGS = 1 };
 
 // MODE: COLLECT_OWN -- a wavefront's own collection at render time; COLLECT_FLAGS -- fat beams of receiver cells (fb): no
@@ -2075,11 +2087,13 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
         uint4 lst = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
         if (use && cidx != RT_NO_CELL) lst = P.cell_lists[(size_t)cidx * sc.n_lights + l];
         // (mirrors union_cell_lists: calling it changes the benchmark-path kernels, profiles/shared_rules.md)
-        const lanemask unusable = use_m & (wave_ballot(cidx == RT_NO_CELL) | wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_OVERFLOW));
+        // (the list kernels: a lane whose overflowed list stands for a wide record is usable; plain overflow and no cell alone make the set walk)
+        const lanemask wide_m = C::WIDE ? use_m & wave_ballot(lst.x == RT_CELL_WIDE_HEAD) : 0ull;
+        const lanemask unusable = use_m & (wave_ballot(cidx == RT_NO_CELL) | wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_OVERFLOW)) & ~wide_m;
         if (!unusable) {
           have_pre = true;
           const uint32_t lane_id = threadIdx.x & 63u;
-          for (lanemask todo = use_m & ~wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_END); todo;) {
+          for (lanemask todo = use_m & ~wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_END) & ~wide_m; todo;) {
             const int fl = __ffsll((long long)todo) - 1;
             const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cidx, fl);
             auto add_slot = [&](uint32_t slot) {  // (uniform)
@@ -2097,11 +2111,71 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
             add_pair(lst.x), add_pair(lst.y), add_pair(lst.z), add_pair(lst.w);
             todo &= ~wave_ballot(cidx == c);
           }
+          // ... then the cells with a wide record, in a loop of their own (the loop above is the one every kernel has): the
+          // record comes through the scalar path (its index is uniform after the readlane), a quarter at a time; padding ends
+          // it.  Marked unlikely: the block is laid out behind the light loop, whose code stays where it was.
+          if constexpr (C::WIDE) {
+            if (__builtin_expect(wide_m != 0ull, 0))
+            for (lanemask todo = wide_m; todo;) {
+              const int fl = __ffsll((long long)todo) - 1;
+              const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cidx, fl);
+              const uint32_t iw = (uint32_t)__builtin_amdgcn_readlane((int)lst.y, fl);
+              const uint4* rec = (const uint4*)(P.cell_wide + (size_t)((iw & 0x7FFFu) | ((iw >> 1) & 0x3FFF8000u)) * RT_CELL_WIDE_DWORDS);
+              auto add_slot = [&](uint32_t slot) {  // (as above)
+                if (slot >= RT_CELL_LIST_OVERFLOW) return;
+                const lanemask filled = pre_count >= 64u ? ~0ull : ((1ull << pre_count) - 1ull);
+                if (wave_ballot(pre_reg == slot) & filled) return;
+                lane_put(pre_reg, pre_count, slot, lane_id);
+                pre_count++;
+              };
+              // (the slots of one record are distinct: into an empty union they go without the search)
+              auto put_slot = [&](uint32_t slot) {
+                if (slot >= RT_CELL_LIST_OVERFLOW) return;
+                lane_put(pre_reg, pre_count, slot, lane_id);
+                pre_count++;
+              };
+              const bool fresh = pre_count == 0u;
+              for (uint32_t k = 0; k < RT_CELL_WIDE_DWORDS / 4u; k++) {
+                const uint4 q = uload(rec + k);
+                if (fresh) {
+                  put_slot(q.x & 0xFFFFu), put_slot(q.x >> 16), put_slot(q.y & 0xFFFFu), put_slot(q.y >> 16);
+                  put_slot(q.z & 0xFFFFu), put_slot(q.z >> 16), put_slot(q.w & 0xFFFFu), put_slot(q.w >> 16);
+                } else {
+                  add_slot(q.x & 0xFFFFu), add_slot(q.x >> 16), add_slot(q.y & 0xFFFFu), add_slot(q.y >> 16);
+                  add_slot(q.z & 0xFFFFu), add_slot(q.z >> 16), add_slot(q.w & 0xFFFFu), add_slot(q.w >> 16);
+                }
+                if ((q.w >> 16) == RT_CELL_LIST_END) break;
+              }
+              todo &= ~wave_ballot(cidx == c);
+            }
+          }
           if (pre_count > 64u) have_pre = false;  // (more than a VGPR's worth of lanes: walk)
         }
       }
 #if RT_PROFILE == 4
       prof_walked = (walk_tris && !have_pre) ? 1u : 0u, prof_listed = have_pre ? 1u : 0u, prof_pre = have_pre ? pre_count : 0u;
+#endif
+#if RT_PROFILE == 6  // why the sets that still walk do, and what the wide records (at 32 and at 16 slots) take off the walks
+      if (!CULL && (C::TABLES == CFG_TABLES_LISTS || (C::TABLES == CFG_TABLES_RUNTIME && P.cell_lists)) && walk_tris) {
+        uint32_t tix = threadIdx.x;
+        RT_OPAQUE(tix);
+        const uint32_t cidx = __float_as_uint(stash[RT_STASH_CELL * 256u + tix]);
+        uint4 lst = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+        if (use && cidx != RT_NO_CELL) lst = P.cell_lists[(size_t)cidx * sc.n_lights + l];
+        const bool is_wide = C::WIDE && lst.x == RT_CELL_WIDE_HEAD;
+        const lanemask nocell_m = use_m & wave_ballot(cidx == RT_NO_CELL);
+        const lanemask plain_m = use_m & wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_OVERFLOW && !is_wide);
+        const lanemask wide_m = use_m & wave_ballot(is_wide);
+        bool longer = false;  // this lane's record holds more than 16 slots
+        if (use && is_wide) longer = (P.cell_wide[(size_t)((lst.y & 0x7FFFu) | ((lst.y >> 1) & 0x3FFF8000u)) * RT_CELL_WIDE_DWORDS + 8u] & 0xFFFFu) != RT_CELL_LIST_END;
+        W.prof[0] += have_pre ? 0u : 1u;                                    // sets that walk
+        W.prof[1] += (!have_pre && nocell_m) ? 1u : 0u;                     // ... with a lane that has no cell
+        W.prof[2] += (!have_pre && !nocell_m && plain_m) ? 1u : 0u;         // ... else with a lane on a plain overflowed list
+        W.prof[3] += (!have_pre && !nocell_m && !plain_m) ? 1u : 0u;        // ... else because the union exceeds 64 slots
+        W.prof[4] += (have_pre && wide_m) ? 1u : 0u;                        // listed sets that read a wide record (they walked before)
+        W.prof[5] += (have_pre && wide_m && !wave_ballot(longer)) ? 1u : 0u;  // ... whose records all hold at most 16 slots
+        W.prof[6] += have_pre ? 1u : 0u;                                    // listed sets
+      }
 #endif
       if (test_spheres) {
         cand = collect_light_candidates<CULL, COLLECT_OWN, C>(sc, W, use, sf.p, centre, P, p_first, p_spread, P.cand_cap, nullptr, walk_tris,

@@ -962,7 +962,8 @@ typedef struct rt_scene_info {
   uint64_t bytes_geometry;    /* spheres, triangle records (intersection + shading), ids, materials, lights, receiver records */
   uint64_t bytes_bvh;         /* BVH nodes + the 8 per-octant copies + the threaded copy */
   uint64_t bytes_flags;       /* receiver flags + the cell geometry rt_flags_kernel reads (optional table, under the budget) */
-  uint64_t bytes_cell_lists;  /* per-cell candidate lists (optional table, under the budget; 0 = not built) */
+  uint64_t bytes_cell_lists;  /* per-cell candidate lists, the work list of their third stage and the pool of wide records (64 bytes per list of 9 to 32
+                                 candidates; RT_CELL_WIDE=0 in the environment leaves it out) -- optional tables, under the budget; 0 = not built */
   uint64_t bytes_tables;      /* AA samples, light clouds, tile lists, counters */
   uint64_t bytes_workspace;   /* ray queues, sort workspace, pair queues, set records, pixel accumulators of every frame slot in use */
   uint64_t bytes_frames;      /* frame buffer + aux planes rt_render keeps for host callers */

@@ -6,8 +6,9 @@ rt_flags_kernel with lists, reads lists and flags back, runs rt_cell_prune_kerne
 and after pruning: listed slots, non-empty lists, lists emptied, triangle-clear bits gained per light, and the overflowed
 lists (more than 8 candidates: left alone by that kernel, the render walks the tree for such a cell).  Then it runs
 rt_cell_resolve_kernel with survivor counts and reports the overflowed lists before and after it, a histogram of the
-survivors per formerly overflowed list (0, 1-4, 5-8, 9-16, more) and the stage's device time (timed in a run of its own
-without the counts, as the render launches it).  A probe compiled on the fly links against the built librt_hip.so, so the
+survivors per formerly overflowed list (0, 1-4, 5-8, 9-16, more; and of those above 8: 9-16, 17-24, 25-32, 33-64, more) and the
+stage's device time (timed in a run of its own without the counts, as the render launches it: once without and once with the
+pool of wide records, whose records it then counts).  A probe compiled on the fly links against the built librt_hip.so, so the
 kernels counted here are the ones that ship.  Prints one JSON line.
 
     python tools/cell_list_stats.py [--scene semesterbild] [--model text] [--budget BYTES]
@@ -47,9 +48,10 @@ int probe_pack(const rt_scene_desc* d, uint64_t budget, uint32_t* out) {
 }
 // lists [n_cells][n_lights][8] and flags [n_cells]: raw_* as rt_flags_kernel leaves them, out_* after rt_cell_prune_kernel,
 // res_* after rt_cell_resolve_kernel; counts [n_cells][n_lights]: survivors of every formerly overflowed list (capped at 255);
-// ms = {-, prune, resolve as the render launches it, resolve with counts}
+// ms = {resolve with the pool of wide records, prune, resolve as the render launches it without a pool, resolve with counts};
+// wide = {records the pool has room for, records asked for, pool bytes}, wide_lists: the lists after the run with the pool
 int probe_run(const float* cloud, uint64_t n_floats, const float* f, float eps, uint64_t budget, uint16_t* raw_lists, uint16_t* raw_flags, uint16_t* out_lists,
-              uint16_t* out_flags, uint16_t* res_lists, uint16_t* res_flags, uint8_t* counts, float* ms) {
+              uint16_t* out_flags, uint16_t* res_lists, uint16_t* res_flags, uint8_t* counts, float* ms, uint64_t* wide, uint16_t* wide_lists) {
   if (!g.n_cells || g.dev.n_lights > 8u || g.dev.n_slots > 65533u) return -100;
   std::vector<float> scaled;
   float ball[4];
@@ -121,6 +123,27 @@ int probe_run(const float* cloud, uint64_t n_floats, const float* f, float eps, 
   TRY(hipMemcpy(res_lists, lists, list_bytes, hipMemcpyDeviceToHost));
   TRY(hipMemcpy(res_flags, flags, flag_bytes, hipMemcpyDeviceToHost));
   TRY(hipMemcpy(counts, dcounts, (size_t)g.n_cells * g.dev.n_lights, hipMemcpyDeviceToHost));
+  // ... and a third time with the pool of wide records, sized as the render sizes it
+  wide[0] = wide[1] = wide[2] = 0;
+  uint32_t cap = 0;
+  const size_t pool_bytes = budget > used + temp ? rt_cell_wide_pool_bytes(g.n_cells, g.dev.n_lights, budget - used - temp, &cap) : 0;
+  if (pool_bytes) {
+    char* pool = nullptr;
+    TRY(hipMalloc((void**)&pool, pool_bytes));
+    TRY(hipMemcpy(lists, out_lists, list_bytes, hipMemcpyHostToDevice));
+    TRY(hipMemcpy(flags, out_flags, flag_bytes, hipMemcpyHostToDevice));
+    r.counts = nullptr, r.wide = (uint16_t*)pool, r.wide_cap = cap, r.wide_count = (uint32_t*)(pool + (size_t)cap * 2u * RT_CELL_WIDE_SLOTS);
+    TRY(hipEventRecord(e[1], nullptr));
+    TRY((hipError_t)rt_launch_cell_resolve(sc, r, nullptr));
+    TRY(hipEventRecord(e[2], nullptr));
+    TRY(hipDeviceSynchronize());
+    TRY(hipEventElapsedTime(&ms[0], e[1], e[2]));
+    uint32_t asked = 0;
+    TRY(hipMemcpy(&asked, r.wide_count, 4, hipMemcpyDeviceToHost));
+    TRY(hipMemcpy(wide_lists, lists, list_bytes, hipMemcpyDeviceToHost));
+    wide[0] = cap, wide[1] = asked, wide[2] = pool_bytes;
+    TRY(hipFree(pool));
+  }
   TRY(hipFree(r.work));
   TRY(hipFree(dcounts));
   TRY(hipFree(blob));
@@ -147,6 +170,10 @@ def resolve_report(over, new_l, res_l, new_f, res_f, counts, nl):
             "overflowed_lists_after_per_light": [int(v) for v in still.sum(0)],
             "survivors_per_formerly_overflowed_list": {"0": int((n == 0).sum()), "1-4": int(((n >= 1) & (n <= 4)).sum()), "5-8": int(((n >= 5) & (n <= 8)).sum()),
                                                        "9-16": int(((n >= 9) & (n <= 16)).sum()), ">16": int((n > 16).sum())},
+            # (the counts saturate at 255: every bin below is exact)
+            "survivors_of_the_lists_still_overflowed": {"9-16": int(((n >= 9) & (n <= 16)).sum()), "17-24": int(((n >= 17) & (n <= 24)).sum()),
+                                                        "25-32": int(((n >= 25) & (n <= 32)).sum()), "33-64": int(((n >= 33) & (n <= 64)).sum()),
+                                                        ">64": int((n > 64).sum())},
             "slots_listed_by_the_stage": int(((res_l < 0xFFFE) & (over & ~still)[:, :, None]).sum()),
             "clear_bits_gained_per_light": [int((((res_f & ~new_f) >> l) & 1).sum()) for l in range(nl)],
             "lists_that_were_not_overflowed_and_changed": int((~same & ~over).sum()),
@@ -182,9 +209,14 @@ def main():
     raw_f, new_f, res_f = (np.zeros(n_cells, np.uint16) for _ in range(3))
     counts = np.zeros((n_cells, nl), np.uint8)
     ms = np.zeros(4, np.float32)
+    wide, wide_l = np.zeros(3, np.uint64), np.zeros((n_cells, nl, 8), np.uint16)
     rc = probe.probe_run(ptr(cs), C.c_uint64(cs.size), ptr(f), C.c_float(cfg.eps_distance), C.c_uint64(args.budget), ptr(raw_l), ptr(raw_f), ptr(new_l), ptr(new_f),
-                         ptr(res_l), ptr(res_f), ptr(counts), ptr(ms))
+                         ptr(res_l), ptr(res_f), ptr(counts), ptr(ms), ptr(wide), ptr(wide_l))
     assert rc == 0, f"probe_run: {rc}"
+    marked = (wide_l[:, :, 0] == 0xFFFE) & (wide_l[:, :, 1] == 0xFFFD)
+    wide_report = {"pool_records": int(wide[0]), "records_asked_for": int(wide[1]), "pool_bytes": int(wide[2]), "wide_lists": int(marked.sum()),
+                   "wide_lists_per_light": [int(v) for v in marked.sum(0)], "plain_overflowed_lists_left": int(((wide_l[:, :, 0] == 0xFFFE) & ~marked).sum()),
+                   "lists_without_a_record_that_differ": int((~marked & (wide_l != res_l).any(2)).sum()), "resolve_stage_with_pool_ms": float(ms[0])}
     over = raw_l[:, :, 0] == 0xFFFE
     usable = ~over
 
@@ -206,6 +238,7 @@ def main():
            "slots_removed_fraction": (before["listed_slots"] - after["listed_slots"]) / max(1, before["listed_slots"]),
            "prune_kernel_ms": float(ms[1]),
            "resolve": resolve_report(over, new_l, res_l, new_f, res_f, counts, nl), "resolve_stage_ms": float(ms[2]), "resolve_stage_with_counts_ms": float(ms[3]),
+           "wide": wide_report,
            "build_id": _lib.load().rt_build_id().decode()}
     print(json.dumps(res))
 

@@ -2,12 +2,14 @@
 // candidate lists (csrc/rt_cell_resolve.h, rt_cell_resolve.cpp) and the scene packer, meant to be compiled host-only under
 // -fsanitize=address,undefined: the walk indexes the threaded tree, the leaf records and the lists by values read from memory.
 //
-//   cell_resolve_check SCENE.bin BUDGET_BYTES STRIDE
+//   cell_resolve_check SCENE.bin BUDGET_BYTES STRIDE [POOL_RECORDS]
 //
 // SCENE.bin (tests/test_cell_resolve_sanitize.py writes it): uint32 {n_spheres, n_triangles, n_materials, n_lights, n_cloud_floats},
 // then sphere centres, r^2, 1/r (float), sphere materials (uint32), triangle v1, e1, e2, normals (float), triangle materials
 // (uint32), materials, lights, the light-cloud table, {fw, fh, fd, eps} (float).  Every STRIDE-th cell gets all its lists set to the
-// overflow marker and resolved; the program prints how many lists it resolved, emptied and left overflowed.
+// overflow marker and resolved; the program prints how many lists it resolved, emptied and left overflowed.  With POOL_RECORDS the
+// stage gets a pool of that many wide records (64 bytes each, at a 64-byte boundary, exactly that long: a write past the last
+// record is a write past the allocation), and every list that carries the mark is followed to its record.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -25,7 +27,7 @@ static bool take(FILE* f, std::vector<T>& v, size_t n) {
 }
 
 int main(int argc, char** argv) {
-  if (argc != 4) return fprintf(stderr, "usage: %s SCENE.bin BUDGET_BYTES STRIDE\n", argv[0]), 2;
+  if (argc != 4 && argc != 5) return fprintf(stderr, "usage: %s SCENE.bin BUDGET_BYTES STRIDE [POOL_RECORDS]\n", argv[0]), 2;
   FILE* f = fopen(argv[1], "rb");
   if (!f) return perror(argv[1]), 2;
   const uint64_t budget = strtoull(argv[2], nullptr, 10);
@@ -63,7 +65,15 @@ int main(int argc, char** argv) {
   a.eps_push = P.beam_eps_push, a.eps_ulp = P.beam_eps_ulp;
   const uint32_t nl = pk.dev.n_lights;
   if (nl == 0u || nl > 8u || pk.n_cells == 0u) return fprintf(stderr, "no receiver cells or lights\n"), 1;
-  unsigned long long cells = 0, resolved = 0, emptied = 0, left = 0, slots = 0;
+  const uint32_t pool_records = argc == 5 ? (uint32_t)strtoul(argv[4], nullptr, 10) : 0u;
+  uint16_t* pool = nullptr;
+  uint32_t asked = 0;
+  if (pool_records) {
+    pool = (uint16_t*)aligned_alloc(64, (size_t)pool_records * 2u * RT_CELL_WIDE_SLOTS);
+    if (!pool) return fprintf(stderr, "no memory for the pool\n"), 2;
+    a.wide = pool, a.wide_cap = pool_records, a.wide_count = &asked;
+  }
+  unsigned long long cells = 0, resolved = 0, emptied = 0, left = 0, slots = 0, wide = 0, wide_slots = 0;
   for (uint32_t c = 0; c < pk.n_cells; c += stride, cells++) {
     alignas(16) uint16_t list[8 * RT_PRUNE_LIST_SLOTS];
     for (uint32_t k = 0; k < 8 * RT_PRUNE_LIST_SLOTS; k++) list[k] = (k % RT_PRUNE_LIST_SLOTS) ? (uint16_t)RT_PRUNE_LIST_END : (uint16_t)RT_PRUNE_LIST_OVERFLOW;
@@ -72,6 +82,17 @@ int main(int argc, char** argv) {
     rt_cell_resolve_cell(pk.dev, (const char*)pk.blob.data(), a, c, list, &flag, (c / stride) & 1u ? counts : nullptr);
     for (uint32_t l = 0; l < nl; l++) {
       const uint16_t* w = list + l * RT_PRUNE_LIST_SLOTS;
+      const uint32_t at = rt_cell_wide_index(w);
+      if (at != ~0u) {  // a wide list: its record lies inside the pool and holds 9 .. 32 slots of the scene, then padding
+        if (!pool || at >= pool_records) return fprintf(stderr, "cell %u light %u: record %u outside the pool\n", c, l, at), 1;
+        const uint16_t* rec = pool + (size_t)at * RT_CELL_WIDE_SLOTS;
+        uint32_t n = 0;
+        while (n < RT_CELL_WIDE_SLOTS && rec[n] != RT_PRUNE_LIST_END) n++;
+        for (uint32_t k = 0; k < RT_CELL_WIDE_SLOTS; k++)
+          if (k < n ? rec[k] >= pk.dev.n_slots : rec[k] != RT_PRUNE_LIST_END) return fprintf(stderr, "cell %u light %u: record %u is malformed at %u\n", c, l, at, k), 1;
+        if (n <= RT_PRUNE_LIST_SLOTS) return fprintf(stderr, "cell %u light %u: a record of %u slots\n", c, l, n), 1;
+        wide++, wide_slots += n;
+      }
       if (w[0] == RT_PRUNE_LIST_OVERFLOW) { left++; continue; }
       resolved++, emptied += w[0] == RT_PRUNE_LIST_END;
       for (uint32_t k = 0; k < RT_PRUNE_LIST_SLOTS && w[k] < RT_PRUNE_LIST_OVERFLOW; k++) {
@@ -80,7 +101,10 @@ int main(int argc, char** argv) {
       }
     }
   }
-  printf("cells %llu lists_resolved %llu emptied %llu left_overflowed %llu slots_listed %llu n_cells %u n_slots %u\n", cells, resolved, emptied, left, slots,
+  printf("cells %llu lists_resolved %llu emptied %llu left_overflowed %llu slots_listed %llu n_cells %u n_slots %u", cells, resolved, emptied, left, slots,
          pk.n_cells, pk.dev.n_slots);
+  if (pool_records) printf(" wide_lists %llu wide_slots %llu records_asked %u", wide, wide_slots, asked);
+  printf("\n");
+  free(pool);
   return 0;
 }

@@ -71,7 +71,8 @@ for spec in args or ["c3"]:
           f"simd_eff {st.wave_ray_lanes/max(1, 64*st.wave_ray_passes):.3f}  {rays/ms/1e3:8.1f} Mray/s  {st.rays_shadow/ms/1e6:7.2f} Gshadow/s  checksum {int(fb.to(torch.int64).sum()) & 0xFFFFFFFF:08x}")
     sp = max(1, st.wave_shadow_passes)
     print(f"{'':28s} per wave-pass: nearest nodes {st.wave_nearest_nodes/max(1,st.wave_ray_passes):.1f} tris {st.wave_nearest_tris/max(1,st.wave_ray_passes):.1f} | "
-          f"shadow passes {st.wave_shadow_passes} nodes {st.wave_shadow_nodes/sp:.1f} tris {st.wave_shadow_tris/sp:.1f} exact {st.wave_shadow_tris_exact/sp:.2f}")
+          f"shadow passes {st.wave_shadow_passes} nodes {st.wave_shadow_nodes/sp:.1f} tris {st.wave_shadow_tris/sp:.1f} exact {st.wave_shadow_tris_exact/sp:.2f} "
+          f"(totals: nodes {st.wave_shadow_nodes} tris {st.wave_shadow_tris} exact {st.wave_shadow_tris_exact})")
     if os.environ.get("RT_HIP_LIB", "").endswith("_stats2.so"):
         # make STATS=2 build: nearest_nodes = transmissive occluders accumulated on shadow rays (wave-level executions),
         # nearest_tris = those whose material row differs from the one before in the same (wavefront, light)
@@ -86,6 +87,12 @@ for spec in args or ["c3"]:
         print(f"{'':28s} sets with nothing to test: {n_no} ({l_no/max(1,n_no):.1f} lanes each) | sets traced: {n_tr} "
               f"({l_tr/max(1,n_tr):.1f} lanes each) | candidates by BVH walk: {walked} sets, by per-cell lists: {listed} sets "
               f"({pre/max(1,listed):.1f} slots per union)")
+    elif os.environ.get("RT_HIP_LIB", "").endswith("_prof6.so"):
+        # make PROFILE=6 build: why the sets that still walk do, and what the wide records take off the walks
+        walk, nocell, plain, big, wide, wide16, listed = (st.wave_nearest_nodes, st.wave_nearest_tris, st.wave_shadow_nodes, st.wave_shadow_tris,
+                                                          st.wave_nearest_tris_exact, st.wave_shadow_tris_exact, st.wave_ray_lanes)
+        print(f"{'':28s} sets that walk: {walk} (a lane without a cell {nocell}, else a plain overflowed list {plain}, else a union above 64 slots {big}) | "
+              f"listed sets: {listed}, of them through a wide record {wide} (every record at most 16 slots: {wide16})")
     elif os.environ.get("RT_HIP_LIB", "").endswith("_prof5.so"):
         # make PROFILE=5 build: what regrouping lanes could save in the sets that are traced with a shared candidate list
         sets, lanes, pairs, own, needy, sph, lens = (st.wave_nearest_nodes, st.wave_nearest_tris, st.wave_shadow_nodes, st.wave_shadow_tris,
