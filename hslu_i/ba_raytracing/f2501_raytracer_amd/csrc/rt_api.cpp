@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "rt_cell_resolve.h"
+#include "rt_cell_through.h"
 #include "rt_host.h"
 
 static void trace_point(hipStream_t stream, const char* what, uint32_t a = 0, uint32_t b = 0, uint32_t c = 0);  // RT_TRACE_LAUNCHES
@@ -323,6 +324,7 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
       // scene allows it and a quarter of the free memory holds them
       s->cell_lists_built = false;
       s->cell_wide_built = false;
+      s->cell_marks_bytes = 0;
       B.cell_list_out = nullptr;
       const size_t list_bytes = (size_t)s->n_cells * s->dev.n_lights * 16u;
       size_t free_b = 0, total_b = 0;
@@ -341,8 +343,16 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
       // the flags do.  RT_CELL_PRUNE=0 (read once per process) leaves it out (A/B timing, equality tests).
       static const char* const prune_env = getenv("RT_CELL_PRUNE");
       static const bool prune_off = prune_env && *prune_env == '0';
-      if (s->cell_lists_built && !prune_off) {
-        RtCellPruneArgs a{};
+      // marks of the listed glass panes every shadow ray of a cell crosses (rt_cell_through.h): a fourth stage behind the same key,
+      // after the lists have their final form.  One byte per list, in front of the wide records in their allocation, counted
+      // against the budget before the later stages' temporary memory and pool are sized; RT_CELL_THROUGH=0 (read once per
+      // process) leaves it out.
+      static const char* const through_env = getenv("RT_CELL_THROUGH");
+      static const bool through_off = through_env && *through_env == '0';
+      size_t mark_bytes = s->cell_lists_built && !through_off ? rt_cell_through_bytes(s->n_cells, s->dev.n_lights, s->budget - flag_bytes - list_bytes) : 0;
+      if (mark_bytes && !(hipMemGetInfo(&free_b, &total_b) == hipSuccess && mark_bytes <= (free_b + s->cell_wide.cap) / 4)) mark_bytes = 0;
+      RtCellPruneArgs a{};
+      if (s->cell_lists_built) {
         a.flag_geo = (const float*)s->flag_geo.p;
         a.lists = (uint16_t*)s->cell_lists.p;
         a.flags = (uint16_t*)s->flags.p;
@@ -350,6 +360,8 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
         memcpy(a.cloud_centre, P->cloud_centre, 12);
         a.beam_delta = P->beam_delta, a.beam_eps_o = P->beam_eps_o;
         a.mode = RT_PRUNE_FULL;
+      }
+      if (s->cell_lists_built && !prune_off) {
         e = (hipError_t)rt_launch_cell_prune(s->dev, a, stream);
         if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_cell_prune_kernel launch failed: %s", hipGetErrorString(e));
         trace_point(stream, "rt_cell_prune_kernel: cells, lights", s->n_cells, s->dev.n_lights, 0u);
@@ -359,7 +371,7 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
         static const char* const resolve_env = getenv("RT_CELL_RESOLVE");
         static const bool resolve_off = resolve_env && *resolve_env == '0';
         RtCellResolveArgs r{};
-        const size_t temp_bytes = resolve_off ? 0 : rt_cell_resolve_temp_bytes(s->n_cells, s->budget - flag_bytes - list_bytes, &r.chunk_cells);
+        const size_t temp_bytes = resolve_off ? 0 : rt_cell_resolve_temp_bytes(s->n_cells, s->budget - flag_bytes - list_bytes - mark_bytes, &r.chunk_cells);
         if (temp_bytes && s->resolve_work.ensure(temp_bytes) == RT_OK) {
           r.cell = a;
           r.eps_push = P->beam_eps_push, r.eps_ulp = P->beam_eps_ulp;
@@ -368,12 +380,12 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
           // with the lists; the stage empties it whenever it runs.  RT_CELL_WIDE=0 (read once per process) leaves it out.
           static const char* const wide_env = getenv("RT_CELL_WIDE");
           static const bool wide_off = wide_env && *wide_env == '0';
-          const size_t used = flag_bytes + list_bytes + temp_bytes;
+          const size_t used = flag_bytes + list_bytes + temp_bytes + mark_bytes;
           const size_t wide_bytes = wide_off || used >= s->budget ? 0 : rt_cell_wide_pool_bytes(s->n_cells, s->dev.n_lights, s->budget - used, &r.wide_cap);
-          if (wide_bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && wide_bytes <= (free_b + s->cell_wide.cap) / 4 &&
-              s->cell_wide.ensure(wide_bytes) == RT_OK) {
-            r.wide = (uint16_t*)s->cell_wide.p;
-            r.wide_count = (uint32_t*)((char*)s->cell_wide.p + (size_t)r.wide_cap * 2u * RT_CELL_WIDE_SLOTS);
+          if (wide_bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && mark_bytes + wide_bytes <= (free_b + s->cell_wide.cap) / 4 &&
+              s->cell_wide.ensure(mark_bytes + wide_bytes) == RT_OK) {
+            r.wide = (uint16_t*)((char*)s->cell_wide.p + mark_bytes);  // (the records behind the marks, at 64-byte boundaries)
+            r.wide_count = (uint32_t*)((char*)r.wide + (size_t)r.wide_cap * 2u * RT_CELL_WIDE_SLOTS);
             s->cell_wide_built = true;
           } else {
             r.wide_cap = 0u;
@@ -385,13 +397,25 @@ static int prepare_receiver_flags(rt_scene* s, const rt_params* p, TableUpload& 
           s->resolve_work.release();
         }
       }
+      if (mark_bytes && (s->cell_wide_built || s->cell_wide.ensure(mark_bytes + 64u) == RT_OK)) {  // (no pool: the marks alone)
+        RtCellThroughArgs t{};
+        t.cell = a;
+        t.marks_end = (uint8_t*)s->cell_wide.p + mark_bytes;
+        e = (hipError_t)rt_launch_cell_through(s->dev, t, stream);
+        if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_cell_through_kernel launch failed: %s", hipGetErrorString(e));
+        trace_point(stream, "rt_cell_through_kernel: cells, lights", s->n_cells, s->dev.n_lights, 0u);
+        s->cell_wide_built = true;
+        s->cell_marks_bytes = mark_bytes;
+      }
       if (!s->cell_lists_built) s->resolve_work.release();
       if (!s->cell_wide_built) s->cell_wide.release();
       memcpy(s->flags_key, key, sizeof(key));
     }
     P->recv_flags = (const uint16_t*)s->flags.p;
     if (s->cell_lists_built && !p->tuning.no_cell_lists) P->cell_lists = (const uint4*)s->cell_lists.p;
-    if (P->cell_lists && s->cell_wide_built) P->cell_wide = (const uint32_t*)s->cell_wide.p;
+    // (bit 0 of the pointer: the marks stand in front of the records; the list kernels, its only readers, take it off)
+    if (P->cell_lists && s->cell_wide_built)
+      P->cell_wide = (const uint32_t*)((uintptr_t)((char*)s->cell_wide.p + s->cell_marks_bytes) | (s->cell_marks_bytes ? 1u : 0u));
   }
   if (!P->cell_lists) s->notes |= RT_NOTE_CELL_LISTS_OFF;
   return RT_OK;

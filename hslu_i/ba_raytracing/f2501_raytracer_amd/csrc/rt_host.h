@@ -320,8 +320,9 @@ struct rt_scene {
   DevBuf flag_geo, flags;
   DevBuf cell_lists;     // per (receiver cell, light): 8 x uint16 leaf slots surviving the cell's fat beam (rt_flags_kernel)
   DevBuf resolve_work;   // work list of rt_cell_resolve_kernel (at most 64 MiB, counted with the lists)
-  DevBuf cell_wide;      // pool of wide records (rt_cell_resolve.h: 64 bytes each, then the counter), counted with the lists
+  DevBuf cell_wide;      // marks of certain crossings (rt_cell_through.h), then the pool of wide records (rt_cell_resolve.h: 64 bytes each, then the counter); counted with the lists
   bool cell_wide_built = false;
+  size_t cell_marks_bytes = 0;  // the marks of rt_cell_through.h in front of the records of cell_wide (0: none); counted with the lists
   bool cell_lists_built = false;
   uint32_t n_cells = 0, n_tri_cells = 0;
   float flags_key[8] = {-1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // beam_delta, eps, cloud centre: what the flags were built for

@@ -125,6 +125,8 @@ struct RtDevParams {
   // every other reader sees an overflowed list and walks.  nullptr: no list carries the mark.  The pointer shares its place
   // with cell_list_out, which rt_flags_kernel alone reads and no render launch sets: a field of its own moves the kernel
   // arguments behind RtDevParams, and that alone changed the register allocation of rt_rays_stream_kernel.
+  // Bit 0 of cell_wide (the records are 64-byte aligned): the marks of rt_cell_through.h stand in front of the records, the byte
+  // of (cell c, light l) at ((const uint8_t*)records)[-1 - (c n_lights + l)].  The list kernels take the bit off before they read.
   union {
     uint16_t* cell_list_out;
     const uint32_t* cell_wide;

@@ -27,7 +27,9 @@
 //   * per-cell candidate lists (8 x 16-bit leaf slots per receiver cell and light; 0xFFFF = end, entry 0 == 0xFFFE = more than
 //     8) replace that walk where every lane's cell has a complete one.  In the three list kernels rt_primary_soft*_kernel an
 //     overflowed list {0xFFFE, 0xFFFD, i & 0x7FFF, i >> 15, ...} stands for wide record i of P.cell_wide: 32 slots in 64 bytes,
-//     read through the scalar path; every other kernel sees the marker alone and walks;
+//     read through the scalar path; every other kernel sees the marker alone and walks.  In front of those records stand the
+//     marks of rt_cell_through.h, one byte per (cell, light): an entry every lane in use lists as crossed for certain is not tested
+//     per sample, its occluder is accumulated for the lanes the test would have returned;
 //   * BVH traversal is WAVE-COOPERATIVE: the 64 rays of a wavefront walk the tree together.  The
 //     current node index is wave-uniform, node / triangle / sphere / light records are fetched with
 //     scalar loads (constant address space -> s_load_dwordx4/x16), and the traversal stack is ONE
@@ -678,6 +680,11 @@ struct WaveCtx {
   // transmissive occluders accumulated by shadow_ray, and how many of them had another material row than the one before
   // in the same (wavefront, light): reported by the STATS=2 build in place of n_nodes / n_tris
   uint32_t o_exec, o_miss;
+#if RT_WORK_STATS == 2
+  // ... those of them that are triangles, and those of the triangles that sit on an entry every lane in use lists as crossed
+  // for certain (rt_cell_through.h): reported in place of n_exact / s_exact
+  uint32_t o_tri, o_thru;
+#endif
 #if RT_PROFILE
   unsigned long long t_mark;
   unsigned long long prof[7];  // 0 nearest hit, 1 candidate collection, 2 sample set-up, 3 spheres, 4 triangles, 5 lighting, 6 whole ray
@@ -702,6 +709,7 @@ struct CfgGeneric {
   static constexpr bool FAR_ORIGINS = false; // true: rays may start far outside the scene (CfgRays)
   static constexpr bool OCC_MEMO = false;    // true: shadow_ray keeps the last transmissive occluder's constants (OccMemo)
   static constexpr bool WIDE = false;        // true: a per-cell list may stand for a wide record of P.cell_wide (RT_CELL_WIDE_MARK)
+  static constexpr bool THROUGH = false;     // true: the marks of certain crossings in front of P.cell_wide are read (rt_cell_through.h)
 };
 template <uint32_t N_, int TABLES_>
 struct CfgSoft {
@@ -715,6 +723,8 @@ struct CfgSoft {
   static constexpr bool OCC_MEMO = TABLES_ == CFG_TABLES_LISTS;
   // (the list kernels alone follow the wide records; to every other kernel such a list is an overflowed one, and it walks)
   static constexpr bool WIDE = TABLES_ == CFG_TABLES_LISTS;
+  // (... and the marks of certain crossings, which stand in front of those records)
+  static constexpr bool THROUGH = TABLES_ == CFG_TABLES_LISTS;
 };
 // Rays the CALLER supplies (rt_rays.h).  The receiver tables stand for hit points that lie ON their surface to within the
 // rounding of p = o + t d for a ray that starts in or near the scene (collect_light_candidates, COLLECT_FLAGS: 4e-7 |p|).  A
@@ -1269,7 +1279,10 @@ __device__ __forceinline__ CandList collect_light_candidates(const RtDevScene& s
     // The lanes' own beams then thin it out exactly as they thin out the leaves of a walk.
     for (uint32_t i = 0; i < pre_count; i++) {
       const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)pre_reg, (int)i);
-      if (beam_rejects_all(slot, grp)) continue;
+      // (bit 31: every lane in use lists the slot as crossed for certain, rt_cell_through.h -- a transmissive triangle every sample
+      // ray is accepted by can be neither rejected nor an umbra: it goes on as it is, bit included)
+      const bool certain = C::THROUGH && (slot >> 31) != 0u;
+      if (!certain && beam_rejects_all(slot, grp)) continue;
       if (L.count >= cand_cap) {
         L.count = RT_CAND_OVERFLOW;
         return L;
@@ -1348,6 +1361,33 @@ __device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevPa
   (void)t_tri;
 
   auto test_tri = [&](uint32_t slot, lanemask lanes) {
+    if constexpr (C::THROUGH && LIST) {
+      // the list kernels' sample loop: bit 31 = crossed for certain by every ray of every lane in use (rt_cell_through.h) -- the
+      // literal test would return the lanes it was given, so it is not run and its record is not read; the occluder is
+      // accumulated for exactly those lanes, and the sums are integers: the same bits
+      lanemask h = lanes & ~S.occ;
+      const bool certain = (slot >> 31) != 0u;
+      slot &= 0xFFFFu;
+      if (!certain) {
+        float4 q0 = sload<float4>(sc, sc.off_tri_isect + slot * 48u);
+        float4 q1 = sload<float4>(sc, sc.off_tri_isect + slot * 48u + 16u);
+        float4 q2 = sload<float4>(sc, sc.off_tri_isect + slot * 48u + 32u);
+        float t;
+        h = tri_hit(q0, q1, q2, o, d, h, tmax, t, W.s_exact);
+        h &= wave_ballot(t <= tmax);
+      }
+      if (h) {
+        float4 sh = sload<float4>(sc, sc.off_tri_shade + slot * 16u);
+#if RT_WORK_STATS == 2
+        const uint32_t exec0 = W.o_exec;
+#endif
+        shadow_accumulate_memo<CULL>(sc, S, memo, __float_as_uint(sh.w), mk(sh.x, sh.y, sh.z), d, h, W.o_exec, W.o_miss);
+#if RT_WORK_STATS == 2
+        W.o_tri += W.o_exec - exec0, W.o_thru += certain ? W.o_exec - exec0 : 0u;
+#endif
+      }
+      return;
+    }
     float4 q0 = sload<float4>(sc, sc.off_tri_isect + slot * 48u);
     float4 q1 = sload<float4>(sc, sc.off_tri_isect + slot * 48u + 16u);
     float4 q2 = sload<float4>(sc, sc.off_tri_isect + slot * 48u + 32u);
@@ -1357,7 +1397,13 @@ __device__ __forceinline__ Shadow shadow_ray(const RtDevScene& sc, const RtDevPa
     if (h) {
       float4 sh = sload<float4>(sc, sc.off_tri_shade + slot * 16u);
       if (C::OCC_MEMO) {
+#if RT_WORK_STATS == 2
+        const uint32_t exec0 = W.o_exec;
+#endif
         shadow_accumulate_memo<CULL>(sc, S, memo, __float_as_uint(sh.w), mk(sh.x, sh.y, sh.z), d, h, W.o_exec, W.o_miss);
+#if RT_WORK_STATS == 2
+        W.o_tri += W.o_exec - exec0;
+#endif
       } else {
         Mat m = load_mat_u(sc, __float_as_uint(sh.w));
         V3 n = mk(sh.x, sh.y, sh.z);
@@ -1557,6 +1603,9 @@ struct Wave {
 __device__ __forceinline__ void wave_init(Wave& w) {
   w.ctx.n_nodes = w.ctx.n_tris = w.ctx.s_nodes = w.ctx.s_tris = w.ctx.s_passes = w.ctx.n_exact = w.ctx.s_exact = 0;
   w.ctx.o_exec = w.ctx.o_miss = 0;
+#if RT_WORK_STATS == 2
+  w.ctx.o_tri = w.ctx.o_thru = 0;
+#endif
   w.cnt_kind[0] = w.cnt_kind[1] = w.cnt_kind[2] = 0;
   w.cnt_shadow = w.cnt_pass = w.cnt_lanes = w.cnt_traced = 0;
 #if RT_PROFILE
@@ -1590,7 +1639,7 @@ __device__ __forceinline__ void wave_flush(const Wave& w, const RtDevParams& P, 
 #elif RT_WORK_STATS == 2
     const unsigned long long v[RT_N_COUNTERS] = {w.cnt_kind[0], w.cnt_kind[1], w.cnt_kind[2], w.cnt_shadow, written,
                                                  w.cnt_pass,    w.cnt_lanes,   w.ctx.o_exec,   w.ctx.o_miss, w.ctx.s_nodes,
-                                                 w.ctx.s_tris,  w.ctx.s_passes, w.ctx.n_exact, w.ctx.s_exact, w.cnt_traced};
+                                                 w.ctx.s_tris,  w.ctx.s_passes, w.ctx.o_tri,   w.ctx.o_thru,  w.cnt_traced};
 #else
     const unsigned long long v[RT_N_COUNTERS] = {w.cnt_kind[0], w.cnt_kind[1], w.cnt_kind[2], w.cnt_shadow, written,
                                                  w.cnt_pass,    w.cnt_lanes,   w.ctx.n_nodes,  w.ctx.n_tris, w.ctx.s_nodes,
@@ -2093,12 +2142,41 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
         if (!unusable) {
           have_pre = true;
           const uint32_t lane_id = threadIdx.x & 63u;
+          // Marks of certain crossings (the list kernels; rt_cell_through.h): bit k of a lane's byte = entry k of its list is a
+          // transmissive triangle that every shadow ray of its cell is accepted by.  An entry of the union may skip the literal test
+          // only when EVERY lane in use lists it as marked, so the marks count only in a set whose lanes all have a short list that is
+          // not empty (a lane with an empty list, or with a wide record, lists nothing as marked).  While the union is built, bits 16
+          // and up of an entry's lane of pre_reg count the cells that list it as marked; n_marking counts the cells.  The byte is
+          // read backwards from the records of P.cell_wide, whose bit 0 says whether the table is there.
+          uint32_t mark = 0u, n_marking = 0u;
+          bool marks_on = false;
+          if constexpr (C::THROUGH) {
+            const uintptr_t wp = (uintptr_t)P.cell_wide;
+            marks_on = (wp & 1u) != 0u && !wide_m && !(use_m & wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_END));
+            // (end - 1 - i as (end - 2^32) + ~i: a scalar base and an unsigned 32-bit lane offset, no 64-bit vector arithmetic)
+            typedef const uint8_t __attribute__((address_space(1))) * GP;
+            if (marks_on && use) mark = ((GP)((wp & ~(uintptr_t)1u) - 0x100000000ull))[(uint32_t)~(cidx * sc.n_lights + l)];
+          }
           for (lanemask todo = use_m & ~wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_END) & ~wide_m; todo;) {
             const int fl = __ffsll((long long)todo) - 1;
             const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cidx, fl);
+            uint32_t mbits = 0u;  // (uniform: the marks of this cell's list, shifted down entry by entry)
+            if constexpr (C::THROUGH) mbits = (uint32_t)__builtin_amdgcn_readlane((int)mark, fl), n_marking++;
             auto add_slot = [&](uint32_t slot) {  // (uniform)
               if (slot >= RT_CELL_LIST_OVERFLOW) return;  // end marker
               const lanemask filled = pre_count >= 64u ? ~0ull : ((1ull << pre_count) - 1ull);
+              if constexpr (C::THROUGH) {
+                const uint32_t marked = (mbits & 1u) << 16;
+                mbits >>= 1;
+                const lanemask there = wave_ballot((pre_reg & 0xFFFFu) == slot) & filled;
+                if (there) {  // another cell listed it already: one more marked listing, or none
+                  pre_reg += lane_of(there) ? marked : 0u;
+                  return;
+                }
+                lane_put(pre_reg, pre_count, slot | marked, lane_id);
+                pre_count++;
+                return;
+              }
               if (wave_ballot(pre_reg == slot) & filled) return;  // another cell listed it already
               lane_put(pre_reg, pre_count, slot, lane_id);
               pre_count++;
@@ -2111,6 +2189,10 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
             add_pair(lst.x), add_pair(lst.y), add_pair(lst.z), add_pair(lst.w);
             todo &= ~wave_ballot(cidx == c);
           }
+          // ... bit 31 of an entry: every cell of the set lists it as marked (the count leaves: slots alone below bit 31)
+          if constexpr (C::THROUGH) {
+            if (marks_on) pre_reg = (pre_reg & 0xFFFFu) | ((pre_reg >> 16) == n_marking ? 0x80000000u : 0u);
+          }
           // ... then the cells with a wide record, in a loop of their own (the loop above is the one every kernel has): the
           // record comes through the scalar path (its index is uniform after the readlane), a quarter at a time; padding ends
           // it.  Marked unlikely: the block is laid out behind the light loop, whose code stays where it was.
@@ -2120,7 +2202,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
               const int fl = __ffsll((long long)todo) - 1;
               const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cidx, fl);
               const uint32_t iw = (uint32_t)__builtin_amdgcn_readlane((int)lst.y, fl);
-              const uint4* rec = (const uint4*)(P.cell_wide + (size_t)((iw & 0x7FFFu) | ((iw >> 1) & 0x3FFF8000u)) * RT_CELL_WIDE_DWORDS);
+              const uint4* rec = (const uint4*)((const uint32_t*)((uintptr_t)P.cell_wide & ~(uintptr_t)1u) + (size_t)((iw & 0x7FFFu) | ((iw >> 1) & 0x3FFF8000u)) * RT_CELL_WIDE_DWORDS);
               auto add_slot = [&](uint32_t slot) {  // (as above)
                 if (slot >= RT_CELL_LIST_OVERFLOW) return;
                 const lanemask filled = pre_count >= 64u ? ~0ull : ((1ull << pre_count) - 1ull);
@@ -2167,7 +2249,7 @@ __device__ __forceinline__ RayOut process_ray(const RtDevScene& sc, const RtDevP
         const lanemask plain_m = use_m & wave_ballot((lst.x & 0xFFFFu) == RT_CELL_LIST_OVERFLOW && !is_wide);
         const lanemask wide_m = use_m & wave_ballot(is_wide);
         bool longer = false;  // this lane's record holds more than 16 slots
-        if (use && is_wide) longer = (P.cell_wide[(size_t)((lst.y & 0x7FFFu) | ((lst.y >> 1) & 0x3FFF8000u)) * RT_CELL_WIDE_DWORDS + 8u] & 0xFFFFu) != RT_CELL_LIST_END;
+        if (use && is_wide) longer = (((const uint32_t*)((uintptr_t)P.cell_wide & ~(uintptr_t)1u))[(size_t)((lst.y & 0x7FFFu) | ((lst.y >> 1) & 0x3FFF8000u)) * RT_CELL_WIDE_DWORDS + 8u] & 0xFFFFu) != RT_CELL_LIST_END;
         W.prof[0] += have_pre ? 0u : 1u;                                    // sets that walk
         W.prof[1] += (!have_pre && nocell_m) ? 1u : 0u;                     // ... with a lane that has no cell
         W.prof[2] += (!have_pre && !nocell_m && plain_m) ? 1u : 0u;         // ... else with a lane on a plain overflowed list

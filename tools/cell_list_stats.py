@@ -8,7 +8,9 @@ lists (more than 8 candidates: left alone by that kernel, the render walks the t
 rt_cell_resolve_kernel with survivor counts and reports the overflowed lists before and after it, a histogram of the
 survivors per formerly overflowed list (0, 1-4, 5-8, 9-16, more; and of those above 8: 9-16, 17-24, 25-32, 33-64, more) and the
 stage's device time (timed in a run of its own without the counts, as the render launches it: once without and once with the
-pool of wide records, whose records it then counts).  A probe compiled on the fly links against the built librt_hip.so, so the
+pool of wide records, whose records it then counts).  Last it runs rt_cell_through_kernel on the final lists (the run with the
+pool) and reports, per light: the listed transmissive entries, the entries marked as crossed for certain, the lists whose every
+entry is marked, and the stage's device time.  A probe compiled on the fly links against the built librt_hip.so, so the
 kernels counted here are the ones that ship.  Prints one JSON line.
 
     python tools/cell_list_stats.py [--scene semesterbild] [--model text] [--budget BYTES]
@@ -35,7 +37,7 @@ CSRC = os.path.join(ROOT, "hslu_i", "ba_raytracing", "f2501_raytracer_amd", "csr
 PROBE = r'''
 #include <hip/hip_runtime_api.h>
 #include <cstring>
-#include "rt_cell_resolve.h"
+#include "rt_cell_through.h"
 #include "rt_scene_pack.h"
 static RtPackedScene g;
 #define TRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return 1000 + (int)e_; } while (0)
@@ -51,7 +53,8 @@ int probe_pack(const rt_scene_desc* d, uint64_t budget, uint32_t* out) {
 // ms = {resolve with the pool of wide records, prune, resolve as the render launches it without a pool, resolve with counts};
 // wide = {records the pool has room for, records asked for, pool bytes}, wide_lists: the lists after the run with the pool
 int probe_run(const float* cloud, uint64_t n_floats, const float* f, float eps, uint64_t budget, uint16_t* raw_lists, uint16_t* raw_flags, uint16_t* out_lists,
-              uint16_t* out_flags, uint16_t* res_lists, uint16_t* res_flags, uint8_t* counts, float* ms, uint64_t* wide, uint16_t* wide_lists) {
+              uint16_t* out_flags, uint16_t* res_lists, uint16_t* res_flags, uint8_t* counts, float* ms, uint64_t* wide, uint16_t* wide_lists, uint8_t* marks,
+              uint32_t* tri_id, float* through_ms) {
   if (!g.n_cells || g.dev.n_lights > 8u || g.dev.n_slots > 65533u) return -100;
   std::vector<float> scaled;
   float ball[4];
@@ -143,6 +146,25 @@ int probe_run(const float* cloud, uint64_t n_floats, const float* f, float eps, 
     TRY(hipMemcpy(wide_lists, lists, list_bytes, hipMemcpyDeviceToHost));
     wide[0] = cap, wide[1] = asked, wide[2] = pool_bytes;
     TRY(hipFree(pool));
+  } else {
+    TRY(hipMemcpy(wide_lists, lists, list_bytes, hipMemcpyDeviceToHost));
+  }
+  // the fourth stage on the final lists: marks[n_cells * n_lights], backwards from the end (rt_cell_through.h)
+  {
+    const size_t n_marks = (size_t)g.n_cells * g.dev.n_lights;
+    uint8_t* dmarks = nullptr;
+    TRY(hipMalloc((void**)&dmarks, n_marks + 64));
+    RtCellThroughArgs t{};
+    t.cell = a;
+    t.marks_end = dmarks + n_marks;
+    TRY(hipEventRecord(e[1], nullptr));
+    TRY((hipError_t)rt_launch_cell_through(sc, t, nullptr));
+    TRY(hipEventRecord(e[2], nullptr));
+    TRY(hipDeviceSynchronize());
+    TRY(hipEventElapsedTime(through_ms, e[1], e[2]));
+    TRY(hipMemcpy(marks, dmarks, n_marks, hipMemcpyDeviceToHost));
+    TRY(hipFree(dmarks));
+    memcpy(tri_id, g.blob.data() + g.dev.off_tri_id, 4u * (size_t)g.dev.n_slots);
   }
   TRY(hipFree(r.work));
   TRY(hipFree(dcounts));
@@ -180,6 +202,27 @@ def resolve_report(over, new_l, res_l, new_f, res_f, counts, nl):
             "resolved_lists_that_disagree_with_their_count": int(((counts <= 8) & over & still).sum() + ((counts > 8) & over & ~still).sum())}
 
 
+def through_of(lists, marks, transmissive, ms):
+    """rt_cell_through_kernel on the final lists: per light, the listed transmissive entries, the marked ones, the short lists
+    with an entry, and those of them whose every entry is marked (the sets that could go without so and tmax)"""
+    out = {"stage_ms": ms, "table_bytes": int(marks.size)}
+    rows = {k: [] for k in ("short_lists_with_an_entry", "listed_entries", "listed_transmissive_entries", "marked_entries", "marked_share_of_transmissive",
+                            "lists_whose_every_entry_is_marked")}
+    shifts = np.arange(8, dtype=np.uint8)[None, :]
+    for l in range(lists.shape[1]):  # (light by light: the index arrays of a whole scene are large)
+        w = lists[:, l, :]
+        entry = (w < 0xFFFE) & (w[:, :1] < 0xFFFE)
+        trans = entry & transmissive[np.minimum(w, len(transmissive) - 1)]
+        bits = ((marks[:, l, None] >> shifts) & 1).astype(bool)
+        assert not (bits & ~trans).any(), "only listed transmissive entries are marked"
+        n_entry, n_bits = entry.sum(1), bits.sum(1)
+        for k, v in zip(rows, (int((n_entry > 0).sum()), int(n_entry.sum()), int(trans.sum()), int(n_bits.sum()), float(n_bits.sum() / max(1, trans.sum())),
+                               int(((n_entry > 0) & (n_bits == n_entry)).sum()))):
+            rows[k].append(v)
+    out.update({k + "_per_light": v for k, v in rows.items()})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", default="semesterbild", choices=["semesterbild", "test_scene"])
@@ -210,9 +253,11 @@ def main():
     counts = np.zeros((n_cells, nl), np.uint8)
     ms = np.zeros(4, np.float32)
     wide, wide_l = np.zeros(3, np.uint64), np.zeros((n_cells, nl, 8), np.uint16)
+    marks, tri_id, through_ms = np.zeros(n_cells * nl, np.uint8), np.zeros(ns, np.uint32), np.zeros(1, np.float32)
     rc = probe.probe_run(ptr(cs), C.c_uint64(cs.size), ptr(f), C.c_float(cfg.eps_distance), C.c_uint64(args.budget), ptr(raw_l), ptr(raw_f), ptr(new_l), ptr(new_f),
-                         ptr(res_l), ptr(res_f), ptr(counts), ptr(ms), ptr(wide), ptr(wide_l))
+                         ptr(res_l), ptr(res_f), ptr(counts), ptr(ms), ptr(wide), ptr(wide_l), ptr(marks), ptr(tri_id), ptr(through_ms))
     assert rc == 0, f"probe_run: {rc}"
+    through_report = through_of(wide_l, marks[::-1].reshape(n_cells, nl), (tri_id & 0x40000000) != 0, float(through_ms[0]))
     marked = (wide_l[:, :, 0] == 0xFFFE) & (wide_l[:, :, 1] == 0xFFFD)
     wide_report = {"pool_records": int(wide[0]), "records_asked_for": int(wide[1]), "pool_bytes": int(wide[2]), "wide_lists": int(marked.sum()),
                    "wide_lists_per_light": [int(v) for v in marked.sum(0)], "plain_overflowed_lists_left": int(((wide_l[:, :, 0] == 0xFFFE) & ~marked).sum()),
@@ -238,7 +283,7 @@ def main():
            "slots_removed_fraction": (before["listed_slots"] - after["listed_slots"]) / max(1, before["listed_slots"]),
            "prune_kernel_ms": float(ms[1]),
            "resolve": resolve_report(over, new_l, res_l, new_f, res_f, counts, nl), "resolve_stage_ms": float(ms[2]), "resolve_stage_with_counts_ms": float(ms[3]),
-           "wide": wide_report,
+           "wide": wide_report, "through": through_report,
            "build_id": _lib.load().rt_build_id().decode()}
     print(json.dumps(res))
 
