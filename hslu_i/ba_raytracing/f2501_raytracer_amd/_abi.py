@@ -146,6 +146,20 @@ class rt_ray_hit_lists(C.Structure):
                 ("id", C.c_void_p), ("t", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("material", C.c_void_p)]
 
 
+RT_MAX_OCCLUSION_SAMPLES = 256
+RT_OCCLUSION_PASS_TRANSMISSIVE = 0x1
+
+
+class rt_occlusion_batch(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("n_points", C.c_uint32), ("point", C.c_void_p), ("normal", C.c_void_p), ("n_samples", C.c_uint32),
+                ("n_table", C.c_uint32), ("table", C.c_void_p), ("first", C.c_void_p), ("bias", C.c_float), ("max_distance", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+class rt_occlusion_out(C.Structure):
+    _fields_ = [("bits", C.c_void_p), ("clear", C.c_void_p), ("visibility", C.c_void_p), ("bent_normal", C.c_void_p)]
+
+
 class rt_ray_radiance(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("valid", C.c_void_p), ("id", C.c_void_p), ("t", C.c_void_p), ("argb", C.c_void_p)]
 

@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_params, rt_point_batch, rt_point_hits, rt_ray_batch, rt_ray_hit_lists, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
+from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_occlusion_batch, rt_occlusion_out, rt_params, rt_point_batch, rt_point_hits, rt_ray_batch, rt_ray_hit_lists, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
                    rt_bvh_quality, rt_pose_desc, rt_rebuild_desc, rt_rebuild_info, rt_rebuild_report, rt_skin_desc, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_adaptive_info, rt_view_camera, rt_view_desc, rt_view_info, rt_view_lens, rt_view_refine)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -19,6 +19,7 @@ EXPORTS = (
     "rt_cast_rays", "rt_cast_rays_device", "rt_any_intersection", "rt_any_intersection_device",
     "rt_closest_points", "rt_closest_points_device", "rt_closest_points_model",
     "rt_list_intersections", "rt_list_intersections_device", "rt_list_intersections_model",
+    "rt_ambient_occlusion", "rt_ambient_occlusion_device", "rt_ambient_occlusion_model", "rt_occlusion_rays_model",
     "rt_trace_rays", "rt_trace_rays_device", "rt_scene_update", "rt_scene_update_device",
     "rt_ray_order_create", "rt_ray_order_destroy", "rt_ray_order_build", "rt_ray_order_build_device", "rt_ray_order_set", "rt_ray_order_read",
     "rt_trace_rays_ordered", "rt_trace_rays_ordered_device",
@@ -107,6 +108,14 @@ def load():
     lib.rt_list_intersections_device.argtypes = [C.c_void_p, C.POINTER(rt_ray_batch), C.POINTER(rt_ray_hit_lists), C.c_void_p]
     lib.rt_list_intersections_model.restype = C.c_int
     lib.rt_list_intersections_model.argtypes = [C.POINTER(rt_scene_desc), C.POINTER(rt_ray_batch), C.POINTER(rt_ray_hit_lists)]
+    lib.rt_ambient_occlusion.restype = C.c_int
+    lib.rt_ambient_occlusion.argtypes = [C.c_void_p, C.POINTER(rt_occlusion_batch), C.POINTER(rt_occlusion_out)]
+    lib.rt_ambient_occlusion_device.restype = C.c_int
+    lib.rt_ambient_occlusion_device.argtypes = [C.c_void_p, C.POINTER(rt_occlusion_batch), C.POINTER(rt_occlusion_out), C.c_void_p]
+    lib.rt_ambient_occlusion_model.restype = C.c_int
+    lib.rt_ambient_occlusion_model.argtypes = [C.POINTER(rt_scene_desc), C.POINTER(rt_occlusion_batch), C.POINTER(rt_occlusion_out)]
+    lib.rt_occlusion_rays_model.restype = C.c_int
+    lib.rt_occlusion_rays_model.argtypes = [C.POINTER(rt_occlusion_batch), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rt_closest_points.restype = C.c_int
     lib.rt_closest_points.argtypes = [C.c_void_p, C.POINTER(rt_point_batch), C.POINTER(rt_point_hits)]
     lib.rt_closest_points_device.restype = C.c_int

@@ -13,6 +13,7 @@
 #include "rt_closest.h"
 #include "rt_lbvh.h"
 #include "rt_multihit.h"
+#include "rt_occlusion.h"
 #include "rt_refit.h"
 #include "rt_ploc.h"
 #include "rt_sah.h"
@@ -475,6 +476,11 @@ void rt_closest_packed(const RtPackedScene& pk, const RtClosestArgs& a) {
 void rt_multihit_packed(const RtPackedScene& pk, const RtMultiHitArgs& a) {
   const RtMhBlob S = {pk.dev, (const char*)pk.blob.data()};
   for (uint32_t i = 0; i < a.n; i++) rt_mh_query<RT_MH_KMAX>(S, RtMhArgsRef{a}, i, true);
+}
+
+void rt_occlusion_packed(const RtPackedScene& pk, const RtOcclusionArgs& a) {
+  const RtMhBlob S = {pk.dev, (const char*)pk.blob.data()};
+  for (uint32_t i = 0; i < a.n; i++) rt_occ_query_host(S, RtOccArgsRef{a}, i);
 }
 
 int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {

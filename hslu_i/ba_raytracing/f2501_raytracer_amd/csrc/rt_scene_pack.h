@@ -112,6 +112,13 @@ void rt_closest_packed(const RtPackedScene& pk, const RtClosestArgs& a);
 struct RtMultiHitArgs;
 void rt_multihit_packed(const RtPackedScene& pk, const RtMultiHitArgs& a);
 
+// ---- ambient-occlusion queries (rt_ambient_occlusion*; the arithmetic and the walk: rt_occlusion.h) ---------------------------
+// The KERNEL's walk -- spheres, threaded walk with rt_mh_box_enter at the limit max_distance, ended at the first hit -- over the
+// packed blob for a batch of HOST arrays, one sample after the other: the same functions the kernels are made of, so the
+// pruning is checked on the CPU against the linear scan of rt_ambient_occlusion_model.
+struct RtOcclusionArgs;
+void rt_occlusion_packed(const RtPackedScene& pk, const RtOcclusionArgs& a);
+
 // ---- parameter tables of a frame -----------------------------------------------------------------------------------------
 // AA samples: the distinct offsets in first-occurrence order (compared as values; `dedup` off: every sample is distinct),
 // their multiplicities and the sample -> thread map, as the device image [2U offsets (float bits) | U | n].  Returns U.

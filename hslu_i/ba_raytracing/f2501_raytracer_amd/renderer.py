@@ -79,6 +79,16 @@ class RayHitLists(NamedTuple):
     total: Any
 
 
+class Occlusion(NamedTuple):
+    """Hemisphere visibility per surface point (`rt_occlusion_out`): `clear` (n,) samples that are not occluded, `visibility` (n,)
+    = clear / samples, `bent_normal` (n, 3) the normalised mean direction of the clear samples (0 where none is clear), and
+    `bits` (n, ceil(samples / 32)) with bit s % 32 of word s / 32 set where sample s is occluded, or None when not asked for."""
+    clear: Any
+    visibility: Any
+    bent_normal: Any
+    bits: Any
+
+
 class IntersectionTest(NamedTuple):
     """`IntersectionTest` (raytracer.rs:17-22) per segment.  color_filter is unspecified where completely_occluded."""
     has_intersection: Any
@@ -558,6 +568,59 @@ class DeviceScene:
             return RayHitLists(None, None, None, None, None, None, cnt["total"])
         return RayHitLists(cnt["count"], lists["id"].reshape(n, k), lists["t"].reshape(n, k), lists["point"].reshape(n, k, 3),
                            lists["normal"].reshape(n, k, 3), lists["material"].reshape(n, k), cnt["total"] if total else None)
+
+    def ambient_occlusion(self, points, normals, samples: int = 16, table=None, first=None, bias: float = 1e-4, max_distance=float("inf"),
+                          pass_transmissive: bool = False, bits: bool = False) -> "Occlusion":
+        """`rt_ambient_occlusion` for a batch of surface points: of `samples` (1 .. 256) directions of the hemisphere above each
+        point -- rows first[i], first[i] + 1, ... (modulo its length) of `table`, (m, 3) directions in the local frame with z
+        along the normal; None: sampling.hemisphere_samples(samples) -- how many reach max_distance without a hit, from an origin
+        moved `bias` along the normal.  pass_transmissive: transmissive objects do not occlude.  bits=True also returns the
+        occluded samples as bit words.  normals may have any length; the point and normal planes of cast_rays and
+        closest_points plug in directly.  Same input kinds as cast_rays: numpy arrays (the host entry point; numpy results) or
+        torch tensors on this scene's device (the _device entry point on torch.cuda.current_stream(); tensor results, no
+        synchronisation; a numpy table is uploaded on that stream; `first` is an (n,) int32 tensor there, uint32 in numpy)."""
+        from . import sampling
+
+        torch_in, n, p, nrm, _ = self._batch(points, normals, None)
+        s = int(samples)
+        if not 1 <= s <= _abi.RT_MAX_OCCLUSION_SAMPLES:
+            raise ValueError(f"samples must be 1 .. {_abi.RT_MAX_OCCLUSION_SAMPLES}, got {s}")
+        if table is None:
+            table = sampling.hemisphere_samples(s)
+        if torch_in:
+            import torch
+
+            if isinstance(table, np.ndarray):
+                table = torch.from_numpy(np.ascontiguousarray(table, np.float32)).to(p.device)
+            if not (isinstance(table, torch.Tensor) and table.dtype == torch.float32 and table.device == p.device):
+                raise ValueError("table must be a float32 array or a float32 tensor on the points' device")
+            table = table.contiguous()
+            if first is not None:
+                if not (isinstance(first, torch.Tensor) and first.dtype == torch.int32 and first.device == p.device and tuple(first.shape) == (n,)):
+                    raise ValueError(f"first must be an int32 tensor of shape ({n},) on the points' device")
+                first = first.contiguous()
+        else:
+            table = np.ascontiguousarray(table, np.float32)
+            if first is not None:
+                first = np.ascontiguousarray(first, np.uint32)
+                if first.shape != (n,):
+                    raise ValueError(f"first must be ({n},), got {first.shape}")
+        if len(table.shape) != 2 or table.shape[1] != 3 or table.shape[0] < 1:
+            raise ValueError(f"table must be (m, 3) with m >= 1, got {tuple(table.shape)}")
+        u32 = "int32" if torch_in else "uint32"  # (torch has no uint32 arithmetic)
+        words = (s + 31) // 32
+        out, ptr = self._planes(dict, p, n, ("clear", u32, 1), ("visibility", "float32", 1), ("bent_normal", "float32", 3))
+        word_plane, _ = self._planes(dict, p, n * words, ("bits", u32, 1))
+        b = _abi.rt_occlusion_batch(_abi.RT_ABI_VERSION, int(n), ptr(p), ptr(nrm), s, int(table.shape[0]), ptr(table),
+                                    ptr(first) if first is not None else None, float(bias), float(max_distance),
+                                    _abi.RT_OCCLUSION_PASS_TRANSMISSIVE if pass_transmissive else 0)
+        o = _abi.rt_occlusion_out(ptr(word_plane["bits"]) if bits else None, ptr(out["clear"]), ptr(out["visibility"]), ptr(out["bent_normal"]))
+        lib = _lib.load()
+        if torch_in:
+            _lib.check(lib.rt_ambient_occlusion_device(self.handle, C.byref(b), C.byref(o), self._stream_of(p)))
+        else:
+            _lib.check(lib.rt_ambient_occlusion(self.handle, C.byref(b), C.byref(o)))
+        return Occlusion(out["clear"], out["visibility"], out["bent_normal"], word_plane["bits"].reshape(n, words) if bits else None)
 
     def ray_order(self, origins, directions, origin_bits: int = 0) -> RayOrder:
         """A RayOrder for these rays on this scene's device, sorted on the device by the Morton code of origin and

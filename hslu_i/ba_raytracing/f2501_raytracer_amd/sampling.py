@@ -136,3 +136,19 @@ def cloud_sets(cfg: RenderConfig) -> np.ndarray:
             pts = np.concatenate([pts, pad], axis=0)
         sets[s] = pts.astype(np.float32)
     return sets
+
+
+def hemisphere_samples(n: int) -> np.ndarray:
+    """The default direction table of `DeviceScene.ambient_occlusion`: n cosine-weighted directions of the hemisphere z >= 0 in
+    the local frame (z along the normal), (n, 3) float32.  A Fibonacci (golden-angle) spiral over the unit disc, lifted to the
+    hemisphere (Malley's method): point k lies at radius sqrt((k + 0.5) / n) and angle k * pi (3 - sqrt(5)), and z =
+    sqrt(1 - r^2).  Deterministic, computed in float64 and cast; not part of the bit-exact definition of the query, which
+    takes whatever table it is given."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"n must be at least 1, got {n}")
+    k = np.arange(n, dtype=np.float64)
+    r2 = (k + 0.5) / n
+    phi = k * (math.pi * (3.0 - math.sqrt(5.0)))
+    r = np.sqrt(r2)
+    return np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r2)], axis=1).astype(np.float32)

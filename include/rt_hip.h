@@ -32,6 +32,9 @@
  *   rt_list_intersections[_device] <- none (has_any_intersection visits every hit at t <= max_distance; this returns them):
  *                                   the first K hits per ray in order and their number; rt_list_intersections_model is
  *                                   its specification
+ *   rt_ambient_occlusion[_device] <- none (the reference shades with point lights only): which of S hemisphere directions
+ *                                   above a surface point are blocked, their number and the bent normal;
+ *                                   rt_ambient_occlusion_model is its specification
  *   rt_closest_points[_device]   <- none (the reference has no point query): the nearest surface point per query
  *                                   point, Embree's rtcPointQuery; rt_closest_points_model is its specification
  *   rt_trace_rays     <- RaytracerRenderer::single_raytrace, src/renderer/raytracer_renderer.rs:147-264 (the colour of
@@ -580,6 +583,80 @@ int rt_list_intersections_device(rt_scene* scene, const rt_ray_batch* batch, con
 /* The specification, without a device or a tree: a LINEAR scan of `desc` with the same arithmetic.  HOST arrays; no HIP call.
  * The two calls above return the same bits. */
 int rt_list_intersections_model(const rt_scene_desc* desc, const rt_ray_batch* batch, const rt_ray_hit_lists* lists);
+
+/* ---- ambient-occlusion queries: hemisphere visibility per surface point ----------------------------------------------------------
+ *
+ * How open the surface is at a point: ambient occlusion, sky visibility and bent normals, for baking per vertex or texel,
+ * contact shading, accessibility of a point on a part (Embree's rtcOccluded over a hemisphere; Open3D's and trimesh's
+ * occlusion bakes).  The points and normals that rt_cast_rays* and rt_closest_points* return plug in directly.  The rays are
+ * made on the device, each stops at its first hit, a point's samples are reduced inside a wavefront and one record per point
+ * is written.  The call works on whatever the handle holds after rt_scene_update*, rt_pose_apply*, rt_skin_apply* and
+ * rt_scene_rebuild*.
+ *
+ * Definition (csrc/rt_occlusion.h holds the formulas; every float result is one correctly rounded operation or an fmaf).
+ * Per point: n = normalize(normal); the point is DEAD if a coordinate of it is non-finite or n has a NaN.  The frame is the
+ * branchless orthonormal basis of Duff et al. 2017 (tx, ty, n); the origin is fma(n, bias, point).  Sample s takes table row
+ * ((uint64)first[i] + s) % n_table (first NULL: 0), a direction l in the LOCAL frame (z along the normal, any length); the
+ * world direction is l.x tx + l.y ty + l.z n and is normalised as every ray's is (u).  A sample is OCCLUDED if some object has
+ * a hit -- what rt_list_intersections defines, at most one per object, no back-face culling -- with t <= max_distance (a NaN
+ * or negative max_distance admits nothing; +inf is allowed).  With RT_OCCLUSION_PASS_TRANSMISSIVE objects whose material is
+ * transmissive (TransmissionProperties::mask) do not count.  A sample whose ray is dead (its row normalises to NaN, the
+ * origin overflowed) counts as occluded: a ray that cannot be cast shows no open sky.
+ *
+ * Output per point, for n_samples = S: bits[(S + 31) / 32] -- bit s % 32 of word s / 32 is set when sample s is occluded, the
+ * unused high bits are 0; clear = the samples that are not occluded; visibility = clear / S; bent_normal = the normalised sum
+ * of the unit directions u of the clear samples, summed in 2^-20 fixed point (int32, so the sum has no order), or (0, 0, 0)
+ * when the three sums are 0.  A dead point: bits all set, clear 0, visibility 0, bent_normal 0.
+ *
+ * The result is a function of the scene description and the batch alone: it does not depend on the tree, on slot order, on
+ * split-clipped duplicate references, on how samples map to lanes or on the order a walk meets hits in.
+ *
+ * Validation (RT_ERR_INVALID_ARG + rt_last_error, before any HIP call; nothing is written): a NULL scene, description, batch
+ * or out; a wrong abi_version; NULL point, normal or table with n_points > 0; n_samples outside 1 ..
+ * RT_MAX_OCCLUSION_SAMPLES; n_table == 0; a non-finite bias; a flag bit other than RT_OCCLUSION_PASS_TRANSMISSIVE; every
+ * output NULL.  n_points == 0 is a valid no-op.
+ *
+ * Streams and concurrency: as the ray queries above.
+ *
+ * Not offered: per-sample weights, transmittance-weighted occlusion, culling, distance falloff, a max_distance per point,
+ * more than RT_MAX_OCCLUSION_SAMPLES samples in a call (the caller pages through a longer table with `first`). */
+#define RT_MAX_OCCLUSION_SAMPLES 256u
+#define RT_OCCLUSION_PASS_TRANSMISSIVE 0x1u /* rt_occlusion_batch.flags: transmissive objects do not occlude */
+
+typedef struct rt_occlusion_batch {
+  uint32_t abi_version;   /* RT_ABI_VERSION */
+  uint32_t n_points;      /* 0 is a valid no-op */
+  const float* point;     /* [n_points][3] */
+  const float* normal;    /* [n_points][3], any length */
+  uint32_t n_samples;     /* S: 1 .. RT_MAX_OCCLUSION_SAMPLES samples per point */
+  uint32_t n_table;       /* rows of `table`, >= 1 */
+  const float* table;     /* [n_table][3] directions in the local frame (z along the normal), any length */
+  const uint32_t* first;  /* [n_points] table row of sample 0, any value (taken modulo n_table); NULL = 0 */
+  float bias;             /* the origin is moved this far along the normal; finite */
+  float max_distance;     /* hits at t <= max_distance occlude; +inf allowed */
+  uint32_t flags;         /* RT_OCCLUSION_PASS_TRANSMISSIVE or 0 */
+} rt_occlusion_batch;
+
+/* output of rt_ambient_occlusion*.  Every member nullable, at least one non-NULL: a NULL plane is not written. */
+typedef struct rt_occlusion_out {
+  uint32_t* bits;      /* [n_points][(S + 31) / 32] occluded samples */
+  uint32_t* clear;     /* [n_points] samples that are not occluded, 0 .. S */
+  float* visibility;   /* [n_points] clear / S */
+  float* bent_normal;  /* [n_points][3] unit, or 0 */
+} rt_occlusion_out;
+
+/* HOST arrays: staged through device memory allocated for the call; returns when the results are in host memory. */
+int rt_ambient_occlusion(rt_scene* scene, const rt_occlusion_batch* batch, const rt_occlusion_out* out);
+/* DEVICE arrays on the scene's device, the table included: ONE launch enqueued on `hip_stream` (NULL = default stream);
+ * allocates nothing, needs no workspace, returns once the work is enqueued. */
+int rt_ambient_occlusion_device(rt_scene* scene, const rt_occlusion_batch* batch, const rt_occlusion_out* out, void* hip_stream);
+/* The specification, without a device or a tree: a LINEAR scan of `desc` with the same arithmetic.  HOST arrays; no HIP call.
+ * The two calls above return the same bits. */
+int rt_ambient_occlusion_model(const rt_scene_desc* desc, const rt_occlusion_batch* batch, const rt_occlusion_out* out);
+/* The rays of the definition (no device needed), every output nullable: origin [n_points][3]; direction [n_points][S][3], the
+ * world direction of each sample BEFORE normalisation (a ray batch of these origins and directions is normalised exactly as
+ * the query normalises them); alive [n_points], 0 for a dead point. */
+int rt_occlusion_rays_model(const rt_occlusion_batch* batch, float* origin, float* direction, uint8_t* alive);
 
 /* ---- radiance queries: Whitted shading of caller-supplied rays -------------------------------------------------------------
  *
