@@ -8,4 +8,4 @@ from .f32math import Isometry3, Rotor3, Similarity3, Vec3  # noqa: F401
 from .scene import (BoundedPlane, ColorType, FlatScene, Material, PointLight, Scene, SphereData,  # noqa: F401
                     TransmissionProperties, TriangleData, maximize_value)
 from .camera import PinholeCamera, reference_rays  # noqa: F401
-from .renderer import AdaptiveRadiance, ClosestPoints, DevicePose, DeviceScene, DeviceSkin, DeviceView, IntersectionTest, Occlusion, Radiance, RayHitLists, RayHits, Refine  # noqa: F401
+from .renderer import AdaptiveRadiance, ClosestPoints, Containment, SignedDistance, DevicePose, DeviceScene, DeviceSkin, DeviceView, IntersectionTest, Occlusion, Radiance, RayHitLists, RayHits, Refine  # noqa: F401

@@ -160,6 +160,23 @@ class rt_occlusion_out(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("clear", C.c_void_p), ("visibility", C.c_void_p), ("bent_normal", C.c_void_p)]
 
 
+RT_MAX_SOLID_DIRECTIONS = 8
+RT_SOLID_RULE_PARITY, RT_SOLID_RULE_WINDING = 0, 1
+
+
+class rt_solid_batch(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("n_points", C.c_uint32), ("point", C.c_void_p), ("max_distance", C.c_void_p),
+                ("n_directions", C.c_uint32), ("rule", C.c_uint32), ("directions", C.c_void_p)]
+
+
+class rt_solid_out(C.Structure):
+    _fields_ = [("inside", C.c_void_p), ("votes", C.c_void_p), ("crossings", C.c_void_p), ("winding", C.c_void_p)]
+
+
+class rt_signed_distance_out(C.Structure):
+    _fields_ = [("signed_distance", C.c_void_p), ("solid", rt_solid_out), ("closest", rt_point_hits)]
+
+
 class rt_ray_radiance(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("valid", C.c_void_p), ("id", C.c_void_p), ("t", C.c_void_p), ("argb", C.c_void_p)]
 

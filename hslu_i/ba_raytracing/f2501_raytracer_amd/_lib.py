@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_occlusion_batch, rt_occlusion_out, rt_params, rt_point_batch, rt_point_hits, rt_ray_batch, rt_ray_hit_lists, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta,
+from ._abi import (rt_aux, rt_bvh_info, rt_gather_info, rt_occlusion_batch, rt_occlusion_out, rt_params, rt_point_batch, rt_point_hits, rt_ray_batch, rt_ray_hit_lists, rt_ray_hits, rt_ray_occlusion, rt_ray_order_desc, rt_ray_order_info, rt_ray_radiance, rt_scene_delta, rt_signed_distance_out, rt_solid_batch, rt_solid_out,
                    rt_bvh_quality, rt_pose_desc, rt_rebuild_desc, rt_rebuild_info, rt_rebuild_report, rt_skin_desc, rt_scene_desc, rt_scene_info, rt_stats, rt_update_info, rt_view_adaptive_info, rt_view_camera, rt_view_desc, rt_view_info, rt_view_lens, rt_view_refine)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,6 +20,8 @@ EXPORTS = (
     "rt_closest_points", "rt_closest_points_device", "rt_closest_points_model",
     "rt_list_intersections", "rt_list_intersections_device", "rt_list_intersections_model",
     "rt_ambient_occlusion", "rt_ambient_occlusion_device", "rt_ambient_occlusion_model", "rt_occlusion_rays_model",
+    "rt_contains_points", "rt_contains_points_device", "rt_contains_points_model",
+    "rt_signed_distance", "rt_signed_distance_device", "rt_signed_distance_model",
     "rt_trace_rays", "rt_trace_rays_device", "rt_scene_update", "rt_scene_update_device",
     "rt_ray_order_create", "rt_ray_order_destroy", "rt_ray_order_build", "rt_ray_order_build_device", "rt_ray_order_set", "rt_ray_order_read",
     "rt_trace_rays_ordered", "rt_trace_rays_ordered_device",
@@ -122,6 +124,13 @@ def load():
     lib.rt_closest_points_device.argtypes = [C.c_void_p, C.POINTER(rt_point_batch), C.POINTER(rt_point_hits), C.c_void_p]
     lib.rt_closest_points_model.restype = C.c_int
     lib.rt_closest_points_model.argtypes = [C.POINTER(rt_scene_desc), C.POINTER(rt_point_batch), C.POINTER(rt_point_hits)]
+    for name, out in (("rt_contains_points", rt_solid_out), ("rt_signed_distance", rt_signed_distance_out)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(rt_solid_batch), C.POINTER(out)]
+        getattr(lib, name + "_device").restype = C.c_int
+        getattr(lib, name + "_device").argtypes = [C.c_void_p, C.POINTER(rt_solid_batch), C.POINTER(out), C.c_void_p]
+        getattr(lib, name + "_model").restype = C.c_int
+        getattr(lib, name + "_model").argtypes = [C.POINTER(rt_scene_desc), C.POINTER(rt_solid_batch), C.POINTER(out)]
     lib.rt_trace_rays.restype = C.c_int
     lib.rt_trace_rays.argtypes = [C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_ray_batch), C.POINTER(rt_ray_radiance), C.POINTER(rt_stats)]
     lib.rt_trace_rays_device.restype = C.c_int

@@ -51,8 +51,8 @@
 // Split clipping needs no special case: the clipped references cover the triangle, so the reference whose (padded) box holds
 // the closest point is never skipped, every reference evaluates the WHOLE triangle, and duplicates give equal results.
 //
-// Out of scope: signed distance and inside tests (the meshes need not be closed), k nearest, a wave-cooperative walk for
-// coherent point sets such as grids, an ordered variant.
+// Signed distance and inside tests are rt_solid.h (the meshes need not be closed: it says what an open one gets).  Out of scope:
+// k nearest, a wave-cooperative walk for coherent point sets such as grids, an ordered variant.
 // Not part of the public ABI.
 #pragma once
 

@@ -10,6 +10,7 @@
 #include "rt_closest.h"     // (RtClosestArgs, rt_launch_closest: the kernel of rt_closest_points*, rt_closest.hip)
 #include "rt_multihit.h"    // (RtMultiHitArgs, rt_launch_multihit: the kernel of rt_list_intersections*, rt_multihit.hip)
 #include "rt_occlusion.h"   // (RtOcclusionArgs, rt_launch_occlusion: the kernels of rt_ambient_occlusion*, rt_occlusion.hip)
+#include "rt_solid.h"       // (RtSolidArgs, rt_launch_solid: the kernel of rt_contains_points* / rt_signed_distance*, rt_solid.hip)
 #include "rt_ray_key.h"     // (RtOrderWs)
 #include "rt_scene_pack.h"  // (rt_internal.h; rt_fail; the device-free scene packer and table builders)
 

@@ -63,9 +63,9 @@
 // Split clipping needs no special case: the clipped references cover the triangle, the reference whose widened box holds the
 // hit point is reached, and it evaluates the whole triangle.
 //
-// Out of scope: inside / occupancy tests and signed distance (a sphere gives ONE hit, so crossing parity needs a definition of
-// its own); both roots of a sphere; K above RT_MAX_HITS_PER_RAY; an ordered or wave-cooperative variant for coherent rays; a
-// phase-1 prefilter like tri_hit's.
+// Inside / occupancy tests and signed distance are rt_solid.h (a sphere gives ONE hit, so crossing parity has a definition of
+// its own there).  Out of scope: both roots of a sphere; K above RT_MAX_HITS_PER_RAY; an ordered or wave-cooperative variant for
+// coherent rays; a phase-1 prefilter like tri_hit's.
 // Not part of the public ABI.
 #pragma once
 
@@ -151,12 +151,18 @@ RT_HD static inline bool rt_mh_ray(const float o[3], const float d_raw[3], RtMhR
 }
 
 // ---- the intersection tests --------------------------------------------------------------------------------------------------------
+// The two quantities of SphereData::intersect that do not depend on the direction: v = o - c and cc = v.v - r_sq.  cc < 0 exactly
+// where the test sees the origin INSIDE the sphere (its one hit is then the exit point): rt_solid.h decides containment with it.
+RT_HD static inline void rt_mh_sphere_v(const float c[3], const float o[3], float v[3]) {
+  for (int k = 0; k < 3; k++) v[k] = rt_fadd(o[k], -c[k]);
+}
+RT_HD static inline float rt_mh_sphere_cc(const float v[3], float r_sq) { return rt_fadd(rt_mh_dot(v, v), -r_sq); }
 // SphereData::intersect (sphere.rs:78-162) up to the choice of the root
 RT_HD static inline bool rt_mh_sphere(const float c[3], float r_sq, const RtMhRay& r, float* t_out) {
   float v[3];
-  for (int k = 0; k < 3; k++) v[k] = rt_fadd(r.o[k], -c[k]);
+  rt_mh_sphere_v(c, r.o, v);
   const float b = rt_fmul(2.0f, rt_mh_dot(r.d, v));
-  const float cc = rt_fadd(rt_mh_dot(v, v), -r_sq);
+  const float cc = rt_mh_sphere_cc(v, r_sq);
   const float disc = fmaf(b, b, rt_fmul(-4.0f, cc));
   const float sq = rt_fsqrt(disc);
   const float mba = rt_fmul(-b, 0.5f), sa = rt_fmul(sq, 0.5f);

@@ -14,6 +14,7 @@
 #include "rt_lbvh.h"
 #include "rt_multihit.h"
 #include "rt_occlusion.h"
+#include "rt_solid.h"
 #include "rt_refit.h"
 #include "rt_ploc.h"
 #include "rt_sah.h"
@@ -481,6 +482,21 @@ void rt_multihit_packed(const RtPackedScene& pk, const RtMultiHitArgs& a) {
 void rt_occlusion_packed(const RtPackedScene& pk, const RtOcclusionArgs& a) {
   const RtMhBlob S = {pk.dev, (const char*)pk.blob.data()};
   for (uint32_t i = 0; i < a.n; i++) rt_occ_query_host(S, RtOccArgsRef{a}, i);
+}
+
+int rt_check_solid(const RtDevScene& dev, const char* fn) {
+  if (dev.n_slots > dev.n_triangles)
+    return rt_fail(RT_ERR_UNSUPPORTED, "%s: the tree was built with split clipping (%u references of %u triangles); "
+                   "a counting walk would count a triangle once per reference", fn, dev.n_slots, dev.n_triangles);
+  return RT_OK;
+}
+
+int rt_solid_packed(const RtPackedScene& pk, const RtSolidArgs& a) {
+  const int rc = rt_check_solid(pk.dev, "rt_solid_packed");
+  if (rc != RT_OK) return rc;
+  const RtMhBlob S = {pk.dev, (const char*)pk.blob.data()};
+  for (uint32_t i = 0; i < a.n; i++) rt_solid_query(S, RtSolidArgsRef{a}, i, true);
+  return RT_OK;
 }
 
 int rt_pack_scene(const rt_scene_desc* d, uint64_t budget, RtPackedScene* o) {

@@ -119,6 +119,17 @@ void rt_multihit_packed(const RtPackedScene& pk, const RtMultiHitArgs& a);
 struct RtOcclusionArgs;
 void rt_occlusion_packed(const RtPackedScene& pk, const RtOcclusionArgs& a);
 
+// ---- containment and signed-distance queries (rt_contains_points*, rt_signed_distance*; the arithmetic and the walk: rt_solid.h) --
+// what these queries refuse of a scene, without a device: a split-clipped tree (RT_ERR_UNSUPPORTED; the message names the
+// reference and triangle counts), as rt_check_scene_delta and rt_check_rebuild do
+int rt_check_solid(const RtDevScene& dev, const char* fn);
+// The KERNEL's walk -- spheres by their cc, per direction the threaded walk with rt_mh_box_enter at the limit +inf, counting --
+// over the packed blob for a batch of HOST arrays: the same functions rt_solid_kernel is made of, so the pruning is checked on
+// the CPU against the linear scan of rt_contains_points_model.  With a.signed_distance it reads a.distance, as the kernel does
+// (rt_closest_packed writes that plane).  Returns rt_check_solid's code; nothing is written when it refuses.
+struct RtSolidArgs;
+int rt_solid_packed(const RtPackedScene& pk, const RtSolidArgs& a);
+
 // ---- parameter tables of a frame -----------------------------------------------------------------------------------------
 // AA samples: the distinct offsets in first-occurrence order (compared as values; `dedup` off: every sample is distinct),
 // their multiplicities and the sample -> thread map, as the device image [2U offsets (float bits) | U | n].  Returns U.

@@ -89,6 +89,29 @@ class Occlusion(NamedTuple):
     bits: Any
 
 
+class Containment(NamedTuple):
+    """Inside test per point (`rt_solid_out`): `inside` (n,) bool; `votes` (n,) uint8, the directions that voted inside -- a value
+    other than 0 or R means the directions disagree: the point lies on or near a surface, or the surface is open or inconsistently
+    oriented there; `crossings` (n, R) triangles crossed and `winding` (n, R) leaving minus entering crossings per direction."""
+    inside: Any
+    votes: Any
+    crossings: Any
+    winding: Any
+
+
+class SignedDistance(NamedTuple):
+    """Signed distance per point (`rt_signed_distance_out`): `distance` (n,) is negative inside, positive outside, +-inf on a miss
+    of the closest-point search; `inside` and `votes` as in Containment; id, point, normal, bary and material as in ClosestPoints."""
+    distance: Any
+    inside: Any
+    votes: Any
+    id: Any
+    point: Any
+    normal: Any
+    bary: Any
+    material: Any
+
+
 class IntersectionTest(NamedTuple):
     """`IntersectionTest` (raytracer.rs:17-22) per segment.  color_filter is unspecified where completely_occluded."""
     has_intersection: Any
@@ -621,6 +644,67 @@ class DeviceScene:
         else:
             _lib.check(lib.rt_ambient_occlusion(self.handle, C.byref(b), C.byref(o)))
         return Occlusion(out["clear"], out["visibility"], out["bent_normal"], word_plane["bits"].reshape(n, words) if bits else None)
+
+    def _solid_batch(self, points, max_distance, directions, rule):
+        """-> (torch?, n, points, rt_solid_batch, the table it points to) for contains / signed_distance"""
+        from . import sampling
+
+        rules = {"parity": _abi.RT_SOLID_RULE_PARITY, "winding": _abi.RT_SOLID_RULE_WINDING}
+        if rule not in rules:
+            raise ValueError(f"rule {rule!r} is not one of {sorted(rules)}")
+        torch_in, n, p, _, m = self._batch(points, points, max_distance)
+        # the direction table is a host array in every entry point: it is small, validated by the library and passed by value
+        if directions is None:
+            table = sampling.solid_directions()
+        elif isinstance(directions, np.ndarray) or not hasattr(directions, "cpu"):
+            table = np.ascontiguousarray(directions, np.float32)
+        else:
+            table = np.ascontiguousarray(directions.cpu().numpy(), np.float32)
+        if table.ndim != 2 or table.shape[1] != 3 or not 1 <= table.shape[0] <= _abi.RT_MAX_SOLID_DIRECTIONS:
+            raise ValueError(f"directions must be (R, 3) with R in 1 .. {_abi.RT_MAX_SOLID_DIRECTIONS}, got {table.shape}")
+        ptr = (lambda a: a.data_ptr()) if torch_in else (lambda a: a.ctypes.data)
+        b = _abi.rt_solid_batch(_abi.RT_ABI_VERSION, int(n), ptr(p), ptr(m) if m is not None else None, int(table.shape[0]), rules[rule],
+                                table.ctypes.data)
+        return torch_in, n, p, b, table
+
+    def contains(self, points, directions=None, rule: str = "parity") -> "Containment":
+        """`rt_contains_points` for a batch of points: whether each lies inside the closed surfaces of the scene.  Along each of
+        the R (1 .. 8) rows of `directions` ((R, 3), any length; None: sampling.solid_directions()) a ray is cast from the point;
+        rule="parity": the direction votes inside when the triangles it crosses plus the spheres that contain the point are odd
+        in number; rule="winding": when the crossings that leave a surface (by its stored normal) minus those that enter one,
+        plus the containing spheres, are positive -- the rules differ where solids overlap.  A point is inside when more than half
+        of the directions say so.  `votes` other than 0 or R marks points on or near a surface and open or inconsistently
+        oriented surfaces.  Same input kinds as cast_rays: numpy arrays (the host entry point; numpy results) or torch tensors on
+        this scene's device (the _device entry point on torch.cuda.current_stream(); tensor results, no synchronisation;
+        crossings is int32 there)."""
+        torch_in, n, p, b, keep = self._solid_batch(points, None, directions, rule)
+        r = b.n_directions
+        out, ptr = self._planes(dict, p, n, ("inside", "bool", 1), ("votes", "uint8", 1))
+        rows, _ = self._planes(dict, p, n * r, ("crossings", "int32" if torch_in else "uint32", 1), ("winding", "int32", 1))
+        o = _abi.rt_solid_out(ptr(out["inside"]), ptr(out["votes"]), ptr(rows["crossings"]), ptr(rows["winding"]))
+        lib = _lib.load()
+        if torch_in:
+            _lib.check(lib.rt_contains_points_device(self.handle, C.byref(b), C.byref(o), self._stream_of(p)))
+        else:
+            _lib.check(lib.rt_contains_points(self.handle, C.byref(b), C.byref(o)))
+        return Containment(out["inside"], out["votes"], rows["crossings"].reshape(n, r), rows["winding"].reshape(n, r))
+
+    def signed_distance(self, points, max_distance=None, directions=None, rule: str = "parity") -> "SignedDistance":
+        """`rt_signed_distance` for a batch of points: closest_points' answer for each -- the same bits -- with the distance
+        negated where `contains` says inside.  max_distance (None = +inf) bounds the closest-point search only: a point with
+        nothing in reach gets +inf outside and -inf inside.  directions and rule as in contains; same input kinds."""
+        torch_in, n, p, b, keep = self._solid_batch(points, max_distance, directions, rule)
+        out, ptr = self._planes(SignedDistance, p, n, ("distance", "float32", 1), ("inside", "bool", 1), ("votes", "uint8", 1), ("id", "int32", 1),
+                                ("point", "float32", 3), ("normal", "float32", 3), ("bary", "float32", 2),
+                                ("material", "int32" if torch_in else "uint32", 1))
+        o = _abi.rt_signed_distance_out(ptr(out.distance), _abi.rt_solid_out(ptr(out.inside), ptr(out.votes), None, None),
+                                        _abi.rt_point_hits(ptr(out.id), None, ptr(out.point), ptr(out.normal), ptr(out.bary), ptr(out.material)))
+        lib = _lib.load()
+        if torch_in:
+            _lib.check(lib.rt_signed_distance_device(self.handle, C.byref(b), C.byref(o), self._stream_of(p)))
+        else:
+            _lib.check(lib.rt_signed_distance(self.handle, C.byref(b), C.byref(o)))
+        return out
 
     def ray_order(self, origins, directions, origin_bits: int = 0) -> RayOrder:
         """A RayOrder for these rays on this scene's device, sorted on the device by the Morton code of origin and

@@ -152,3 +152,23 @@ def hemisphere_samples(n: int) -> np.ndarray:
     phi = k * (math.pi * (3.0 - math.sqrt(5.0)))
     r = np.sqrt(r2)
     return np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r2)], axis=1).astype(np.float32)
+
+
+def solid_directions() -> np.ndarray:
+    """The default direction table of `DeviceScene.contains` and `signed_distance`: the three rows (1, 2, 3), (2, -3, 1) and
+    (-3, -1, 2), (3, 3) float32 (the query normalises them).  They are pairwise near-orthogonal (cosines of magnitude 1/14), and
+    none is parallel to an axis or a face diagonal, so the rays of a grid over axis-aligned slabs never run exactly along a
+    slab edge.  An odd number of rows: the majority vote has no tie."""
+    return np.array([(1, 2, 3), (2, -3, 1), (-3, -1, 2)], np.float32)
+
+
+def grid_points(lo, hi, shape) -> np.ndarray:
+    """The points of a regular grid over the box lo .. hi, both ends included: shape = (nx, ny, nz) points per axis (one point
+    on an axis sits at lo), (nx * ny * nz, 3) float32 with x varying slowest and z fastest -- `result.reshape(nx, ny, nz)` of a
+    per-point plane is the volume.  Computed in float64 and cast."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    shape = tuple(int(s) for s in shape)
+    if lo.shape != (3,) or hi.shape != (3,) or len(shape) != 3 or min(shape) < 1:
+        raise ValueError("grid_points: lo and hi are 3-vectors, shape is three positive counts")
+    axes = [np.linspace(lo[a], hi[a], shape[a]) if shape[a] > 1 else np.array([lo[a]]) for a in range(3)]
+    return np.ascontiguousarray(np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 3), np.float32)

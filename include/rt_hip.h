@@ -37,6 +37,9 @@
  *                                   rt_ambient_occlusion_model is its specification
  *   rt_closest_points[_device]   <- none (the reference has no point query): the nearest surface point per query
  *                                   point, Embree's rtcPointQuery; rt_closest_points_model is its specification
+ *   rt_contains_points[_device], rt_signed_distance[_device] <- none: whether a point lies inside the closed surfaces of
+ *                                   the scene, by crossing parity or winding along up to 8 directions, and the signed
+ *                                   distance to the surface; the two _model functions are their specification
  *   rt_trace_rays     <- RaytracerRenderer::single_raytrace, src/renderer/raytracer_renderer.rs:147-264 (the colour of
  *                        a ray: nearest hit, the lights' shadow and transmittance rays, soft-shadow clouds, attenuation,
  *                        reflection and refraction trees), for a batch of HOST rays; blocks
@@ -499,8 +502,8 @@ int rt_any_intersection_device(rt_scene* scene, const rt_ray_batch* batch, const
  * have finished before rt_scene_update* / rt_scene_rebuild* (and the pose and skin calls, which update), exactly as the ray
  * queries.
  *
- * Not offered: signed distance and inside tests (the meshes need not be closed), the k nearest objects, a walk shared by the
- * wavefront for coherent point sets such as grids, and an ordered variant. */
+ * Signed distance and inside tests: rt_signed_distance* and rt_contains_points* below.  Not offered: the k nearest objects, a
+ * walk shared by the wavefront for coherent point sets such as grids, and an ordered variant. */
 typedef struct rt_point_batch {
   uint32_t abi_version;      /* RT_ABI_VERSION */
   uint32_t n_points;         /* 0 is a valid no-op */
@@ -558,8 +561,9 @@ int rt_closest_points_model(const rt_scene_desc* desc, const rt_point_batch* bat
  *
  * Streams and concurrency: as the ray queries above.
  *
- * Not offered: inside / occupancy tests and signed distance (a sphere gives one hit, so crossing parity needs a definition of
- * its own), both roots of a sphere, K above RT_MAX_HITS_PER_RAY, an ordered or wave-cooperative variant. */
+ * Inside / occupancy tests and signed distance: rt_contains_points* and rt_signed_distance* below (a sphere gives one hit, so
+ * crossing parity has a definition of its own).  Not offered: both roots of a sphere, K above RT_MAX_HITS_PER_RAY, an ordered
+ * or wave-cooperative variant. */
 #define RT_MAX_HITS_PER_RAY 16u
 
 /* request and output of rt_list_intersections*.  Every output member nullable, at least one non-NULL: a NULL plane is not written. */
@@ -657,6 +661,97 @@ int rt_ambient_occlusion_model(const rt_scene_desc* desc, const rt_occlusion_bat
  * world direction of each sample BEFORE normalisation (a ray batch of these origins and directions is normalised exactly as
  * the query normalises them); alive [n_points], 0 for a dead point. */
 int rt_occlusion_rays_model(const rt_occlusion_batch* batch, float* origin, float* direction, uint8_t* alive);
+
+/* ---- containment and signed-distance queries for closed surfaces -------------------------------------------------------------------
+ *
+ * "Is this point inside something, and how deep?" (trimesh's contains / signed_distance, Open3D's occupancy and SDF grids), on
+ * whatever the handle holds after rt_scene_update*, rt_pose_apply*, rt_skin_apply* and rt_scene_rebuild*: collision and
+ * voxelisation loops against the current pose without a host round trip.
+ *
+ * Definition (csrc/rt_solid.h holds the formulas; every float result is one correctly rounded operation or an fmaf).  A batch
+ * is n points, a table of R = n_directions rows (1 .. RT_MAX_SOLID_DIRECTIONS, any length; a HOST array in every entry point:
+ * it is validated and passed to the kernel by value) and a rule.  Per point p and direction r a ray is cast from p along row
+ * r, normalised as every ray's direction is, without bias and without max_distance.  A CROSSING is a triangle the ray hits as
+ * rt_list_intersections defines a hit (the literal test, no culling, transmissive objects included).
+ *   crossings[i][r]  the number of distinct triangles crossed
+ *   winding[i][r]    the sum over the crossings of the sign of dot(direction, stored normal): +1 where the ray leaves through
+ *                    the triangle, -1 where it enters, 0 for a zero or NaN product.  The orientation is the stored normal's,
+ *                    never the vertex order's.
+ *   spheres          are decided analytically: a sphere contains p when |p - c|^2 - r_sq < 0 as the sphere test computes it (a NaN
+ *                    or negative r_sq never contains); k_s = the number of containing spheres.
+ *   the vote of r    RT_SOLID_RULE_PARITY: (crossings + k_s) & 1;  RT_SOLID_RULE_WINDING: winding + k_s > 0.
+ *   votes[i] = the directions voting inside; inside[i] = 2 votes > R.  R odd is recommended; a tie at an even R is outside.
+ * The rules differ where solids overlap: in the intersection of two boxes parity says outside, winding says inside.
+ *
+ * Open and inconsistent surfaces get a defined, diagnosable answer, not a refusal: votes not in {0, R} means the directions
+ * disagree -- the point lies on or near a surface, or the surface is open or inconsistently oriented there.  (The letters of the
+ * built-in text meshes are open surfaces; this is how they show.)
+ *
+ * Dead points: a point with a non-finite coordinate gets inside 0, votes 0, crossings 0, winding 0.
+ *
+ * Signed distance: rt_closest_points' result for the point, unchanged bit for bit, every plane of it available, and
+ * signed_distance = inside ? -distance : distance (a miss is +inf or -inf).  max_distance applies to the closest-point search
+ * only; rt_contains_points* ignore it.
+ *
+ * The result is a function of the scene description and the batch alone: it does not depend on the tree, on slot order or on the
+ * order a walk meets crossings in.
+ *
+ * Split-clipped trees (rt_bvh_tuning.split_depth > 0; off by default) are refused with RT_ERR_UNSUPPORTED, as rt_scene_update
+ * and rt_scene_rebuild refuse them: every reference of such a triangle evaluates the whole triangle, so a counting walk would
+ * count it once per reference reached.
+ *
+ * Validation (RT_ERR_INVALID_ARG + rt_last_error, before any HIP call; nothing is written): a NULL scene, description, batch or
+ * out; a wrong abi_version; NULL point with n_points > 0; NULL directions; n_directions outside 1 .. RT_MAX_SOLID_DIRECTIONS;
+ * a row that does not normalise to finite components, not all zero (a zero, NaN or infinite row, one whose squared length under-
+ * or overflows); an unknown rule; every output NULL.
+ * n_points == 0 is a valid no-op.
+ *
+ * Streams and concurrency: as the ray queries above.
+ *
+ * Not offered: generalized winding numbers, a watertight triangle test, split-clipped trees, per-object containment ids, a flag
+ * that skips transmissive objects, the k nearest objects. */
+#define RT_MAX_SOLID_DIRECTIONS 8u
+#define RT_SOLID_RULE_PARITY 0u
+#define RT_SOLID_RULE_WINDING 1u
+
+typedef struct rt_solid_batch {
+  uint32_t abi_version;       /* RT_ABI_VERSION */
+  uint32_t n_points;          /* 0 is a valid no-op */
+  const float* point;         /* [n_points][3] */
+  const float* max_distance;  /* [n_points] search radius of the closest-point part of rt_signed_distance*; NULL = +inf */
+  uint32_t n_directions;      /* R: 1 .. RT_MAX_SOLID_DIRECTIONS */
+  uint32_t rule;              /* RT_SOLID_RULE_PARITY or RT_SOLID_RULE_WINDING */
+  const float* directions;    /* [R][3] HOST array in every entry point, any length */
+} rt_solid_batch;
+
+/* output of rt_contains_points*.  Every member nullable, at least one non-NULL: a NULL plane is not written. */
+typedef struct rt_solid_out {
+  uint8_t* inside;     /* [n_points] 0 or 1 */
+  uint8_t* votes;      /* [n_points] directions voting inside, 0 .. R */
+  uint32_t* crossings; /* [n_points][R] */
+  int32_t* winding;    /* [n_points][R] */
+} rt_solid_out;
+
+/* output of rt_signed_distance*.  Every member nullable, at least one non-NULL: a NULL plane is not written. */
+typedef struct rt_signed_distance_out {
+  float* signed_distance; /* [n_points] inside ? -distance : distance */
+  rt_solid_out solid;     /* as rt_contains_points */
+  rt_point_hits closest;  /* as rt_closest_points */
+} rt_signed_distance_out;
+
+/* HOST arrays: staged through device memory allocated for the call; returns when the results are in host memory. */
+int rt_contains_points(rt_scene* scene, const rt_solid_batch* batch, const rt_solid_out* out);
+int rt_signed_distance(rt_scene* scene, const rt_solid_batch* batch, const rt_signed_distance_out* out);
+/* DEVICE arrays on the scene's device (points, max_distance and every output; the direction table stays a HOST array): enqueued
+ * on `hip_stream` (NULL = default stream); allocates nothing.  rt_signed_distance_device enqueues the closest-point kernel and
+ * then the containment kernel, which reads the distance plane; it needs no plane beyond those asked for (without
+ * closest.distance the unsigned distance travels in the signed_distance plane itself). */
+int rt_contains_points_device(rt_scene* scene, const rt_solid_batch* batch, const rt_solid_out* out, void* hip_stream);
+int rt_signed_distance_device(rt_scene* scene, const rt_solid_batch* batch, const rt_signed_distance_out* out, void* hip_stream);
+/* The specification, without a device or a tree: a LINEAR scan of `desc` with the same arithmetic.  HOST arrays; no HIP call.
+ * The calls above return the same bits. */
+int rt_contains_points_model(const rt_scene_desc* desc, const rt_solid_batch* batch, const rt_solid_out* out);
+int rt_signed_distance_model(const rt_scene_desc* desc, const rt_solid_batch* batch, const rt_signed_distance_out* out);
 
 /* ---- radiance queries: Whitted shading of caller-supplied rays -------------------------------------------------------------
  *
